@@ -11,7 +11,7 @@ VIMA-200M, batch 256 per GPU, 512-token prompt (32 x [8 words + 1 image -> 8 obj
 Multi-GPU = data parallel, weak scaling: every rank evaluates its own batch of 256 with a full weight replica and the
 only collective is one all-gather of the [256,700] logits per step (vima_allgather_logits in the C ABI, RCCL over xGMI).
 `python bench.py --gpus N` on its own re-launches itself with N ranks; it exits non-zero when fewer than N GPUs are visible.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0. `--dump-outputs DIR` also writes the logits of the last timed step to DIR/logits.npy.
 """
 from __future__ import annotations
 
@@ -221,6 +221,27 @@ def rccl_summary(path, max_chars=1500):
     pick["log_lines"] = len(lines)
     out = {k: v for k, v in pick.items() if v}
     return out or None
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs DIR: what the timed path returned in its last step, one DIR/<name>.npy per array in float32, so that two builds can
+    be compared output for output on the same seeded inputs. When the arrays exceed 64 MB together, every array keeps the same fixed,
+    seeded sample of its rows, and the row indices go to DIR/<name>_rows.npy (float64)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(a.numel() * 4 for a in arrays.values())
+    budget = DUMP_LIMIT_BYTES - (1 << 20)         # headroom for the row-index files and the .npy headers
+    for name, a in arrays.items():
+        a = a.detach().float().cpu()
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, a.shape[0] * budget // total)
+            rows = torch.randperm(a.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            a = a[rows]
+            np.save(os.path.join(dirname, f"{name}_rows.npy"), rows.double().numpy())
+        np.save(os.path.join(dirname, f"{name}.npy"), a.contiguous().numpy())
 
 
 def usable_cores() -> int:
@@ -507,9 +528,11 @@ def bench_baseline_policy(args):
     assert torch.isfinite(logits).all() and tuple(logits.shape) == (B, 700)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        logits, _ = step()
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) / args.steps * 1e3
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"logits": logits})
     pol.prof_enable(True)
     pol.set_option("dual_stream", 0)
     step()
@@ -562,7 +585,11 @@ def main():
                     "and teardown. No GPU, no policy, no measurement: the line it prints is marked dry_run")
     ap.add_argument("--no-side-configs", action="store_true", help="skip the other BASELINE.json configurations (VIMA-20M batch 32, Lp = 1024 in bf16 "
                     "and fp8, T = 8) that the default run reports under config.secondary_cold")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step returned "
+                    "(the [global batch, 700] action logits) to DIR/logits.npy in float32; the inputs are seeded, so two builds can be compared")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.policy != "vima":
         if args.gpus != 1 or os.environ.get("WORLD_SIZE", "1") != "1":
             sys.exit("bench.py --policy gpt|gato|flamingo is a single-GPU line")
@@ -588,10 +615,11 @@ def main():
                "--master-port", str(port), os.path.abspath(__file__)] + argv + ["--gpus", str(args.dry_ranks)]
         sys.exit(subprocess.call(cmd, env=dict(os.environ, VIMA_BENCH_DRY="1", OMP_NUM_THREADS="1")))
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
-        visible = torch.cuda.device_count()
-        if visible < args.gpus and not shared_gpu:
-            sys.exit(f"bench.py: --gpus {args.gpus} requested but only {visible} GPU(s) are visible on this node; refusing to "
-                     f"print a {visible}-GPU number as a {args.gpus}-GPU result")
+        if not shared_gpu:           # counting devices starts the HIP runtime: in the shared-GPU test mode the launcher never opens the GPU
+            visible = torch.cuda.device_count()
+            if visible < args.gpus:
+                sys.exit(f"bench.py: --gpus {args.gpus} requested but only {visible} GPU(s) are visible on this node; refusing to "
+                         f"print a {visible}-GPU number as a {args.gpus}-GPU result")
         import socket
         import subprocess
         sk = socket.socket()
@@ -760,6 +788,8 @@ def main():
                       "note": "ms_per_step_own: each rank's K steps up to its own device synchronize (no barrier); allgather_us: HIP events around the "
                               "logits all-gather on its stream, mean over the timed steps (includes waiting for the slowest rank to arrive)"}
     assert out.shape == (B * world, 700) and bool(torch.isfinite(out).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"logits": out})
     ms_per_step = dt / args.steps * 1e3
     collective_info = None
     if rccl_log and rank == 0:

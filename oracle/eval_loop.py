@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import ast
 import collections.abc
+import json
 import os
 import sys
 import types
@@ -221,6 +222,46 @@ def compare_logs(a, b, atol=0.0):
                 else:
                     assert va == vb, (where, va, vb)
     return n
+
+
+def save_log(path, log, actions):
+    """Store a RecordingPolicy log and the actions sent to the environment as one .npz: every tensor / action array as an array of
+    its own, the nesting (dicts, lists, ints, None) as a JSON skeleton. No pickles: load_log() rebuilds both."""
+    arrays = []
+
+    def enc(x):
+        if torch.is_tensor(x):
+            arrays.append(x.numpy())
+            return {"t": len(arrays) - 1}
+        if isinstance(x, dict):
+            return {"d": [[k, enc(v)] for k, v in x.items()]}
+        if isinstance(x, list):
+            return {"l": [enc(v) for v in x]}
+        assert x is None or isinstance(x, (bool, int, float, str)), type(x)
+        return {"v": x}
+
+    skel = {"calls": [[c[0]] + [enc(p) for p in c[1:]] for c in log],
+            "actions": [enc({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in a.items()}) for a in actions]}
+    np.savez_compressed(path, _skeleton=np.array(json.dumps(skel)), **{f"a{i}": a for i, a in enumerate(arrays)})
+
+
+def load_log(path):
+    """-> (log, actions) as written by save_log: the log in RecordingPolicy's form, the actions as dicts of numpy arrays."""
+    z = np.load(path)
+    skel = json.loads(str(z["_skeleton"]))
+
+    def dec(e):
+        if "t" in e:
+            return torch.from_numpy(z[f"a{e['t']}"].copy())
+        if "d" in e:
+            return {k: dec(v) for k, v in e["d"]}
+        if "l" in e:
+            return [dec(v) for v in e["l"]]
+        return e["v"]
+
+    log = [tuple([c[0]] + [dec(p) for p in c[1:]]) for c in skel["calls"]]
+    actions = [{k: v.numpy() for k, v in dec(a).items()} for a in skel["actions"]]
+    return log, actions
 
 
 def load_reference_loop(policy, env, device="cpu"):

@@ -6,8 +6,11 @@ proven as a chain:
      replaced by synthetic stand-ins (oracle/eval_loop.py) -- and this repository's swap-in loop
      (examples/reference_loop.run_episode) are driven with the SAME recording policy (the unmodified reference VIMAPolicy):
      every policy call, argument, keyword name and result, and every action sent to the environment, must be identical;
-  2. (CPU, anywhere) the golden action trace of that run (tests/golden/eval_loop_20M.npz, written by
-     `python -m tests.test_eval_loop --write-golden` in the build container) is reproduced by the swap-in loop on the oracle;
+     That run's call log and the actions it sent to the environment are stored (tests/golden/eval_loop_20M_calls.npz), and on
+     any machine the swap-in loop, answered call by call with the reference policy's stored results, must make exactly the
+     stored calls and send the stored actions;
+  2. (CPU, anywhere) the golden action trace of that run (tests/golden/eval_loop_20M.npz; both files are written by
+     `python -m tests.test_eval_loop --write-golden` where the reference tree is present) is reproduced by the swap-in loop on the oracle;
   3. (GPU box) the swap-in loop runs on `vima_amd` -- policy AND image preprocessing on the GPU -- and reproduces the golden
      discrete actions of the reference: identical in fp32-operand mode over all env steps, agreement rate reported for bf16;
      the incremental `forward_step` form gives the same actions."""
@@ -30,6 +33,7 @@ import reference_loop                                       # noqa: E402  (examp
 MODEL, STEPS, N_OBJ, ENV_SEED, WSEED = "20M", 6, 4, 3, 7
 MISSING = {2: (3,), 4: (2, 5)}            # objects that vanish in steps 2 / 4: masked slots, reference slot order
 GOLDEN = os.path.join(ROOT, "tests", "golden", "eval_loop_20M.npz")
+CALLS = os.path.join(ROOT, "tests", "golden", "eval_loop_20M_calls.npz")
 KEYS = ("pose0_position", "pose0_rotation", "pose1_position", "pose1_rotation")
 
 
@@ -87,22 +91,55 @@ def _reference_run():
     return pol, env, log
 
 
-@pytest.mark.skipif(not ref_shim.reference_available(), reason="reference tree not present")
-def test_swap_in_loop_makes_exactly_the_reference_loops_calls():
-    pol, env_ref, log_ref = _reference_run()
-    assert len(env_ref.actions) == STEPS and [c[0] for c in log_ref].count("forward") == STEPS
-    rec = eval_loop.RecordingPolicy(pol)
+class _ReplayPolicy:
+    """Answers the loop's policy calls, in order, with the results the reference policy returned in the stored run of the
+    reference's own loop; a call the stored run did not make next fails at once."""
+
+    def __init__(self, log):
+        self._log, self._i = log, 0
+
+    def __getattr__(self, name):
+        if name not in eval_loop.RecordingPolicy.LOGGED:
+            raise AttributeError(name)
+
+        def call(*args, **kwargs):
+            assert self._i < len(self._log), f"call {self._i} ({name}) is beyond the stored run"
+            want, result = self._log[self._i][0], self._log[self._i][3]
+            assert want == name, f"call {self._i}: the reference loop called {want}, the swap-in loop {name}"
+            self._i += 1
+            if name == "forward_action_decoder":
+                return {k: _OracleAsPolicy._Mode(v.clone()) for k, v in result.items()}
+            if isinstance(result, list):
+                return tuple(t.clone() for t in result)
+            return {k: v.clone() for k, v in result.items()} if isinstance(result, dict) else result.clone()
+        return call
+
+
+def _check_swap_in_against(log_ref, actions_ref, policy):
+    """The swap-in loop around `policy` makes the calls of `log_ref` (identical tensors at every call boundary) and sends the
+    environment the actions `actions_ref`."""
+    assert len(actions_ref) == STEPS and [c[0] for c in log_ref].count("forward") == STEPS
+    rec = eval_loop.RecordingPolicy(policy)
     env = _env()
     records = _run_swap_in(rec, env)
     n = eval_loop.compare_logs(log_ref, rec.log)              # identical tensors at every call boundary
     assert n > 100
-    for a, b in zip(env_ref.actions, env.actions):            # what the simulator would have received
+    assert len(env.actions) == len(actions_ref)
+    for a, b in zip(actions_ref, env.actions):                # what the simulator would have received
         for k in KEYS:
             assert a[k].dtype == b[k].dtype and np.array_equal(a[k], b[k]), k
-    if os.path.exists(GOLDEN):                                # the committed trace is this run
-        gold = np.load(GOLDEN)
-        for k in KEYS:
-            assert np.array_equal(gold[k], _discrete(records)[k]), k
+    gold = np.load(GOLDEN)                                    # the committed trace is this run
+    for k in KEYS:
+        assert np.array_equal(gold[k], _discrete(records)[k]), k
+
+
+def test_swap_in_loop_makes_exactly_the_reference_loops_calls():
+    """Against the stored run of the reference's loop, and live where the reference tree is present."""
+    log_ref, actions_ref = eval_loop.load_log(CALLS)
+    _check_swap_in_against(log_ref, actions_ref, _ReplayPolicy(log_ref))
+    if ref_shim.reference_available():
+        pol, env_ref, log_live = _reference_run()
+        _check_swap_in_against(log_live, env_ref.actions, pol)
 
 
 def test_swap_in_loop_on_the_oracle_reproduces_the_reference_trace():
@@ -149,6 +186,8 @@ def _write_golden():
     os.makedirs(os.path.dirname(GOLDEN), exist_ok=True)
     np.savez(GOLDEN, **out)
     print("wrote", GOLDEN, {k: v.shape for k, v in out.items()})
+    eval_loop.save_log(CALLS, log, env.actions)
+    print("wrote", CALLS, f"{len(log)} calls, {len(env.actions)} actions")
 
 
 if __name__ == "__main__":

@@ -1,5 +1,7 @@
 """Host-side logic of the VIMAPolicy mirror that needs no GPU: prompt assembly index, action (de)discretisation, the
 MultiCategorical wrapper, constructor errors, and the algorithmic FLOP count used as the roofline numerator."""
+import collections.abc
+
 import numpy as np
 import pytest
 import torch
@@ -108,21 +110,37 @@ def test_bench_helpers_without_gpu():
         assert default in line, line
 
 
-def test_obj_inputs_accept_the_reference_datadict():
-    """The boundary is fed by the reference's own container in scripts/example.py (`vima.utils.DataDict`,
-    /root/reference/vima/utils.py:228, a MutableMapping that is NOT a dict subclass): VIMAPolicy._obj_inputs must flatten
-    and order it exactly like the plain-dict path. Needs the reference tree (build container only)."""
-    from oracle import ref_shim
-    if not ref_shim.reference_available():
-        pytest.skip("reference tree not present")
-    ref_shim.load_reference()
-    from vima.utils import DataDict
+class _NestedMapping(collections.abc.MutableMapping):
+    """A mapping that is NOT a dict subclass and wraps nested dicts on access -- the two properties of the reference's
+    `vima.utils.DataDict` that the boundary has to cope with."""
+
+    def __init__(self, d):
+        self._d = dict(d)
+
+    def __getitem__(self, k):
+        v = self._d[k]
+        return _NestedMapping(v) if isinstance(v, dict) else v
+
+    def __setitem__(self, k, v):
+        self._d[k] = v
+
+    def __delitem__(self, k):
+        del self._d[k]
+
+    def __iter__(self):
+        return iter(self._d)
+
+    def __len__(self):
+        return len(self._d)
+
+
+def _check_obj_inputs_accept(container):
     cfg = syn.config("2M")
     pol = VIMAPolicy(**cfg.ctor_kwargs())
     obs = syn.make_obs(2, 3, 2, seed=3)
     plain = {k: {v: t for v, t in d.items()} for k, d in obs["objects"].items()}
-    dd = DataDict({"objects": plain, "ee": obs["ee"]})
-    assert isinstance(dd["objects"], DataDict) and not isinstance(dd["objects"], dict)
+    dd = container({"objects": plain, "ee": obs["ee"]})
+    assert isinstance(dd["objects"], container) and not isinstance(dd["objects"], dict)
     a = pol._obj_inputs(dd["objects"], 2)
     b = pol._obj_inputs(obs["objects"], 2)
     assert a[3:] == b[3:] == (6, 2)
@@ -131,10 +149,23 @@ def test_obj_inputs_accept_the_reference_datadict():
             assert x.dtype == y.dtype and torch.equal(x, y)
     # the prompt side indexes image_batch the same way (vima_policy.py:164,193)
     imgs = syn.make_prompt(2, n_segments=2, words_per_segment=1, q_per_view=2, seed=4)[2]
-    dd_img = DataDict({k: {v: t for v, t in d.items()} for k, d in imgs.items()})
+    dd_img = container({k: {v: t for v, t in d.items()} for k, d in imgs.items()})
     for xs, ys in zip(pol._obj_inputs(dd_img, 1)[:3], pol._obj_inputs(imgs, 1)[:3]):
         for x, y in zip(xs, ys):
             assert torch.equal(x, y)
+
+
+def test_obj_inputs_accept_the_reference_datadict():
+    """The boundary is fed by the reference's own container in scripts/example.py (`vima.utils.DataDict`,
+    /root/reference/vima/utils.py:228, a MutableMapping that is NOT a dict subclass): VIMAPolicy._obj_inputs must flatten
+    and order it exactly like the plain-dict path. Checked with a stand-in of the same two properties everywhere, and with the
+    reference's DataDict itself where the reference tree is present."""
+    _check_obj_inputs_accept(_NestedMapping)
+    from oracle import ref_shim
+    if ref_shim.reference_available():
+        ref_shim.load_reference()
+        from vima.utils import DataDict
+        _check_obj_inputs_accept(DataDict)
 
 
 def _pmc_db(path, counter, rows):

@@ -3,7 +3,9 @@ the integer logic (bbox, crop, padding, slot order, masks, shapes, dtypes) again
 function body -- extracted from /root/reference/scripts/example.py with `ast` (the module itself cannot be imported:
 it needs vima_bench, gym, cv2 and the t5-base tokenizer from the Hub) and run with `cv2.resize` bound to the oracle's
 `resize_area_32`, since OpenCV is not installed here (parity of the resize arithmetic itself is UNPINNED, see the oracle
-header)."""
+header). What the reference's function returned is stored in tests/golden/reference_prepare_obs.npz (written by
+`python -m tests.test_preprocess_oracle --write-golden` where the reference tree is present), so the check runs anywhere; where
+the reference tree is present it also runs live."""
 import ast
 import os
 import sys
@@ -81,25 +83,59 @@ def _reference_prepare_obs():
     return ns["prepare_obs"]
 
 
-@pytest.mark.skipif(not ref_shim.reference_available(), reason="reference tree not present")
-@pytest.mark.parametrize("seed,missing", [(0, ()), (1, (3,)), (2, (2, 5))])
-def test_oracle_matches_the_references_prepare_obs(seed, missing):
-    L, n_obj = 2, 5
-    frames = {v: synthetic_frames(L, n_obj, seed=seed * 10 + i, missing=missing) for i, v in enumerate(("front", "top"))}
-    obj_ids = frames["front"][2]
-    rgb = {v: frames[v][0] for v in frames}
-    segm = {v: frames[v][1] for v in frames}
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_prepare_obs.npz")
+CASES = [(0, ()), (1, (3,)), (2, (2, 5))]
+L, N_OBJ = 2, 5
+KEYS, VIEWS = ("cropped_img", "bbox", "mask"), ("front", "top")
+
+
+def _frames(seed, missing):
+    frames = {v: synthetic_frames(L, N_OBJ, seed=seed * 10 + i, missing=missing) for i, v in enumerate(VIEWS)}
+    return ({v: frames[v][0] for v in frames}, {v: frames[v][1] for v in frames}, frames["front"][2])
+
+
+def _reference_live(seed, missing):
+    """-> {key: {view: array}} of the reference's prepare_obs, or None where the shims do not cover its container plumbing."""
+    rgb, segm, obj_ids = _frames(seed, missing)
     prepare_obs = _reference_prepare_obs()
     obs = {"ee": np.zeros((L,), dtype=np.int64), "rgb": {v: rgb[v].copy() for v in rgb}, "segm": {v: segm[v].copy() for v in segm}}
-    meta = {"n_objects": n_obj, "obj_id_to_info": {i: {} for i in obj_ids}}
+    meta = {"n_objects": N_OBJ, "obj_id_to_info": {i: {} for i in obj_ids}}
     try:
         ref = prepare_obs(obs=obs, rgb_dict=None, meta=meta)
-    except (AttributeError, ImportError, NotImplementedError) as e:     # container plumbing the shims do not cover
-        pytest.skip(f"reference plumbing unavailable here: {e}")
+    except (AttributeError, ImportError, NotImplementedError):     # container plumbing the shims do not cover
+        return None
+    return {key: {v: np.asarray(ref["objects"][key][v]) for v in VIEWS} for key in KEYS}
+
+
+@pytest.mark.parametrize("seed,missing", CASES)
+def test_oracle_matches_the_references_prepare_obs(seed, missing):
+    rgb, segm, obj_ids = _frames(seed, missing)
+    g = np.load(GOLDEN)
+    refs = [{key: {v: g[f"s{seed}.{key}.{v}"] for v in VIEWS} for key in KEYS}]
+    if ref_shim.reference_available():
+        live = _reference_live(seed, missing)
+        if live is not None:
+            refs.append(live)
     want = prepare_obs_oracle(rgb, segm, obj_ids)
-    for key in ("cropped_img", "bbox", "mask"):
-        for v in ("front", "top"):
-            got = np.asarray(ref["objects"][key][v])
-            assert got.shape[:2] == (L, 1), (key, got.shape)           # [L_obs, 1, n_obj, ...] after the transpose
-            assert np.array_equal(got[:, 0], want[key][v]), (key, v)
-            assert got.dtype == want[key][v].dtype or key == "bbox", (key, got.dtype)
+    for ref in refs:
+        for key in KEYS:
+            for v in VIEWS:
+                got = ref[key][v]
+                assert got.shape[:2] == (L, 1), (key, got.shape)           # [L_obs, 1, n_obj, ...] after the transpose
+                assert np.array_equal(got[:, 0], want[key][v]), (key, v)
+                assert got.dtype == want[key][v].dtype or key == "bbox", (key, got.dtype)
+
+
+def _write_golden():
+    arrays = {}
+    for seed, missing in CASES:
+        live = _reference_live(seed, missing)
+        assert live is not None, "the reference's prepare_obs did not run here"
+        arrays.update({f"s{seed}.{key}.{v}": live[key][v] for key in KEYS for v in VIEWS})
+    np.savez_compressed(GOLDEN, **arrays)
+    print("wrote", GOLDEN, {k: (v.shape, str(v.dtype)) for k, v in arrays.items()})
+
+
+if __name__ == "__main__":
+    if "--write-golden" in sys.argv:
+        _write_golden()
