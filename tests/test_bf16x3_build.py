@@ -1,0 +1,79 @@
+"""Precision "bf16x3" (split-bf16 matrix products on fp32 operands) without a GPU: the public surface accepts it, the Python
+enum matches the header, and the two new kernels cross-compile for gfx950 scratch-free, within their register budget, on
+the bf16 matrix instruction and never on the fp32 one."""
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+from vima_amd import _lib
+from vima_amd.policy import VIMAPolicy
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+needs_hipcc = pytest.mark.skipif(not shutil.which(HIPCC) and not os.path.exists(HIPCC), reason="hipcc not available")
+
+
+def test_policy_accepts_bf16x3():
+    pol = VIMAPolicy(embed_dim=256, xf_n_layers=1, sattn_n_heads=8, xattn_n_heads=8, precision="bf16x3")
+    assert pol.precision == "bf16x3"
+
+
+def test_python_precision_matches_header():
+    with open(os.path.join(ROOT, "include", "vima_hip.h")) as f:
+        hdr = f.read()
+    m = re.search(r"VIMA_PRECISION_BF16X3\s*=\s*(\d+)", hdr)
+    assert m, "VIMA_PRECISION_BF16X3 missing from include/vima_hip.h"
+    assert _lib.PRECISION["bf16x3"] == int(m.group(1))
+    assert len(set(_lib.PRECISION.values())) == len(_lib.PRECISION)
+
+
+_compiled = {}
+
+
+def _compile(src):
+    if src not in _compiled:
+        out = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-result",
+                              "--cuda-device-only", "-S", os.path.join(ROOT, "vima_amd", "csrc", src), "-o", "-",
+                              "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-2000:]
+        _compiled[src] = (out.stdout, out.stderr)
+    return _compiled[src]
+
+
+def _usage(remarks):
+    res, name = {}, None
+    for line in remarks.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            res[name] = {}
+            continue
+        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
+        if m and name:
+            res[name][m.group(1).split(" ")[0]] = int(m.group(2))
+    return res
+
+
+def _body(asm, name):
+    start = re.search(r"^" + re.escape(name) + r":", asm, flags=re.M)
+    assert start, name
+    return asm[start.end():asm.index("s_endpgm", start.end())]
+
+
+# (source, kernel, expected instantiations, VGPR + AGPR budget per lane: 2 waves / SIMD for the 256-thread GEMM tile (two
+# workgroups per CU), 2 / SIMD for the single-wave attention kernel)
+@needs_hipcc
+@pytest.mark.parametrize("src,kernel,count,budget", [("gemm.hip", "gemm_x3_kernel", 10, 256), ("attention.hip", "attn_x3_kernel", 6, 256)])
+def test_split_kernels_compile_on_the_bf16_matrix_instruction(src, kernel, count, budget):
+    asm, remarks = _compile(src)
+    res = {k: v for k, v in _usage(remarks).items() if kernel in k}
+    assert len(res) == count, sorted(res)
+    for name, v in res.items():
+        assert v.get("ScratchSize", 0) == 0, (name, v)
+        assert v.get("VGPRs", 0) + v.get("AGPRs", 0) <= budget, (name, v)
+        body = _body(asm, name)
+        assert "v_mfma_f32_32x32x16_bf16" in body, name
+        assert "v_mfma_f32_32x32x2_f32" not in body, name

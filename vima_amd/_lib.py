@@ -44,7 +44,7 @@ def _header_abi_version() -> int:
 
 
 ABI_VERSION = _header_abi_version()
-PRECISION = {"fp32": 0, "bf16": 1, "fp8w": 2, "fp8": 3}
+PRECISION = {"fp32": 0, "bf16": 1, "fp8w": 2, "fp8": 3, "bf16x3": 4}   # include/vima_hip.h VIMA_PRECISION_*
 POLICY_KIND = {"vima": 0, "gpt": 1, "gato": 2, "flamingo": 3}   # VIMA_POLICY_* (include/vima_hip.h)
 
 # exported symbol -> (restype, argtypes); must list every function declared in include/vima_hip.h

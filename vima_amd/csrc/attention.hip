@@ -12,6 +12,7 @@
 //       ATTN_CAUSAL Attention._attn (components.py:51-80): /sqrt(d); w*b + -1e4*(1-b) causal fill; + key mask
 //     Masked keys carry the score finfo(fp32).min exactly like the reference (so an all-masked row degenerates to the
 //     same uniform distribution); the -1e4 causal fill is kept literally (no causal tile skipping).
+//  * attn_x3       : precision "bf16x3": attn_mfma's single-wave kernel on fp32 operands with split-bf16 products (3 bf16 MFMAs each).
 #include "kernels.h"
 #include <float.h>
 #include <type_traits>
@@ -403,6 +404,151 @@ __global__ __launch_bounds__(64) void attn_mfma_kernel(const AttnDev p) {
   if (qi < p.Lq) {
     const float inv = 1.0f / l_run;
     bf16_t* op = reinterpret_cast<bf16_t*>(p.out) + ((long long)b * p.Lq + qi) * p.ldo + h * D;
+#pragma unroll
+    for (int it = 0; it < OT; ++it)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int d = it * 32 + 8 * g + 4 * hi;
+        store4(op + d, make_float4(ot[it][4 * g] * inv, ot[it][4 * g + 1] * inv, ot[it][4 * g + 2] * inv,
+                                   ot[it][4 * g + 3] * inv));
+      }
+  }
+}
+
+// =============================================================================================== split-bf16 attention
+// precision "bf16x3": attn_mfma_kernel's single-wave formulation (S^T = K.Q^T with the key tile as the A operand, so that a
+// lane owns one query column; O^T += V^T.P^T) on fp32 Q / K / V / out, every product in split-bf16 (split_bf16x8: x = hi + lo,
+// a.b ~ hi_a.hi_b + hi_a.lo_b + lo_a.hi_b, three v_mfma_f32_32x32x16_bf16, correction terms first). Q is split once per wave,
+// K once per tile; V^T is staged in LDS as a hi and a lo bf16 plane. The probabilities stay fp32 for the running sum and are
+// split for the PV product. Score fix-up and mask semantics are attn_mfma_kernel's (key mask -FLT_MAX after scaling, causal
+// fill -1e4, T5 relative bias without 1/sqrt(d)); the running max starts at -inf, never at a finite sentinel.
+template <int D, int MODE>
+__global__ __launch_bounds__(64) void attn_x3_kernel(const AttnDev p) {
+  __shared__ __attribute__((aligned(16))) bf16_t vth[D * VT_STRIDE];
+  __shared__ __attribute__((aligned(16))) bf16_t vtl[D * VT_STRIDE];
+  constexpr int KD = D / 16;   // MFMA k-steps over the head dim
+  constexpr int OT = D / 32;   // 32-row tiles of O^T
+  const int lane = threadIdx.x;
+  const int hi = lane >> 5, l31 = lane & 31;
+  const int q0 = blockIdx.x * 32, h = blockIdx.y, b = blockIdx.z;
+  const float* Q = reinterpret_cast<const float*>(p.q);
+  const float* K = reinterpret_cast<const float*>(p.k);
+  const float* V = reinterpret_cast<const float*>(p.v);
+
+  const int qi = q0 + l31;
+  const int qrow = qi < p.Lq ? qi : p.Lq - 1;
+  bf16x8_t qh[KD], ql[KD];
+#pragma unroll
+  for (int dd = 0; dd < KD; ++dd) {
+    const float* qp = Q + ((long long)b * p.Lq + qrow) * p.ldq + h * D + dd * 16 + hi * 8;
+    split_bf16x8(load4(qp), load4(qp + 4), qh[dd], ql[dd]);
+  }
+  f32x16_t ot[OT];
+#pragma unroll
+  for (int it = 0; it < OT; ++it)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) ot[it][r] = 0.f;
+  float m_run = -INFINITY, l_run = 0.f;
+  const float* rb = (MODE == ATTN_T5) ? p.relbias + (long long)h * (2 * p.Lk - 1) + (p.Lk - 1) - qi : nullptr;
+  const uint8_t* km = p.kmask ? p.kmask + (long long)b * p.Lkr : nullptr;
+
+  for (int k0 = 0; k0 < p.Lk; k0 += 32) {
+    // ---- S^T tile: rows = 32 keys, cols = 32 queries
+    f32x16_t s;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s[r] = 0.f;
+    {
+      const int krow = (k0 + l31) < p.Lk ? (k0 + l31) : p.Lk - 1;
+      const float* kp = K + b * p.k_bs + (long long)krow * p.ldk + h * p.k_hs + hi * 8;
+#pragma unroll
+      for (int dd = 0; dd < KD; ++dd) {
+        bf16x8_t kh, kl;
+        split_bf16x8(load4(kp + dd * 16), load4(kp + dd * 16 + 4), kh, kl);
+        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kl, qh[dd], s, 0, 0, 0);
+        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kh, ql[dd], s, 0, 0, 0);
+        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kh, qh[dd], s, 0, 0, 0);
+      }
+    }
+    // ---- stage the hi / lo planes of V^T of this key tile (previous tile's readers are done: single wave + barrier)
+    __syncthreads();
+#pragma unroll
+    for (int c0 = 0; c0 < (32 * D / 4) / 64; ++c0) {
+      const int c = lane + c0 * 64;
+      const int key = c / (D / 4), dc = c % (D / 4);
+      const int vrow = (k0 + key) < p.Lk ? (k0 + key) : p.Lk - 1;
+      const float4 u = load4(V + b * p.v_bs + (long long)vrow * p.ldv + h * p.v_hs + dc * 4);
+      const float x4[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const bf16_t vh = f32_to_bf16(x4[e]);
+        vth[(dc * 4 + e) * VT_STRIDE + key] = vh;
+        vtl[(dc * 4 + e) * VT_STRIDE + key] = f32_to_bf16(x4[e] - bf16_to_f32(vh));
+      }
+    }
+    // ---- scores -> probabilities (fp32), online softmax
+    float x[16];
+    float mt = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+      float v;
+      if (key < p.Lk) {
+        const float madd = (km && !km[key]) ? -FLT_MAX : 0.0f;
+        if (MODE == ATTN_T5) {
+          v = s[r] + ((qi < p.Lq ? rb[key] : 0.f) + madd);
+        } else if (MODE == ATTN_CROSS) {
+          v = s[r] * p.scale + madd;
+        } else {
+          v = s[r] * p.scale;
+          if (key > qi + p.q_off) v = -1e4f;
+          v = v + madd;
+        }
+      } else {
+        v = -INFINITY;
+      }
+      x[r] = v;
+      mt = fmaxf(mt, v);
+    }
+    mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
+    const float m_new = fmaxf(m_run, mt);   // finite: key k0 < Lk is in this tile
+    const float alpha = __expf(m_run - m_new);
+    float pr[16];
+    float rs = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      pr[r] = __expf(x[r] - m_new);
+      rs += pr[r];
+    }
+    rs += __shfl_xor(rs, 32, 64);
+    l_run = l_run * alpha + rs;
+    m_run = m_new;
+#pragma unroll
+    for (int it = 0; it < OT; ++it)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) ot[it][r] *= alpha;
+    __syncthreads();
+    // ---- O^T += V^T . P^T   (two K=16 steps per 32-row tile of O^T, three MFMAs each)
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      bf16x8_t ph, pl;
+      split_bf16x8(make_float4(pr[half * 8 + 0], pr[half * 8 + 1], pr[half * 8 + 2], pr[half * 8 + 3]),
+                   make_float4(pr[half * 8 + 4], pr[half * 8 + 5], pr[half * 8 + 6], pr[half * 8 + 7]), ph, pl);
+#pragma unroll
+      for (int it = 0; it < OT; ++it) {
+        const int o = (it * 32 + l31) * VT_STRIDE + 16 * half + 4 * hi;
+        const uint2 h0 = *reinterpret_cast<const uint2*>(vth + o), h1 = *reinterpret_cast<const uint2*>(vth + o + 8);
+        const uint2 g0 = *reinterpret_cast<const uint2*>(vtl + o), g1 = *reinterpret_cast<const uint2*>(vtl + o + 8);
+        const bf16x8_t vh = __builtin_bit_cast(bf16x8_t, make_uint4(h0.x, h0.y, h1.x, h1.y));
+        const bf16x8_t vl = __builtin_bit_cast(bf16x8_t, make_uint4(g0.x, g0.y, g1.x, g1.y));
+        ot[it] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vl, ph, ot[it], 0, 0, 0);
+        ot[it] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh, pl, ot[it], 0, 0, 0);
+        ot[it] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh, ph, ot[it], 0, 0, 0);
+      }
+    }
+  }
+  if (qi < p.Lq) {
+    const float inv = 1.0f / l_run;
+    float* op = reinterpret_cast<float*>(p.out) + ((long long)b * p.Lq + qi) * p.ldo + h * D;
 #pragma unroll
     for (int it = 0; it < OT; ++it)
 #pragma unroll
@@ -1284,6 +1430,30 @@ int launch_attn_mfma(const AttnArgs& a, hipStream_t st) {
   }
   dim3 grid((unsigned)((a.Lq + 31) / 32), (unsigned)a.H, (unsigned)a.B);
 #define VIMA_ATTN(D_, M_) hipLaunchKernelGGL((attn_mfma_kernel<D_, M_>), grid, dim3(64), 0, st, d)
+  if (a.D == 32) {
+    if (a.mode == ATTN_T5) VIMA_ATTN(32, ATTN_T5);
+    else if (a.mode == ATTN_CROSS) VIMA_ATTN(32, ATTN_CROSS);
+    else VIMA_ATTN(32, ATTN_CAUSAL);
+  } else {
+    if (a.mode == ATTN_T5) VIMA_ATTN(64, ATTN_T5);
+    else if (a.mode == ATTN_CROSS) VIMA_ATTN(64, ATTN_CROSS);
+    else VIMA_ATTN(64, ATTN_CAUSAL);
+  }
+#undef VIMA_ATTN
+  return (int)hipGetLastError();
+}
+
+
+int launch_attn_x3(const AttnArgs& a, hipStream_t st) {
+  if (a.B <= 0 || a.Lq <= 0 || a.Lk <= 0) return 0;
+  if (a.D != 32 && a.D != 64) return (int)hipErrorInvalidValue;
+  if (a.mode == ATTN_T5 && !a.relbias) return (int)hipErrorInvalidValue;
+  // 16-byte fp32 loads / stores: rows, head offsets and batch strides must be 16-B aligned
+  if ((a.ldq % 4) || (a.ldk % 4) || (a.ldv % 4) || (a.ldo % 4) || (a.k_bs % 4) || (a.v_bs % 4) || (a.k_hs % 4) || (a.v_hs % 4))
+    return (int)hipErrorInvalidValue;
+  const AttnDev d = to_dev(a);
+  dim3 grid((unsigned)((a.Lq + 31) / 32), (unsigned)a.H, (unsigned)a.B);
+#define VIMA_ATTN(D_, M_) hipLaunchKernelGGL((attn_x3_kernel<D_, M_>), grid, dim3(64), 0, st, d)
   if (a.D == 32) {
     if (a.mode == ATTN_T5) VIMA_ATTN(32, ATTN_T5);
     else if (a.mode == ATTN_CROSS) VIMA_ATTN(32, ATTN_CROSS);

@@ -42,6 +42,18 @@ __device__ __forceinline__ uint32_t pack2_bf16(float a, float b) {   // low half
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
 }
 
+// split-bf16 (precision "bf16x3"): x = hi + lo + e with hi = bf16(x), lo = bf16(x - hi), both round-to-nearest-even.
+// x - hi is exact in fp32 (hi is the nearest bf16 to x), so |e| <= 2^-9 |x - hi| <= 2^-18 |x|. A product then needs
+// hi_a.hi_b + hi_a.lo_b + lo_a.hi_b (three bf16 MFMAs); the dropped lo_a.lo_b and the e terms bound its relative error
+// by about 3 x 2^-18. 8 conversions + 8 shifts / masks + 8 subtractions per 8 values.
+typedef __attribute__((ext_vector_type(8))) float f32x8_t;
+__device__ __forceinline__ void split_bf16x8(const float4& a, const float4& b, bf16x8_t& hi, bf16x8_t& lo) {
+  const f32x8_t x = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+  hi = __builtin_convertvector(x, bf16x8_t);
+  const f32x8_t r = x - __builtin_convertvector(hi, f32x8_t);
+  lo = __builtin_convertvector(r, bf16x8_t);
+}
+
 template <typename T> struct Elem;
 template <> struct Elem<float> {
   static __device__ __forceinline__ float load(const float* p) { return *p; }

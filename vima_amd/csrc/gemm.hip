@@ -178,6 +178,21 @@ __device__ __forceinline__ f32x16_t mma(const Frag<float>& w, const Frag<float>&
   return acc;
 }
 
+// Split-bf16 operands of gemm_x3_kernel (precision "bf16x3"): a Frag<float> holds k = hi*8 + e, e = 0..7, of a 16-k step in
+// lane (i = lane&31, hi = lane>>5) -- exactly the operand map of v_mfma_f32_32x32x16_bf16 -- so the fp32 LDS tile and its
+// fragment reads are reused unchanged and each fragment is split once per k-step (split_bf16x8), then feeds all of its
+// MI / NI blocks. Three bf16 MFMAs per block at 3/16 of the cost of the eight fp32 ones; the two small correction terms
+// go first so that the large term is added last.
+struct FragX3 {
+  bf16x8_t h, l;
+  __device__ __forceinline__ void split(const Frag<float>& f) { split_bf16x8(f.v0, f.v1, h, l); }
+};
+__device__ __forceinline__ f32x16_t mma(const FragX3& w, const FragX3& a, f32x16_t acc) {
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.l, a.h, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.h, a.l, acc, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.h, a.h, acc, 0, 0, 0);
+}
+
 // FP8 (OCP e4m3) operands for v_mfma_scale_f32_32x32x64_f8f6f4 (2x the bf16 MFMA rate, K = 64 per instruction): a lane
 // (i = lane & 31, hi = lane >> 5) holds row i's 32 consecutive k of half `hi` = two 16-B chunks of the 128-byte K-tile row
 // (chunks ks*4 + hi*2 + {0,1} for the K = 64 step ks). Both operands are read with the same pattern, so the product does
@@ -287,6 +302,8 @@ struct GemmDev {
 };
 
 // ACT >= 0: compile-time activation; ACT == -1: runtime p.act. VEC: 4-wide vector epilogue. ASMLDS: inline-asm LDS-DMA.
+// gemm_x3_kernel below is a copy of this body for fp32 operands (split-bf16 products): a fix to the pipeline or to the fp32
+// epilogues here belongs there too.
 template <typename T, typename TL, int ACT, bool VEC, bool ASMLDS, bool W8 = false>
 __global__ __launch_bounds__(TL::THREADS, TL::MINW) void gemm_kernel(const GemmDev p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -707,6 +724,369 @@ __global__ __launch_bounds__(TL::THREADS, TL::MINW) void gemm_kernel(const GemmD
         }
         if constexpr (VEC) {   // N % 4 == 0 => n + 3 < N
           if (p.wscale) { const float4 sc = load4(p.wscale + n); v[0] *= sc.x; v[1] *= sc.y; v[2] *= sc.z; v[3] *= sc.w; }
+          if (bias) { const float4 b = load4(bias + n); v[0] += b.x; v[1] += b.y; v[2] += b.z; v[3] += b.w; }
+          if (act != ACT_NONE) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = apply_act_t<T>(v[e], act);
+          }
+          if (mul) { const float4 g = load4(mul + (long long)m * p.ldmul + n); v[0] *= g.x; v[1] *= g.y; v[2] *= g.z; v[3] *= g.w; }
+          if (res) { const float4 r4 = load4(res + (long long)m * p.ldres + n); v[0] += r4.x; v[1] += r4.y; v[2] += r4.z; v[3] += r4.w; }
+          if (resT) { const float4 r4 = load4(resT + (long long)m * p.ldresT + n); v[0] += r4.x; v[1] += r4.y; v[2] += r4.z; v[3] += r4.w; }
+          const float4 o = make_float4(v[0], v[1], v[2], v[3]);
+          if (out32) store4(out32 + orow * p.ld32 + n, o);
+          if (outT) {
+            if (p.split_n) {
+              if (n < p.split_n) store4(reinterpret_cast<T*>(p.outT_lo) + (long long)m * p.ldT_lo + n, o);
+              else store4(outT + orow * p.ldT + (n - p.split_n), o);
+            } else store4(outT + orow * p.ldT + n, o);
+          }
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int ne = n + e;
+            if (ne >= p.N) break;
+            float x = v[e];
+            if (bias) x += bias[ne];
+            x = apply_act_t<T>(x, act);
+            if (mul) x *= Elem<T>::load(mul + (long long)m * p.ldmul + ne);
+            if (res) x += res[(long long)m * p.ldres + ne];
+            if (resT) x += Elem<T>::load(resT + (long long)m * p.ldresT + ne);
+            if (out32) out32[orow * p.ld32 + ne] = x;
+            if (outT) Elem<T>::store(outT + orow * p.ldT + ne, x);
+          }
+        }
+      }
+    }
+  }
+}
+
+// precision "bf16x3": gemm_kernel<float, TL, ACT, VEC, ASMLDS> with the products in split-bf16 (FragX3 on the fp32 fragments)
+// -- same LDS tiles, pipeline, epilogues and launch geometry. A separate body rather than a template flag of gemm_kernel, so that
+// the existing kernels keep their names and their code.
+template <typename TL, int ACT, bool VEC, bool ASMLDS>
+__global__ __launch_bounds__(TL::THREADS, TL::MINW) void gemm_x3_kernel(const GemmDev p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  using T = float;
+  constexpr int RB = TL::RB, NS = TL::NS, CPR = TL::CPR;
+  // W operand geometry: bf16 / fp32 rows like A, or fp8 rows of half the bytes (half the LDS-DMA pieces per K-slice)
+  constexpr int BK = RB / (int)sizeof(T);
+  constexpr int EPC = KCfg<T>::EPC;
+  constexpr int KSTEPS = BK / 16;
+  constexpr int MI = TL::MI, NI = TL::NI, NW = TL::NW;
+  static_assert(KSTEPS >= 2 && (KSTEPS % 2) == 0, "fragment double buffer assumes an even number of k-steps");
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int hi = lane >> 5;
+  const int l31 = lane & 31;
+
+  // XCD-aware tile mapping (block b runs on XCD b % 8): one XCD walks all n-tiles of its A panel back to back
+  const int bid = blockIdx.x;
+  int tm, tn;
+  if (p.raster == 2) {
+    tn = bid % p.ntiles;
+    tm = bid / p.ntiles;
+  } else {
+    const int xcd = bid & 7;
+    const int idx = bid >> 3;
+    if (p.raster == 0) {
+      tn = idx % p.ntiles;
+      tm = (idx / p.ntiles) * 8 + xcd;
+    } else {
+      const int mtx = (p.mtiles + 7) >> 3;                 // A panels per XCD
+      const int full = p.ntiles / p.ngroup;                // complete n-groups
+      const int per_group = mtx * p.ngroup;
+      int g = idx / per_group, rem, ng;
+      if (g < full) { rem = idx - g * per_group; ng = p.ngroup; }
+      else { g = full; rem = idx - full * per_group; ng = p.ntiles - full * p.ngroup; }
+      tn = g * p.ngroup + rem % ng;
+      tm = (rem / ng) * 8 + xcd;
+    }
+  }
+  if (tm >= p.mtiles) return;
+  const int z = blockIdx.y;
+  const int m0 = tm * TL::BM, n0 = tn * TL::BN;
+
+  const T* A = reinterpret_cast<const T*>(p.A) + (long long)z * p.bsA;
+  const char* W = reinterpret_cast<const char*>(p.W) + (long long)z * p.bsW * (long long)sizeof(T);
+  // 8 slots per workgroup: 0-3 shader-clock stamps, 4/5 constant-rate (100 MHz) real-time at start/end, 6 HW_ID, 7 XCC_ID
+  auto stamp = [&](int slot) {
+    if (p.dbg && tid == 0) {
+      long long* d = p.dbg + (long long)blockIdx.x * 8;
+      d[slot] = (long long)__builtin_readcyclecounter();
+      if (slot == 0) {
+        d[4] = (long long)__builtin_amdgcn_s_memrealtime();
+        d[6] = (long long)__builtin_amdgcn_s_getreg((31 << 11) | 4);    // HW_REG_HW_ID
+        d[7] = (long long)__builtin_amdgcn_s_getreg((31 << 11) | 20);   // HW_REG_XCC_ID
+      }
+      if (slot == 3) d[5] = (long long)__builtin_amdgcn_s_memrealtime();
+    }
+  };
+  stamp(0);
+
+  // per-lane source pointers of this wave's LDS-DMA pieces of one K-slice (piece = 1 KiB = 1024/RB tile rows)
+  const T* srcA[TL::PA];
+  const char* srcW[TL::PW];
+#pragma unroll
+  for (int i = 0; i < TL::PA; ++i) {
+    const int s = (i * NW + w) * 64 + lane;
+    const int r = s / CPR, pp = s % CPR;
+    const int c = pp ^ swz<RB>(r);
+    int ra = m0 + r; ra = ra < p.M ? ra : p.M - 1;
+    srcA[i] = A + (long long)ra * p.lda + c * EPC;
+  }
+#pragma unroll
+  for (int i = 0; i < TL::PW; ++i) {
+    const int s = (i * NW + w) * 64 + lane;
+    const int r = s / CPR, pp = s % CPR;
+    const int c = pp ^ swz<RB>(r);
+    int rw = n0 + r; rw = rw < p.N ? rw : p.N - 1;
+    srcW[i] = W + ((long long)rw * p.ldw) * (long long)sizeof(T) + c * 16;
+  }
+
+  f32x16_t acc[MI][NI];
+#pragma unroll
+  for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.0f;
+
+  const int wm = w / TL::WN, wn = w % TL::WN;
+  const int arow = wm * (MI * 32) + l31;   // + mi*32
+  const int wrow = wn * (NI * 32) + l31;   // + ni*32
+  const int nk = p.K / BK;
+  const unsigned smem_base = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
+
+  // one 1-KiB LDS-DMA piece j of K-slice kt into `stage` (j < PA: A tile rows, else W tile rows)
+  constexpr int NP = TL::PA + TL::PW;
+  auto issue_piece = [&](int stage, int kt, int j) {
+    const int i = j < TL::PA ? j : j - TL::PA;
+    const int off = stage * TL::STAGE_BYTES + (j < TL::PA ? 0 : TL::A_BYTES) + (i * NW + w) * 1024;
+    const void* src = j < TL::PA ? (const void*)(srcA[i] + kt * BK) : (const void*)(srcW[i] + kt * RB);
+    if constexpr (ASMLDS) glds16_asm(src, smem_base + off);
+    else glds16(src, smem + off);
+  };
+
+  // Software pipeline (NS LDS stages in a ring, fragments double-buffered in registers):
+  //   slice kt, steps kk = 0 .. KSTEPS-2 : prefetch fragments of step kk+1 (same stage)      | MFMAs of step kk
+  //   last step                          : counted vmcnt + lgkmcnt(0), s_barrier -> every wave has finished READING
+  //                                        stage kt % NS and the DMA of slice kt+1 has landed; then prefetch the
+  //                                        fragments of slice kt+1 / step 0 and issue the DMA of slice kt+NS into the
+  //                                        stage just freed, one piece between two MFMAs   | MFMAs of the last step
+  // so the barrier, the LDS refill latency after it and the VMEM issue are covered by the last step's MFMAs (whose
+  // operands are already in registers). VMEM loads retire in order, so `vmcnt(n * NP)` = "all but the n youngest slices".
+  auto wait_slices_and_barrier = [&](int younger) {   // `younger` slices of DMA may stay in flight (wave-uniform)
+    if constexpr (ASMLDS) {
+      if (younger <= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(NP) : "memory");
+      else if (younger == 2 || NS <= 3) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(2 * NP) : "memory");
+      else if (younger == 3 || NS <= 4) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(NS > 3 ? 3 * NP : 0) : "memory");
+      else asm volatile("s_waitcnt vmcnt(%0)" ::"i"(NS > 4 ? 4 * NP : 0) : "memory");
+      __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0) via the builtin: keeps hipcc's scoreboard exact
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+    } else {
+      wait_all_and_barrier();
+    }
+  };
+  static_assert(NS >= 2 && NS <= 5 && (NS - 1) * NP <= 63, "ring depth (vmcnt is a 6-bit counter)");
+  const int npro = nk < NS ? nk : NS;
+  for (int t = 0; t < npro; ++t) {
+#pragma unroll
+    for (int j = 0; j < NP; ++j) issue_piece(t, t, j);
+  }
+  wait_slices_and_barrier(npro - 1);   // start as soon as slice 0 has landed
+  stamp(1);
+  Frag<T> fa[2][MI], fw[2][NI];
+#pragma unroll
+  for (int mi = 0; mi < MI; ++mi) fa[0][mi].template load<RB>(smem, arow + mi * 32, 0, hi);
+#pragma unroll
+  for (int ni = 0; ni < NI; ++ni) fw[0][ni].template load<RB>(smem + TL::A_BYTES, wrow + ni * 32, 0, hi);
+  // The two waves that share a SIMD (w and w + NW/2 of an 8-wave workgroup) run the SAME instruction stream in lock
+  // step after every barrier; if both fetch fragments at the same moment the matrix pipe idles, then both compete
+  // for it. The second half of the waves therefore issues its fragment prefetch in the MIDDLE of each step's MFMAs.
+  auto main_loop = [&](auto late_tag) {
+    constexpr bool LATE = decltype(late_tag)::value;
+    constexpr int PPM = (NP + MI * NI - 1) / (MI * NI);
+    // MFMAs of k-step buffer cb for mi in [mi0, mi1); when `dma`, the pieces of `slice` are issued into `stage` one
+    // (PPM) per MFMA, in MFMA order
+    auto mma_block = [&](int mi0, int mi1, int cb, bool dma, int stage, int slice) {
+      FragX3 xa[MI], xw[NI];   // split where the fragments are consumed: their ds_reads were issued a k-step earlier
+#pragma unroll
+      for (int mi = mi0; mi < mi1; ++mi) xa[mi].split(fa[cb][mi]);
+#pragma unroll
+      for (int ni = 0; ni < NI; ++ni) xw[ni].split(fw[cb][ni]);
+#pragma unroll
+      for (int mi = mi0; mi < mi1; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < NI; ++ni) {
+          acc[mi][ni] = mma(xw[ni], xa[mi], acc[mi][ni]);
+          if (dma) {
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int j = (mi * NI + ni) * PPM; j < (mi * NI + ni + 1) * PPM && j < NP; ++j) issue_piece(stage, slice, j);
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        }
+    };
+    int cur = 0;
+    for (int kt = 0; kt < nk; ++kt) {
+      const int nxt = cur + 1 == NS ? 0 : cur + 1;
+      const char* sA = smem + cur * TL::STAGE_BYTES;
+      const char* sW = sA + TL::A_BYTES;
+      const char* nA = smem + nxt * TL::STAGE_BYTES;
+      const char* nW = nA + TL::A_BYTES;
+#pragma unroll
+      for (int kk = 0; kk < KSTEPS; ++kk) {
+        const int cb = kk & 1, nb = cb ^ 1;
+        if (kk + 1 < KSTEPS) {   // prefetch the next step's fragments while this step's MFMAs run
+          if constexpr (LATE) {
+            __builtin_amdgcn_sched_barrier(0);
+            mma_block(0, MI / 2, cb, false, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+          }
+#pragma unroll
+          for (int mi = 0; mi < MI; ++mi) fa[nb][mi].template load<RB>(sA, arow + mi * 32, kk + 1, hi);
+#pragma unroll
+          for (int ni = 0; ni < NI; ++ni) fw[nb][ni].template load<RB>(sW, wrow + ni * 32, kk + 1, hi);
+          // pin the order: [ds_reads] then [MFMAs]; without this hipcc re-serialises read -> wait -> 2 MFMAs
+          __builtin_amdgcn_sched_barrier(0);
+          mma_block(LATE ? MI / 2 : 0, MI, cb, false, 0, 0);
+          __builtin_amdgcn_sched_barrier(0);
+        } else {
+          // slices issued so far: up to min(nk-1, kt+NS-1); younger than kt+1 may stay in flight
+          int last = kt + NS - 1;
+          last = last < nk - 1 ? last : nk - 1;
+          wait_slices_and_barrier(last - (kt + 1));
+          if (kt + 1 < nk) {
+#pragma unroll
+            for (int mi = 0; mi < MI; ++mi) fa[nb][mi].template load<RB>(nA, arow + mi * 32, 0, hi);
+#pragma unroll
+            for (int ni = 0; ni < NI; ++ni) fw[nb][ni].template load<RB>(nW, wrow + ni * 32, 0, hi);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+          // the DMA pieces of slice kt+NS go into the stage just freed, ONE BY ONE BETWEEN the MFMAs
+          const bool more = kt + NS < nk;
+          mma_block(0, MI, cb, more, cur, kt + NS);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      cur = nxt;
+    }
+  };
+  if (kDephase && NW == 8 && w >= NW / 2) main_loop(std::true_type{});
+  else main_loop(std::false_type{});
+  stamp(2);
+  // (the barrier inside the last slice already guarantees that no wave reads the stage buffers any more, so the LDS
+  // epilogue below may reuse them)
+
+  // ------------------------------------------------------------------ epilogue
+  // acc[mi][ni][4q+e] = C[m = m0 + wm*MI*32 + mi*32 + l31][n = n0 + wn*NI*32 + ni*32 + 8q + 4hi + e]
+  const float* bias = p.bias ? p.bias + (long long)z * p.bsBias : nullptr;
+  const T* mul = p.mul ? reinterpret_cast<const T*>(p.mul) + (long long)z * p.bsMul : nullptr;
+  const float* res = p.res ? p.res + (long long)z * p.bsRes : nullptr;
+  // residual in the operand type (batch 1 only): residual GEMMs have no activation, so the activation instantiations
+  // (GELU's erf is register-hungry: the extra live values spilled there) do not carry this code
+  constexpr bool kStreamEpi = ACT == ACT_NONE || ACT == -1;
+  const T* resT = kStreamEpi ? reinterpret_cast<const T*>(p.resT) : nullptr;
+  float* out32 = p.out32 ? p.out32 + (long long)z * p.bs32 : nullptr;
+  T* outT = p.outT ? reinterpret_cast<T*>(p.outT) + (long long)z * p.bsT : nullptr;
+  const int act = ACT >= 0 ? ACT : p.act;
+
+  if constexpr (VEC) {
+    if (p.epi_lds) {
+      // LDS-transposed epilogue. The MFMA layout gives a lane 4 consecutive columns of ONE row, i.e. a store
+      // instruction touches 32 different rows with 16-32 B each (32 partial cache lines per instruction: the write
+      // path, not HBM, then bounds the epilogue, ~7 us per 256x256 tile). Each wave therefore bounces its
+      // 32-row x 64-column slabs through a private 16 KiB LDS region (free after the main loop) and finishes the
+      // epilogue row-contiguously: 16 lanes cover one 64-column row segment, so every global access (gate `mul`,
+      // residual, fp32 / bf16 stores) is a full 128/256-byte line.
+      constexpr int WCOLS = NI * 32;                        // columns of the wave tile
+      constexpr int LDE = WCOLS + 4;                        // padded fp32 row stride: conflict-free ds_write_b128
+      constexpr int LPR = WCOLS / 4;                        // lanes per row in the read-back phase
+      constexpr int RPI = 64 / LPR;                         // rows per wave-instruction
+      static_assert(TL::SMEM_BYTES / NW >= 32 * LDE * 4, "per-wave LDS slab for the epilogue");
+      float* stage = reinterpret_cast<float*>(smem + w * (TL::SMEM_BYTES / NW));
+      const int rr = lane / LPR, cc = (lane % LPR) * 4;
+      const int n = n0 + wn * WCOLS + cc;
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi) {
+        float rsc = 1.0f;   // fused RMSNorm: scale of this lane's accumulator row
+        if (p.rs_ssq) {
+          int mr = m0 + wm * (MI * 32) + mi * 32 + l31; mr = mr < p.M ? mr : p.M - 1;
+          rsc = rms_row_scale(p.rs_ssq, p.rs_parts, mr, p.rs_invk, p.rs_eps);
+        }
+#pragma unroll
+        for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int nl = ni * 32 + 8 * q + 4 * hi;
+            float4 v = make_float4(acc[mi][ni][4 * q] * rsc, acc[mi][ni][4 * q + 1] * rsc, acc[mi][ni][4 * q + 2] * rsc, acc[mi][ni][4 * q + 3] * rsc);
+            const int nb = n0 + wn * WCOLS + nl;
+            if (bias && nb < p.N) { const float4 b = load4(bias + nb); v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w; }
+            if (act != ACT_NONE) { v.x = apply_act_t<T>(v.x, act); v.y = apply_act_t<T>(v.y, act); v.z = apply_act_t<T>(v.z, act); v.w = apply_act_t<T>(v.w, act); }
+            *reinterpret_cast<float4*>(stage + l31 * LDE + nl) = v;
+          }
+#pragma unroll
+        for (int it = 0; it < 32 / RPI; ++it) {
+          const int r = it * RPI + rr;
+          float4 v = *reinterpret_cast<const float4*>(stage + r * LDE + cc);
+          const int m = m0 + wm * (MI * 32) + mi * 32 + r;
+          float sq = 0.f, sm = 0.f;
+          if (m < p.M && n < p.N) {
+            long long orow = m;
+            if (p.rb > 0) orow = (long long)(m / p.rb) * p.s_hi + (long long)(m % p.rb) * p.s_lo + p.ro;
+            if (mul) { const float4 g = load4(mul + (long long)m * p.ldmul + n); v.x *= g.x; v.y *= g.y; v.z *= g.z; v.w *= g.w; }
+            if (res) { const float4 r4 = load4(res + (long long)m * p.ldres + n); v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w; }
+            if (resT) { const float4 r4 = load4(resT + (long long)m * p.ldresT + n); v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w; }
+            if (out32) store4(out32 + orow * p.ld32 + n, v);
+            if (outT) {
+              if (p.split_n) {
+                if (n < p.split_n) store4(reinterpret_cast<T*>(p.outT_lo) + (long long)m * p.ldT_lo + n, v);
+                else store4(outT + orow * p.ldT + (n - p.split_n), v);
+              } else store4(outT + orow * p.ldT + n, v);
+            }
+            sq = sumsq4(v);
+            sm = (v.x + v.y) + (v.z + v.w);
+          }
+          if (p.ssq_out) {   // wave-uniform; 8 consecutive lanes hold 32 columns of one row: butterfly, one partial per 32 columns
+            sq += __shfl_xor(sq, 1, 64); sq += __shfl_xor(sq, 2, 64); sq += __shfl_xor(sq, 4, 64);
+            if ((lane & 7) == 0 && m < p.M && n < p.N) p.ssq_out[(long long)m * (p.N >> 5) + (n >> 5)] = sq;
+            if (p.sum_out) {   // fused LayerNorm: the row's partial SUMS as well (same columns, same tree)
+              sm += __shfl_xor(sm, 1, 64); sm += __shfl_xor(sm, 2, 64); sm += __shfl_xor(sm, 4, 64);
+              if ((lane & 7) == 0 && m < p.M && n < p.N) p.sum_out[(long long)m * (p.N >> 5) + (n >> 5)] = sm;
+            }
+          }
+        }
+      }
+      stamp(3);
+      return;
+    }
+  }
+
+#pragma unroll
+  for (int mi = 0; mi < MI; ++mi) {
+    const int m = m0 + wm * (MI * 32) + mi * 32 + l31;
+    if (m >= p.M) continue;
+    long long orow = m;
+    if (p.rb > 0) orow = (long long)(m / p.rb) * p.s_hi + (long long)(m % p.rb) * p.s_lo + p.ro;
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int n = n0 + wn * (NI * 32) + ni * 32 + 8 * q + 4 * hi;
+        if (n >= p.N) continue;
+        float v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = acc[mi][ni][4 * q + e];
+        if (p.rs_ssq) {
+          const float rsc = rms_row_scale(p.rs_ssq, p.rs_parts, m, p.rs_invk, p.rs_eps);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] *= rsc;
+        }
+        if constexpr (VEC) {   // N % 4 == 0 => n + 3 < N
           if (bias) { const float4 b = load4(bias + n); v[0] += b.x; v[1] += b.y; v[2] += b.z; v[3] += b.w; }
           if (act != ACT_NONE) {
 #pragma unroll
@@ -1917,6 +2297,18 @@ int launch_inst(const GemmDev& d, dim3 grid, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
+template <typename TL, int ACT, bool VEC, bool ASMLDS>
+int launch_inst_x3(const GemmDev& d, dim3 grid, hipStream_t st) {
+  static PerDeviceOnce attr;   // per instantiation, per device
+  {
+    const hipError_t e = attr.ensure([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_x3_kernel<TL, ACT, VEC, ASMLDS>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, TL::SMEM_ALLOC); });
+    if (e != hipSuccess) return (int)e;
+  }
+  hipLaunchKernelGGL((gemm_x3_kernel<TL, ACT, VEC, ASMLDS>), grid, dim3(TL::THREADS), TL::SMEM_ALLOC, st, d);
+  return (int)hipGetLastError();
+}
+
 template <typename T, typename TL, bool ASMLDS>
 int launch_tile(GemmDev d, const GemmArgs& a, bool vec, hipStream_t st) {
   d.mtiles = (d.M + TL::BM - 1) / TL::BM;
@@ -1934,6 +2326,18 @@ int launch_tile(GemmDev d, const GemmArgs& a, bool vec, hipStream_t st) {
   }
   dim3 grid((unsigned)(d.raster == 2 ? d.mtiles * d.ntiles : groups * 8 * d.ntiles), (unsigned)(a.batch > 0 ? a.batch : 1), 1);
 #ifndef VIMA_GEMM_LAB
+  if constexpr (sizeof(T) == 4) {
+    if (a.x3) {   // split-bf16 products, same instantiation choice as the fp32 kernel
+      if (!vec) return launch_inst_x3<TL, -1, false, ASMLDS>(d, grid, st);
+      switch (a.act) {
+        case ACT_NONE: return launch_inst_x3<TL, ACT_NONE, true, ASMLDS>(d, grid, st);
+        case ACT_RELU: return launch_inst_x3<TL, ACT_RELU, true, ASMLDS>(d, grid, st);
+        case ACT_GELU: return launch_inst_x3<TL, ACT_GELU, true, ASMLDS>(d, grid, st);
+        case ACT_QUICKGELU: return launch_inst_x3<TL, ACT_QUICKGELU, true, ASMLDS>(d, grid, st);
+        default: return (int)hipErrorInvalidValue;
+      }
+    }
+  }
   if constexpr (sizeof(T) == 2) {
     if (a.w8) {   // fp8 weights: always the asm LDS-DMA pipeline and the vector epilogue (checked by launch_t)
       switch (a.act) {
@@ -2407,6 +2811,7 @@ int launch_t(const GemmArgs& a, hipStream_t st) {
   constexpr int BK = 128 / (int)sizeof(T);   // K granularity of the widest K-slice (TileS / TileL)
   if (a.M <= 0 || a.N <= 0) return 0;
   if (a.K <= 0 || a.K % BK != 0) return (int)hipErrorInvalidValue;
+  if (a.x3 && sizeof(T) != 4) return (int)hipErrorInvalidValue;   // split-bf16 splits fp32 operands
   // LDS-DMA reads 16-B chunks: rows must start 16-B aligned
   const size_t es = sizeof(T);
   const size_t esw = a.w8 ? 1 : es;   // fp8 weights: ldw / bsW count bytes
@@ -2424,7 +2829,8 @@ int launch_t(const GemmArgs& a, hipStream_t st) {
     if (sp.S > 1 && ok4 && a.splitk_ws_bytes >= (size_t)sp.S * MN * sizeof(float) && aligned_to(a.splitk_ws, 16)) {
       GemmArgs p1;
       p1.A = a.A; p1.lda = a.lda; p1.W = a.W; p1.ldw = a.ldw; p1.M = a.M; p1.N = a.N; p1.K = sp.Ks;
-      if (a.kernel_id) *a.kernel_id = 8000 + (a.act + 1) * 10;
+      if (a.kernel_id) *a.kernel_id = (a.x3 ? 23000 : 8000) + (a.act + 1) * 10;
+      p1.x3 = a.x3;   // the partial pass multiplies like the single pass
       p1.tune = a.tune; p1.batch = sp.S; p1.bsA = sp.Ks; p1.bsW = sp.Ks; p1.out32 = a.splitk_ws; p1.ld32 = a.N; p1.bs32 = MN;
       if (int e = launch_t<T>(p1, st)) return e;
       const long long work = (long long)a.M * (a.N / 4);
@@ -2606,7 +3012,7 @@ int launch_t(const GemmArgs& a, hipStream_t st) {
     if (gemm_tile(a.tune) == 7 && v) return launch_tile<T, TileXS, true>(d, a, v, st);
     if (gemm_tile(a.tune) == 8 && v) return launch_tile<T, Tile64, true>(d, a, v, st);
   }
-  if (a.kernel_id) *a.kernel_id = 5000 + (a.act + 1) * 10;
+  if (a.kernel_id) *a.kernel_id = (a.x3 ? 21000 : 5000) + (a.act + 1) * 10;
   if (gemm_variant(a.tune) == 1 || a.w8) return launch_tile<T, TileS, true>(d, a, v, st);
   return launch_tile<T, TileS, false>(d, a, v, st);
 #endif

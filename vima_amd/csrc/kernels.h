@@ -108,8 +108,12 @@ struct GemmArgs {
   // out (profiling): which kernel the launcher chose = kind * 1000 + (act + 1) * 10 + epi ; kind 1 gemm_pp_kernel,
   // 2 gemm_persistent_kernel, 3 gemm_wide_kernel, 4..7 gemm_kernel with the 256x256 / 128x128 / 64x64 / 32x64 tile (epi 0),
   // 8 two-pass split-K, 10 / 11 / 12 gemm_resident_kernel with the 32x32 / 64x32 / 64x64 tile, 15 / 16 its DUAL (GEGLU pair) form on the 32x32 / 64x64 tile,
-  // 17 / 18 gemm_skinny_kernel (M <= 32) / its DUAL form
+  // 17 / 18 gemm_skinny_kernel (M <= 32) / its DUAL form, 19 / 20 gemm_q4_kernel, 21 gemm_x3_kernel (128x128 tile), 23 two-pass split-K over it
   int* kernel_id = nullptr;
+  // precision "bf16x3" (fp32 operands only): the products run in split-bf16 on gemm_x3_kernel -- each fp32 operand is hi + lo
+  // (two bf16), a.b ~ hi_a.hi_b + hi_a.lo_b + lo_a.hi_b on v_mfma_f32_32x32x16_bf16 -- instead of v_mfma_f32_32x32x2_f32.
+  // Same tiles, epilogues and split-K plan as the fp32 path.
+  int x3 = 0;
   // fp8 weights (precision "fp8w", bf16 activations): W is [N,K] OCP e4m3 BYTES (ldw / bsW in elements = bytes) and
   // wscale[n] the per-output-channel dequantisation scale; the kernel widens the fragments to bf16 in registers and
   // multiplies accumulator column n by wscale[n] before bias / activation. Needs N % 4 == 0, K % 64 == 0, batch 1.
@@ -255,5 +259,7 @@ struct AttnArgs {
 // generic exact kernel (any T); the MFMA flash kernel (bf16, D in {32,64})
 int launch_attn_generic(const AttnArgs& a, bool is_bf16, hipStream_t st);
 int launch_attn_mfma(const AttnArgs& a, hipStream_t st);
+// precision "bf16x3": fp32 operands, split-bf16 products on the matrix cores (D in {32,64}; attn_x3_kernel)
+int launch_attn_x3(const AttnArgs& a, hipStream_t st);
 
 }  // namespace vima

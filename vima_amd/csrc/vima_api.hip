@@ -175,6 +175,7 @@ struct VimaHandle {
   VimaConfig cfg;
   int device = 0;
   bool bf16 = true;
+  bool x3 = false;          // precision "bf16x3": the fp32 path (bf16 = false) with split-bf16 GEMMs and MFMA attention
   bool w8 = false;          // precision "fp8w" / "fp8": fp8 e4m3 weights (+ per-output-channel scales) for the large Linear layers
   // precision "fp8": the T5 stack's GEMMs ALSO take fp8 e4m3 activations with one static scale per (layer, site) and run on
   // v_mfma_scale_f32_32x32x64_f8f6f4 (gemm_pp_kernel<.., F8>). Scales are calibrated by the first T5 pass of the handle (which runs
@@ -787,6 +788,7 @@ struct Run {
     }
     int kid = 0;
     a.kernel_id = &kid;
+    a.x3 = h->x3 ? 1 : 0;
     int e = launch_gemm(a, h->bf16, st);
     prof_end();
     if (h->prof && !h->recs.empty()) { ProfRec& r = h->recs.back(); r.kid = kid; r.M = a.M; r.N = a.N; r.K = a.K; }
@@ -861,7 +863,8 @@ struct Run {
     a.tune = &h->tune;
     prof_begin(1, 4.0 * a.B * (double)a.H * a.Lq * (double)a.Lk * a.D);
     int e;
-    if (impl == 1 && h->bf16 && (a.D == 32 || a.D == 64)) e = launch_attn_mfma(a, st);   // other head dims: exact generic kernel
+    if (impl == 1 && h->x3 && (a.D == 32 || a.D == 64)) e = launch_attn_x3(a, st);        // split-bf16 on fp32 operands
+    else if (impl == 1 && h->bf16 && (a.D == 32 || a.D == 64)) e = launch_attn_mfma(a, st);   // other head dims: exact generic kernel
     else e = launch_attn_generic(a, h->bf16, st);
     prof_end();
     if (e) err = fail(std::string("attention launch failed: ") + hipGetErrorString((hipError_t)e), e);
@@ -1568,7 +1571,7 @@ int vima_create(const VimaConfig* cfg, int device, VimaHandle** out) {
     return fail("vima_create: head dim must be 16, 32, 64 or 128 (got " + std::to_string(ds) + "/" + std::to_string(dx) + ")");
   if (E % 64 || E > 1024) return fail("vima_create: embed_dim must be a multiple of 64 and <= 1024");
   if (cfg->precision != VIMA_PRECISION_FP32 && cfg->precision != VIMA_PRECISION_BF16 && cfg->precision != VIMA_PRECISION_FP8W &&
-      cfg->precision != VIMA_PRECISION_FP8)
+      cfg->precision != VIMA_PRECISION_FP8 && cfg->precision != VIMA_PRECISION_BF16X3)
     return fail("vima_create: bad precision");
   if (cfg->n_positions <= 0 || cfg->n_positions > 512 || cfg->xattn_n_positions <= 0) return fail("vima_create: bad table sizes");
   if (cfg->policy_kind < VIMA_POLICY_VIMA || cfg->policy_kind > VIMA_POLICY_FLAMINGO) return fail("vima_create: bad policy_kind");
@@ -1584,7 +1587,8 @@ int vima_create(const VimaConfig* cfg, int device, VimaHandle** out) {
   VimaHandle* h = new VimaHandle();
   h->cfg = *cfg;
   h->device = device;
-  h->bf16 = cfg->precision != VIMA_PRECISION_FP32;
+  h->bf16 = cfg->precision != VIMA_PRECISION_FP32 && cfg->precision != VIMA_PRECISION_BF16X3;
+  h->x3 = cfg->precision == VIMA_PRECISION_BF16X3;
   h->w8 = cfg->precision == VIMA_PRECISION_FP8W || cfg->precision == VIMA_PRECISION_FP8;
   h->a8 = cfg->precision == VIMA_PRECISION_FP8;
   if (hipStreamCreateWithFlags(&h->aux, hipStreamNonBlocking) != hipSuccess ||
@@ -1651,7 +1655,7 @@ int64_t vima_required_params(const VimaConfig* cfg, char* buf, int64_t buflen) {
   // host-only: run the packer against an empty staging map and collect the "missing key" names
   if (!cfg) return -1;
   VimaHandle tmp;
-  tmp.cfg = *cfg; tmp.bf16 = cfg->precision != VIMA_PRECISION_FP32;
+  tmp.cfg = *cfg; tmp.bf16 = cfg->precision != VIMA_PRECISION_FP32 && cfg->precision != VIMA_PRECISION_BF16X3;
   std::string saved = g_err;
   (void)pack_all(&tmp);
   std::string msg = g_err;
@@ -2499,7 +2503,7 @@ int vima_op_attention(VimaHandle* h, const float* q, const float* k, const float
   AttnArgs a;
   a.q = qT; a.ldq = H * D; a.k = kT; a.ldk = H * D; a.v = vT; a.ldv = H * D; a.out = oT; a.ldo = H * D;
   a.kmask = kmask; a.relbias = relbias; a.bias_far = h->op_bias_far; a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.D = D; a.scale = scale; a.mode = mode;
-  if (impl == 1 && !h->bf16) return fail("vima_op_attention: the MFMA kernel needs bf16 precision");
+  if (impl == 1 && !h->bf16 && !h->x3) return fail("vima_op_attention: the MFMA kernel needs bf16 or bf16x3 precision");
   if (R.attn(a, impl)) return R.err;
   if (h->bf16) {
     hipLaunchKernelGGL(widen_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, R.st, (const bf16_t*)oT, out, nq);
