@@ -12,6 +12,12 @@ Multi-GPU = data parallel, weak scaling: every rank evaluates its own batch of 2
 only collective is one all-gather of the [256,700] logits per step (vima_allgather_logits in the C ABI, RCCL over xGMI).
 `python bench.py --gpus N` on its own re-launches itself with N ranks; it exits non-zero when fewer than N GPUs are visible.
 Prints ONE JSON line on rank 0. `--dump-outputs DIR` also writes the logits of the last timed step to DIR/logits.npy.
+
+A plain run does what the headline figure needs and nothing else: set-up, warm-up, the timed steps, the dump, the line. `--full` adds,
+after the timed steps and outside them, everything else this file measures: the WARM / incremental / batch-1 / batch-32 steps and the other
+BASELINE.json configurations (config.secondary_cold), the per-class and per-kernel profile pass with its rooflines, the HBM traffic
+of the dominant kernel and the CPU baseline. `--headline-only`, `--no-side-configs`, `--live-pmc off` and `--no-cpu-baseline` leave single
+parts of `--full` out; `--launch-log` needs it.
 """
 from __future__ import annotations
 
@@ -137,7 +143,7 @@ def live_pmc_traffic(argv_tail, timeout_s=150.0):
     for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
         out = os.path.join(tmp, ctr.lower())
         cmd = [exe, "--kernel-trace", "--pmc", ctr, "-d", out, "-o", "bench", "--", sys.executable, os.path.abspath(__file__),
-               "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--headline-only", "--live-pmc", "off", "--opt", "dual_stream=0",
+               "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--headline-only", "--live-pmc", "off", "--opt", "dual_stream=0",
                "--launch-log", log] + argv_tail
         left = t_end - time.perf_counter()
         if left < 10:
@@ -533,15 +539,21 @@ def bench_baseline_policy(args):
     ms = (time.perf_counter() - t0) / args.steps * 1e3
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, {"logits": logits})
-    pol.prof_enable(True)
-    pol.set_option("dual_stream", 0)
-    step()
-    torch.cuda.synchronize()
-    prof = pol.prof_read_ex()
-    pol.prof_enable(False)
-    tot_fl = sum(prof[k]["flops"] for k in prof)
-    split = {k: {"ms": round(v["ms"], 3), "launches": v["launches"], "tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 1) if v["ms"] > 0 else 0.0}
-             for k, v in prof.items()}
+    split = roofline = None
+    if args.full:          # the per-class split and the executed FLOPs come from a profiled step of their own
+        pol.prof_enable(True)
+        pol.set_option("dual_stream", 0)
+        step()
+        torch.cuda.synchronize()
+        prof = pol.prof_read_ex()
+        pol.prof_enable(False)
+        tot_fl = sum(prof[k]["flops"] for k in prof)
+        split = {k: {"ms": round(v["ms"], 3), "launches": v["launches"], "tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 1) if v["ms"] > 0 else 0.0}
+                 for k, v in prof.items()}
+        peak = BF16_PEAK_TFLOPS if args.precision != "fp32" else FP32_PEAK_TFLOPS
+        roofline = {"bound": "mfma", "achieved": round(tot_fl / (ms * 1e-3) / 1e12, 1), "peak": peak, "unit": "TFLOP/s",
+                    "frac": round(tot_fl / (ms * 1e-3) / 1e12 / peak, 4),
+                    "traffic": None, "note": "whole step: the launch log's executed FLOPs / wall time"}
     print(json.dumps({
         "metric": f"policy-forward steps/sec, {kind} baseline policy (VIMA-200M transformer size), batch {B}", "value": round(1e3 / ms, 4), "unit": "steps/s",
         "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak",
@@ -549,10 +561,7 @@ def bench_baseline_policy(args):
         "config": {"workload": f"{kind} baseline policy: embed_dim 768, 11 layers, 12 heads; batch {B}; prompt of {n_seg} x ({args.words} words + 1 RGB frame pair) = "
                                f"{Lp} tokens; T = {T} observation steps ({cfg.obs_tokens} tokens each); COLD step (prompt + observation encoding, decoder, "
                                f"action head); random-init weights", "policy": kind, "prompt_tokens": int(Lp), "obs_tokens_per_step": cfg.obs_tokens},
-        "class_split_dual_stream_off": split,
-        "roofline": {"bound": "mfma", "achieved": round(tot_fl / (ms * 1e-3) / 1e12, 1), "peak": BF16_PEAK_TFLOPS if args.precision != "fp32" else FP32_PEAK_TFLOPS,
-                     "unit": "TFLOP/s", "frac": round(tot_fl / (ms * 1e-3) / 1e12 / (BF16_PEAK_TFLOPS if args.precision != "fp32" else FP32_PEAK_TFLOPS), 4),
-                     "traffic": None, "note": "whole step: the launch log's executed FLOPs / wall time"}}))
+        "class_split_dual_stream_off": split, "roofline": roofline}))
 
 
 def main():
@@ -568,28 +577,33 @@ def main():
     ap.add_argument("--qv", type=int, default=4, help="objects per view (Q = 2*qv object tokens per observation)")
     ap.add_argument("--words", type=int, default=8, help="words per prompt segment (a segment = words + 1 image)")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32", "fp8w", "fp8"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--headline-only", action="store_true", help="skip the warm / incremental / batch-1 / batch-32 extras (profiler runs: "
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure everything else: the warm / incremental / batch-1 / "
+                    "batch-32 steps, the other BASELINE.json configurations, the per-kernel profile pass and its rooflines, the HBM traffic of the "
+                    "dominant kernel, the CPU baseline. Off by default: a plain run sets up, warms up, times the steps and prints its line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--headline-only", action="store_true", help="with --full: skip the warm / incremental / batch-1 / batch-32 extras (profiler runs: "
                     "every kernel launch in the trace then belongs to the headline workload)")
     ap.add_argument("--cpu-batch", type=int, default=4)
     ap.add_argument("--steps-history", type=int, default=1, help="T: observation steps in the history (T-1 past actions)")
     ap.add_argument("--opt", action="append", default=[], help="library option key=value (vima_set_option), repeatable")
-    ap.add_argument("--live-pmc", default="auto", choices=["auto", "off"], help="auto: collect roofline.traffic NOW with two rocprofv3 --pmc passes "
-                    "over a subprocess of this workload (1 GPU, default workload only, rocprofv3 on the box); off / unavailable: the last committed "
+    ap.add_argument("--live-pmc", default="auto", choices=["auto", "off"], help="with --full. auto: collect roofline.traffic NOW with two rocprofv3 --pmc passes "
+                    "over a subprocess of this workload (1 GPU, default workload only, rocprofv3 installed); off / unavailable: the last committed "
                     "profiles/r*_pmc_traffic.json. The JSON line says which (roofline.traffic_source)")
-    ap.add_argument("--launch-log", default=None, help="write the GEMM launch log of one step (kernel, M, N, K in launch order) to this JSON file "
+    ap.add_argument("--launch-log", default=None, help="with --full: write the GEMM launch log of one step (kernel, M, N, K in launch order) to this JSON file "
                     "(scripts/pmc_summary.py joins it with per-dispatch counter values)")
     ap.add_argument("--dry-ranks", type=int, default=0, help="CPU self-check of the N > 1 HOST path (VERDICT r4 item 6): re-launches this script with N ranks "
                     "over gloo, a stub communicator behind LogitsComm (same call order as the RCCL one: id drawn by rank 0, broadcast, join, all-gather, "
                     "destroy), the rank-0-written state-dict cache, the agreement all-reduce, K synthetic steps with the barrier / max-over-ranks timing "
                     "and teardown. No GPU, no policy, no measurement: the line it prints is marked dry_run")
-    ap.add_argument("--no-side-configs", action="store_true", help="skip the other BASELINE.json configurations (VIMA-20M batch 32, Lp = 1024 in bf16 "
+    ap.add_argument("--no-side-configs", action="store_true", help="with --full: skip the other BASELINE.json configurations (VIMA-20M batch 32, Lp = 1024 in bf16 "
                     "and fp8, T = 8) that the default run reports under config.secondary_cold")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step returned "
                     "(the [global batch, 700] action logits) to DIR/logits.npy in float32; the inputs are seeded, so two builds can be compared")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.launch_log and not args.full:
+        ap.error("--launch-log is written by the profile pass: it needs --full")
     if args.policy != "vima":
         if args.gpus != 1 or os.environ.get("WORLD_SIZE", "1") != "1":
             sys.exit("bench.py --policy gpt|gato|flamingo is a single-GPU line")
@@ -820,116 +834,126 @@ def main():
 
     warm_ms = inc_ms = float("nan")
     secondary = {}
-    if not args.headline_only:
+    if args.full and not args.headline_only:
         warm_ms, inc_ms, secondary = extras(args, pol, syn, cfg, prompts, obs, past, sync, dev, rank, n_seg, Q, B, sd=sd)
-
-    # ---- per-class kernel time (HIP events on the launch stream), same workload, outside the timed region. The
-    # two-stream software pipelining is switched off for this pass so that kernels do not overlap each other and the
-    # event-bracketed durations are those of the kernels alone (what rocprofv3 --kernel-trace reports for the
-    # committed profile, which is taken with --opt dual_stream=0 for the same reason).
-    pol.set_option("dual_stream", 0)
-    step()
-    torch.cuda.synchronize(dev)
-    pol.prof_enable(True)
-    step()
-    torch.cuda.synchronize(dev)
-    gk = pol.prof_read_gemm_kernels()           # per KERNEL (the launcher's choice), before the class read resets the records
-    if args.launch_log and rank == 0:
-        json.dump([{k: e[k] for k in ("kernel", "M", "N", "K")} for e in pol.prof_read_gemm_launches()], open(args.launch_log, "w"))
-    prof = pol.prof_read_ex()
-    pol.prof_enable(False)
-
-    # ---- HBM traffic of the dominant kernel: measured NOW when possible (two rocprofv3 --pmc passes over a subprocess of this same
-    # workload), else the last committed summary -- the line says which
-    global _LIVE_PMC
-    traffic_source = "committed profiles/r*_pmc_traffic.json (not collected in this run)"
-    default_workload = (world == 1 and args.model == "200M" and B == 256 and args.prompt_len == 512 and args.qv == 4 and args.words == 8
-                        and T == 1 and args.precision == "bf16" and not args.opt)
-    if args.live_pmc == "auto" and rank == 0 and default_workload and not args.headline_only:
-        t_pmc = time.perf_counter()
-        summ, why = live_pmc_traffic([])
-        if summ is not None:
-            _LIVE_PMC = summ
-            traffic_source = f"{summ['source']} ({time.perf_counter() - t_pmc:.0f} s)"
-        else:
-            traffic_source = f"committed profiles/r*_pmc_traffic.json (live collection unavailable: {why})"
 
     cold, warm = flops_per_sample(cfg.embed_dim, cfg.xf_n_layers, args.prompt_len, n_seg * Q, Q, T)
     peak = FP32_PEAK_TFLOPS if args.precision == "fp32" else BF16_PEAK_TFLOPS   # fp8w: fp8 weights are widened to bf16 in registers, the matrix op is the bf16 MFMA
     HBM_PEAK_GBS = 8000.0
-    g0, g3 = prof["gemm"], prof["gemm_residual"]
+    if not args.full:
+        # a plain run: the whole step over its timed wall clock is all the roofline there is without runs of its own
+        warm_roof = inc_roof = None
+        ws_tflops = B * cold / (ms_per_step * 1e-3) / 1e12
+        roofline = {"kernel": None, "bound": "mfma", "achieved": round(ws_tflops, 2), "peak": peak, "unit": "TFLOP/s", "frac": round(ws_tflops / peak, 4),
+                    "traffic": None, "whole_step_tflops": round(ws_tflops, 2), "whole_step_frac": round(ws_tflops / peak, 4),
+                    "note": "whole step: the algorithmic FLOPs of the cold step over the timed wall clock. The per-kernel and per-class figures, the HBM "
+                            "traffic of the dominant kernel, the warm / incremental / other-batch / other-configuration steps and the CPU baseline "
+                            "take runs of their own: --full"}
+    else:
+        # ---- per-class kernel time (HIP events on the launch stream), same workload, outside the timed region. The
+        # two-stream software pipelining is switched off for this pass so that kernels do not overlap each other and the
+        # event-bracketed durations are those of the kernels alone (what rocprofv3 --kernel-trace reports for the
+        # committed profile, which is taken with --opt dual_stream=0 for the same reason).
+        pol.set_option("dual_stream", 0)
+        step()
+        torch.cuda.synchronize(dev)
+        pol.prof_enable(True)
+        step()
+        torch.cuda.synchronize(dev)
+        gk = pol.prof_read_gemm_kernels()           # per KERNEL (the launcher's choice), before the class read resets the records
+        if args.launch_log and rank == 0:
+            json.dump([{k: e[k] for k in ("kernel", "M", "N", "K")} for e in pol.prof_read_gemm_launches()], open(args.launch_log, "w"))
+        prof = pol.prof_read_ex()
+        pol.prof_enable(False)
 
-    def klass(d, name, peak=peak):
-        if name.endswith(", true>"):
-            peak = FP8_PEAK_TFLOPS           # fp8 e4m3 operands on v_mfma_scale_f32_32x32x64_f8f6f4: priced against the 5 PF dense fp8 peak
-        tf = d["flops"] / (d["ms"] * 1e-3) / 1e12 if d["ms"] > 0 else 0.0
-        gbs = d["bytes"] / (d["ms"] * 1e-3) / 1e9 if d["ms"] > 0 else 0.0
-        inten = d["flops"] / d["bytes"] if d["bytes"] > 0 else 0.0
-        hbm_bound = inten < peak * 1e12 / (HBM_PEAK_GBS * 1e9)       # below the machine balance (312 FLOP/B for bf16)
-        return {"kernel": name, "bound": "hbm" if hbm_bound else "mfma",
-                "achieved": round(gbs if hbm_bound else tf, 2), "peak": HBM_PEAK_GBS if hbm_bound else peak,
-                "unit": "GB/s" if hbm_bound else "TFLOP/s",
-                "frac": round((gbs / HBM_PEAK_GBS) if hbm_bound else (tf / peak), 4),
-                "launches_per_step": d["launches"], "avg_launch_us": round(d["ms"] * 1e3 / max(d["launches"], 1), 2),
-                "ms_per_step": round(d["ms"], 3), "tflops": round(tf, 2), "algorithmic_gbs": round(gbs, 1),
-                "flop_per_byte": round(inten, 1), "algorithmic_mb_per_launch": round(d["bytes"] / max(d["launches"], 1) / 1e6, 1)}
+        # ---- HBM traffic of the dominant kernel: measured NOW when possible (two rocprofv3 --pmc passes over a subprocess of this same
+        # workload), else the last committed summary -- the line says which
+        global _LIVE_PMC
+        traffic_source = "committed profiles/r*_pmc_traffic.json (not collected in this run)"
+        default_workload = (world == 1 and args.model == "200M" and B == 256 and args.prompt_len == 512 and args.qv == 4 and args.words == 8
+                            and T == 1 and args.precision == "bf16" and not args.opt)
+        if args.live_pmc == "auto" and rank == 0 and default_workload and not args.headline_only:
+            t_pmc = time.perf_counter()
+            summ, why = live_pmc_traffic([])
+            if summ is not None:
+                _LIVE_PMC = summ
+                traffic_source = f"{summ['source']} ({time.perf_counter() - t_pmc:.0f} s)"
+            else:
+                traffic_source = f"committed profiles/r*_pmc_traffic.json (live collection unavailable: {why})"
 
-    k_res = klass(g3, "vima::gemm_persistent_kernel<ACT_NONE, EPI 4 | EPI 3> (+ gemm_kernel fallbacks): the residual GEMMs (T5 o / wo and ViT "
-                      "out_proj / c_proj with the stream in bf16: read + write 2 B per element, RMS partials; decoder: fp32 stream)")
-    k_plain = klass(g0, "vima::gemm_persistent_kernel<*, EPI 1|2> / vima::gemm_kernel: all other GEMM launches (bf16-only output)")
-    gemm_ms = g0["ms"] + g3["ms"]
-    gemm_tflops = (g0["flops"] + g3["flops"]) / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
-    # the DOMINANT KERNEL (most time in the step), under the name rocprofv3 prints for it, with its own algorithmic flops /
-    # bytes and its own counter traffic
-    dom_name = max(gk, key=lambda k: gk[k]["ms"]) if gk else None
-    roofline = klass(gk[dom_name], dom_name) if dom_name else dict(k_res if g3["ms"] >= g0["ms"] else k_plain)
-    roofline.update({
-        "traffic": pmc_traffic(dom_name) if dom_name else pmc_traffic(),
-        "traffic_all_gemm_launches": pmc_traffic(),
-        "traffic_source": traffic_source,
-        "traffic_per_shape": ([{k: (round(v, 1) if isinstance(v, float) else v) for k, v in r.items()} for r in _LIVE_PMC["per_shape"][:12]]
-                              if _LIVE_PMC and _LIVE_PMC.get("per_shape") else None),
-        "gemm_kernels": {k: {"ms_per_step": round(v["ms"], 3), "launches": v["launches"],
-                             "tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 1) if v["ms"] > 0 else 0.0,
-                             "algorithmic_mb_per_launch": round(v["bytes"] / max(v["launches"], 1) / 1e6, 1)}
-                         for k, v in sorted(gk.items(), key=lambda kv: -kv[1]["ms"])[:10]},
-        "gemm_classes": [k_plain, k_res],
-        "all_gemm": {"bound": "mfma", "achieved": round(gemm_tflops, 2), "peak": peak, "unit": "TFLOP/s", "frac": round(gemm_tflops / peak, 4),
-                     "launches_per_step": g0["launches"] + g3["launches"], "ms_per_step": round(gemm_ms, 3)},
-        "gemm_ms_per_step": round(gemm_ms, 3), "attention_ms_per_step": round(prof["attention"]["ms"], 3),
-        "other_ms_per_step": round(prof["other"]["ms"], 3),
-        "whole_step_tflops": round(B * cold / (ms_per_step * 1e-3) / 1e12, 2),
-        "whole_step_frac": round(B * cold / (ms_per_step * 1e-3) / 1e12 / peak, 4),
-        "note": "per-class numbers: HIP events around every launch in a separate pass with dual_stream=0 (un-overlapped kernel "
-                "durations, what rocprofv3 --kernel-trace reports for the committed profile); achieved = ALGORITHMIC flops or bytes "
-                "(each operand / output / epilogue input once) over that time; `bound` from the kernel's flop/byte vs the 312 FLOP/B "
-                "machine balance; `kernel` = the kernel with the most time in the step; `traffic` = ITS HBM bytes per launch from the "
-                + ("rocprofv3 PMC passes collected live by this run" if _LIVE_PMC is not None else "committed rocprofv3 PMC passes (profiles/)")
-                + " (`traffic_source`; `traffic_all_gemm_launches`: average over all bf16 GEMM launches). "
-                "whole_step_*: the 49.09 TFLOP algorithmic numerator over the timed wall clock (the last ViT block is computed for the "
-                "cls token only -- executed GEMM FLOPs are ~6 % below the algorithmic count)",
-    })
+        g0, g3 = prof["gemm"], prof["gemm_residual"]
 
-    # secondary rooflines: the WARM step (prompt reused: obs ViT + decoder against the cached prompt K/V +
-    # action head) and the incremental env step are bound by the matrix pipe on their ~1.4 TFLOP and by HBM on the per-layer
-    # K/V stream (B x Lp x 2E bf16 per decoder layer) + the weights; both bounds are reported, the larger one is the roofline
-    def small_roofline(ms, flops):
-        if not (ms == ms and ms > 0):
-            return None
-        kv_bytes = cfg.xf_n_layers * B * args.prompt_len * 2 * cfg.embed_dim * 2.0
-        w_bytes = {"bf16": 676e6, "fp8w": 370e6, "fp8": 370e6, "fp32": 1352e6}[args.precision] * 0.45      # decoder + obs ViT + heads (no T5)
-        t_mfma, t_hbm = flops / (peak * 1e12) * 1e3, (kv_bytes + w_bytes) / (HBM_PEAK_GBS * 1e9) * 1e3
-        return {"bound": "hbm" if t_hbm > t_mfma else "mfma", "mfma_ms": round(t_mfma, 4), "hbm_ms": round(t_hbm, 4),
-                "roofline_ms": round(max(t_mfma, t_hbm), 4), "frac": round(max(t_mfma, t_hbm) / ms, 4),
-                "algorithmic_tflop": round(flops / 1e12, 3), "kv_stream_mb": round(kv_bytes / 1e6, 1)}
+        def klass(d, name, peak=peak):
+            if name.endswith(", true>"):
+                peak = FP8_PEAK_TFLOPS           # fp8 e4m3 operands on v_mfma_scale_f32_32x32x64_f8f6f4: priced against the 5 PF dense fp8 peak
+            tf = d["flops"] / (d["ms"] * 1e-3) / 1e12 if d["ms"] > 0 else 0.0
+            gbs = d["bytes"] / (d["ms"] * 1e-3) / 1e9 if d["ms"] > 0 else 0.0
+            inten = d["flops"] / d["bytes"] if d["bytes"] > 0 else 0.0
+            hbm_bound = inten < peak * 1e12 / (HBM_PEAK_GBS * 1e9)       # below the machine balance (312 FLOP/B for bf16)
+            return {"kernel": name, "bound": "hbm" if hbm_bound else "mfma",
+                    "achieved": round(gbs if hbm_bound else tf, 2), "peak": HBM_PEAK_GBS if hbm_bound else peak,
+                    "unit": "GB/s" if hbm_bound else "TFLOP/s",
+                    "frac": round((gbs / HBM_PEAK_GBS) if hbm_bound else (tf / peak), 4),
+                    "launches_per_step": d["launches"], "avg_launch_us": round(d["ms"] * 1e3 / max(d["launches"], 1), 2),
+                    "ms_per_step": round(d["ms"], 3), "tflops": round(tf, 2), "algorithmic_gbs": round(gbs, 1),
+                    "flop_per_byte": round(inten, 1), "algorithmic_mb_per_launch": round(d["bytes"] / max(d["launches"], 1) / 1e6, 1)}
 
-    # executed FLOPs of a WARM / incremental step: the per-layer prompt K/V projection (2 * Lp * 2E * E per sample and layer) is cached
-    kv_proj_flops = cfg.xf_n_layers * 2.0 * args.prompt_len * 2 * cfg.embed_dim * cfg.embed_dim
-    warm_roof = small_roofline(warm_ms, B * (warm - kv_proj_flops))
-    inc_roof = small_roofline(inc_ms, B * (warm - kv_proj_flops))
+        k_res = klass(g3, "vima::gemm_persistent_kernel<ACT_NONE, EPI 4 | EPI 3> (+ gemm_kernel fallbacks): the residual GEMMs (T5 o / wo and ViT "
+                          "out_proj / c_proj with the stream in bf16: read + write 2 B per element, RMS partials; decoder: fp32 stream)")
+        k_plain = klass(g0, "vima::gemm_persistent_kernel<*, EPI 1|2> / vima::gemm_kernel: all other GEMM launches (bf16-only output)")
+        gemm_ms = g0["ms"] + g3["ms"]
+        gemm_tflops = (g0["flops"] + g3["flops"]) / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
+        # the DOMINANT KERNEL (most time in the step), under the name rocprofv3 prints for it, with its own algorithmic flops /
+        # bytes and its own counter traffic
+        dom_name = max(gk, key=lambda k: gk[k]["ms"]) if gk else None
+        roofline = klass(gk[dom_name], dom_name) if dom_name else dict(k_res if g3["ms"] >= g0["ms"] else k_plain)
+        roofline.update({
+            "traffic": pmc_traffic(dom_name) if dom_name else pmc_traffic(),
+            "traffic_all_gemm_launches": pmc_traffic(),
+            "traffic_source": traffic_source,
+            "traffic_per_shape": ([{k: (round(v, 1) if isinstance(v, float) else v) for k, v in r.items()} for r in _LIVE_PMC["per_shape"][:12]]
+                                  if _LIVE_PMC and _LIVE_PMC.get("per_shape") else None),
+            "gemm_kernels": {k: {"ms_per_step": round(v["ms"], 3), "launches": v["launches"],
+                                 "tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 1) if v["ms"] > 0 else 0.0,
+                                 "algorithmic_mb_per_launch": round(v["bytes"] / max(v["launches"], 1) / 1e6, 1)}
+                             for k, v in sorted(gk.items(), key=lambda kv: -kv[1]["ms"])[:10]},
+            "gemm_classes": [k_plain, k_res],
+            "all_gemm": {"bound": "mfma", "achieved": round(gemm_tflops, 2), "peak": peak, "unit": "TFLOP/s", "frac": round(gemm_tflops / peak, 4),
+                         "launches_per_step": g0["launches"] + g3["launches"], "ms_per_step": round(gemm_ms, 3)},
+            "gemm_ms_per_step": round(gemm_ms, 3), "attention_ms_per_step": round(prof["attention"]["ms"], 3),
+            "other_ms_per_step": round(prof["other"]["ms"], 3),
+            "whole_step_tflops": round(B * cold / (ms_per_step * 1e-3) / 1e12, 2),
+            "whole_step_frac": round(B * cold / (ms_per_step * 1e-3) / 1e12 / peak, 4),
+            "note": "per-class numbers: HIP events around every launch in a separate pass with dual_stream=0 (un-overlapped kernel "
+                    "durations, what rocprofv3 --kernel-trace reports for the committed profile); achieved = ALGORITHMIC flops or bytes "
+                    "(each operand / output / epilogue input once) over that time; `bound` from the kernel's flop/byte vs the 312 FLOP/B "
+                    "machine balance; `kernel` = the kernel with the most time in the step; `traffic` = ITS HBM bytes per launch from the "
+                    + ("rocprofv3 PMC passes collected live by this run" if _LIVE_PMC is not None else "committed rocprofv3 PMC passes (profiles/)")
+                    + " (`traffic_source`; `traffic_all_gemm_launches`: average over all bf16 GEMM launches). "
+                    "whole_step_*: the 49.09 TFLOP algorithmic numerator over the timed wall clock (the last ViT block is computed for the "
+                    "cls token only -- executed GEMM FLOPs are ~6 % below the algorithmic count)",
+        })
+
+        # secondary rooflines: the WARM step (prompt reused: obs ViT + decoder against the cached prompt K/V +
+        # action head) and the incremental env step are bound by the matrix pipe on their ~1.4 TFLOP and by HBM on the per-layer
+        # K/V stream (B x Lp x 2E bf16 per decoder layer) + the weights; both bounds are reported, the larger one is the roofline
+        def small_roofline(ms, flops):
+            if not (ms == ms and ms > 0):
+                return None
+            kv_bytes = cfg.xf_n_layers * B * args.prompt_len * 2 * cfg.embed_dim * 2.0
+            w_bytes = {"bf16": 676e6, "fp8w": 370e6, "fp8": 370e6, "fp32": 1352e6}[args.precision] * 0.45      # decoder + obs ViT + heads (no T5)
+            t_mfma, t_hbm = flops / (peak * 1e12) * 1e3, (kv_bytes + w_bytes) / (HBM_PEAK_GBS * 1e9) * 1e3
+            return {"bound": "hbm" if t_hbm > t_mfma else "mfma", "mfma_ms": round(t_mfma, 4), "hbm_ms": round(t_hbm, 4),
+                    "roofline_ms": round(max(t_mfma, t_hbm), 4), "frac": round(max(t_mfma, t_hbm) / ms, 4),
+                    "algorithmic_tflop": round(flops / 1e12, 3), "kv_stream_mb": round(kv_bytes / 1e6, 1)}
+
+        # executed FLOPs of a WARM / incremental step: the per-layer prompt K/V projection (2 * Lp * 2E * E per sample and layer) is cached
+        kv_proj_flops = cfg.xf_n_layers * 2.0 * args.prompt_len * 2 * cfg.embed_dim * cfg.embed_dim
+        warm_roof = small_roofline(warm_ms, B * (warm - kv_proj_flops))
+        inc_roof = small_roofline(inc_ms, B * (warm - kv_proj_flops))
 
     cpu_baseline = None
-    if rank == 0 and not args.no_cpu_baseline:          # timed on rank 0's host cores, outside the timed region, for every N
+    if args.full and rank == 0 and not args.no_cpu_baseline:          # timed on rank 0's host cores, outside the timed region, for every N
         if affinity0 is not None and host_affinity.get("pinned"):
             os.sched_setaffinity(0, affinity0)          # the NUMA pin was for the GPU step; the CPU baseline gets the cores the process was given
         cpu_baseline = run_cpu_baseline(cfg, sd, n_seg, args.qv, args.cpu_batch, B, budget_s=20.0, words=args.words)

@@ -8,7 +8,7 @@
 # Tasks (a task argument follows after a colon, e.g. pytest:tests/test_fp8_gpu.py; pytest / bench / py arguments are eval'ed, so a -k expression
 # with spaces is written pytest:"tests/x.py -k 'a or b'"):
 #   pytest[:<pytest args>]   python -m pytest <args or `tests -m gpu -x -q`>            -> <tag>_pytest.txt
-#   bench[:<bench args>]     python bench.py <args or `--steps 20 --warmup 5`>          -> <tag>_bench.json
+#   bench[:<bench args>]     python bench.py <args or `--full --steps 20 --warmup 5`>   -> <tag>_bench.json  (the whole record: --full)
 #   smoke                    __graft_entry__.smoke()
 #   headline                 rocprofv3 --kernel-trace --stats of 3 headline steps       -> <tag>_kernel_stats.md
 #   b1 | b32                 the same at batch 1 / 32 (cold steps)                      -> <tag>_b1_kernel_stats.md
@@ -36,8 +36,8 @@ for task in "$@"; do
   cd $R
   case "$task" in
     pytest) eval "timeout 1500 python -m pytest ${arg:-tests -m gpu -x -q}" > $O/${TAG}_pytest_$n.txt 2>&1; tail -4 $O/${TAG}_pytest_$n.txt;;
-    bench) S=$(date +%s); eval "timeout 900 python bench.py ${arg:---steps 20 --warmup 5}" > $O/${TAG}_bench_$n.json 2> $O/${TAG}_bench_${n}_stderr.txt
-           echo "bench.py ${arg:---steps 20 --warmup 5}: $(( $(date +%s) - S )) s wall"; cut -c1-300 $O/${TAG}_bench_$n.json; tail -3 $O/${TAG}_bench_${n}_stderr.txt;;
+    bench) S=$(date +%s); eval "timeout 900 python bench.py ${arg:---full --steps 20 --warmup 5}" > $O/${TAG}_bench_$n.json 2> $O/${TAG}_bench_${n}_stderr.txt
+           echo "bench.py ${arg:---full --steps 20 --warmup 5}: $(( $(date +%s) - S )) s wall"; cut -c1-300 $O/${TAG}_bench_$n.json; tail -3 $O/${TAG}_bench_${n}_stderr.txt;;
     smoke) python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -3;;
     headline) prof headline "$TAG: rocprofv3 --kernel-trace --stats -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --headline-only --opt dual_stream=0 $arg (VIMA-200M B=256 Lp=512 bf16, 1x MI355X)" \
                 python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --headline-only --opt dual_stream=0 $arg
@@ -52,7 +52,7 @@ for task in "$@"; do
                 python $R/bench.py --policy $task --batch 256 --steps 4 --warmup 2 --opt dual_stream=0 $arg;;
     pmc) for c in FETCH_SIZE WRITE_SIZE; do
            rm -rf /tmp/pmc_$c
-           (cd /tmp && timeout 300 rocprofv3 --kernel-trace --pmc $c -d /tmp/pmc_$c -o bench -- python $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --headline-only --live-pmc off --opt dual_stream=0 --launch-log /tmp/launches.json $arg > /dev/null 2>&1)
+           (cd /tmp && timeout 300 rocprofv3 --kernel-trace --pmc $c -d /tmp/pmc_$c -o bench -- python $R/bench.py --steps 1 --warmup 0 --full --no-cpu-baseline --headline-only --live-pmc off --opt dual_stream=0 --launch-log /tmp/launches.json $arg > /dev/null 2>&1)
          done
          python $R/scripts/pmc_summary.py /tmp/pmc_FETCH_SIZE/bench_results.db /tmp/pmc_WRITE_SIZE/bench_results.db $O/${TAG}_pmc_traffic.md $O/${TAG}_pmc_traffic.json /tmp/launches.json | tail -2;;
     sq) rm -rf /tmp/pmc_sq

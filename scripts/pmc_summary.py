@@ -2,7 +2,7 @@
 FETCH_SIZE / WRITE_SIZE are in KiB; on gfx950 FETCH_SIZE reports 1/2 of the bytes of wide coalesced streaming reads
 (guides/MI355X_MICROARCH.md, HBM section), so read bytes = 2 * FETCH_SIZE * 1024; WRITE_SIZE is used as reported.
 
-The launch log (bench.py --launch-log: [{"kernel", "M", "N", "K"}] of ONE step in launch order, written by the profiled process itself from
+The launch log (bench.py --full --launch-log: [{"kernel", "M", "N", "K"}] of ONE step in launch order, written by the profiled process itself from
 vima_prof_read_gemm_launches) attributes per-DISPATCH counter values to shapes: with dual_stream = 0 every step dispatches the same GEMM
 sequence, so the GEMM dispatches of the trace are that sequence repeated; a kernel-name mismatch anywhere voids the attribution
 (reported, never guessed).
@@ -74,7 +74,7 @@ def summarise(fetch_db, write_db, launch_log=None):
     gem_bytes = sum(r[1] * r[4] for r in gem) / max(n, 1)
     out = {"gemm_bf16_launches": n, "gemm_bf16_bytes_per_launch": gem_bytes,
            "per_kernel": {r[0]: {"launches": r[1], "bytes_per_launch": r[4]} for r in table[:40]},
-           "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes), bench.py --steps 1 --warmup 0",
+           "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes), bench.py --steps 1 --warmup 0 --full",
            "correction": "read bytes = 2 x FETCH_SIZE x 1024 (gfx950 half-count)", "counters_collection_columns": cols,
            "_table": table}
     if launch_log:

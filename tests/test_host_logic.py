@@ -110,6 +110,22 @@ def test_bench_helpers_without_gpu():
         assert default in line, line
 
 
+def test_bench_full_option_is_a_switch_off_by_default():
+    """A plain `bench.py --gpus 1 --steps K --warmup W` measures the headline alone; everything else sits behind `--full`, a switch that is
+    off by default (what each of the two runs carries: tests/test_bench_gpu.py). `--launch-log`, written by the profile pass, is refused without it."""
+    import inspect
+    import os
+    import subprocess
+    import sys
+    import bench
+    src = inspect.getsource(bench.main)
+    line = next(l for l in src.splitlines() if '"--full"' in l)
+    assert 'action="store_true"' in line, line
+    r = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"), "--launch-log", "x.json"],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--full" in r.stderr, r.stderr[-500:]
+
+
 class _NestedMapping(collections.abc.MutableMapping):
     """A mapping that is NOT a dict subclass and wraps nested dicts on access -- the two properties of the reference's
     `vima.utils.DataDict` that the boundary has to cope with."""
