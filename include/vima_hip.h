@@ -33,7 +33,7 @@ enum { VIMA_PRECISION_FP32 = 0, VIMA_PRECISION_BF16 = 1, VIMA_PRECISION_FP8W = 2
  * the matrix products run in split-bf16: each fp32 operand is written x = hi + lo with hi = bf16(x), lo = bf16(x - hi) (round to
  * nearest even) and a.b ~ hi_a.hi_b + hi_a.lo_b + lo_a.hi_b on three v_mfma_f32_32x32x16_bf16 with fp32 accumulation (about 3 x 2^-18
  * relative error per product against 2^-8 for bf16; 3/16 of the cost of the fp32 matrix instruction). Every GEMM runs on
- * gemm_x3_kernel (kinds 21 / 23 of vima_prof_read_gemm_kernels); attention with impl 1 and head dim 32 / 64 on attn_x3_kernel, other
+ * gemm_kernel<float, ..., X3> (kinds 21 / 23 of vima_prof_read_gemm_kernels); attention with impl 1 and head dim 32 / 64 on attn_x3_kernel, other
  * head dims on the exact generic kernel. The 5-token ViT attention is the fp32 kernel. ABI version unchanged (additive). */
 /* FP8W: bf16 activations and matrix instruction, OCP e4m3 weights (+ one fp32 scale per output channel) for the large Linear layers.
  * FP8 : FP8W plus e4m3 ACTIVATIONS into the large GEMMs of the T5 stack, the ViT and the decoder's prompt K/V projection (one static
@@ -327,7 +327,7 @@ int vima_prof_read_ex(VimaHandle* h, double out_ms[4], int64_t out_launches[4], 
  * kind 1 gemm_pp_kernel<ACT, EPI>, 2 gemm_persistent_kernel<ACT, EPI>, 3 gemm_wide_kernel,
  * 4..7 gemm_kernel with the 256x256 / 128x128 / 64x64 / 32x64 tile (kind 5 with N = 8 x embed_dim: the block-interleaved GEGLU pair, two products per launch), 8 two-pass split-K, 10..12 gemm_resident_kernel with the
  * 32x32 / 64x32 / 64x64 tile (also the grouped launch of the action head's last layers), 15 / 16 its GEGLU-pair form (two products per launch:
- * 32x32 / 64x64 tile), 17 / 18 gemm_skinny_kernel (at most 32 rows) / its GEGLU-pair form, 21 gemm_x3_kernel (precision BF16X3: split-bf16
+ * 32x32 / 64x64 tile), 17 / 18 gemm_skinny_kernel (at most 32 rows) / its GEGLU-pair form, 21 gemm_kernel<float, ..., X3> (precision BF16X3: split-bf16
  * products, 128x128 tile), 23 two-pass split-K over it; per kernel the summed milliseconds,
  * launches, algorithmic FLOPs and algorithmic HBM bytes. Returns the number of kernels (<= max_n) or a negative error; does
  * NOT reset the records (call it before vima_prof_read / vima_prof_read_ex). */

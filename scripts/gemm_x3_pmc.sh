@@ -1,5 +1,5 @@
 #!/bin/bash
-# What bounds gemm_x3_kernel (precision "bf16x3"): matrix-pipe and vector-issue counters of ONE split-bf16 GEMM launched through
+# What bounds gemm_kernel<float, ..., X3> (precision "bf16x3"): matrix-pipe and vector-issue counters of ONE split-bf16 GEMM launched through
 # vima_op_linear on a bf16x3 handle (default shape: the T5 qkv GEMM of VIMA-200M at batch 32, M = 16384, N = 2304, K = 768).
 # Separate small --pmc passes, each under its own time limit, kernel trace only. Usage: bash scripts/gemm_x3_pmc.sh OUTDIR [M N K]
 R=$(cd "$(dirname "$0")/.." && pwd)
@@ -23,15 +23,15 @@ pass a GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES
 pass b SQ_INSTS_VALU SQ_INSTS_LDS SQ_WAVES
 pass c SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_LDS SQ_WAIT_ANY
 python3 - "$OUT" $SHAPE <<'PY'
-import csv, glob, sys, collections
+import csv, glob, re, sys, collections
 out, M, N, K = sys.argv[1], *map(int, sys.argv[2:5])
 acc = collections.defaultdict(list)
 for f in glob.glob(f"{out}/**/*counter_collection.csv", recursive=True):
     for r in csv.DictReader(open(f)):
-        if "gemm_x3_kernel" in r["Kernel_Name"]:
+        if re.search(r"gemm_kernel<float,.*, false, true>", r["Kernel_Name"]):   # W8 = false, X3 = true
             acc[r["Counter_Name"]].append(float(r["Counter_Value"]))
 c = {k: sum(v) / len(v) for k, v in acc.items()}
-print(f"gemm_x3_kernel, M = {M}, N = {N}, K = {K}; per-dispatch means of the chip-summed counters:")
+print(f"gemm_kernel<float, ..., X3>, M = {M}, N = {N}, K = {K}; per-dispatch means of the chip-summed counters:")
 for k in sorted(c):
     print(f"  {k} {c[k]:.6g}")
 need = ("GRBM_GUI_ACTIVE", "SQ_VALU_MFMA_BUSY_CYCLES", "SQ_INSTS_VALU", "SQ_WAVES")

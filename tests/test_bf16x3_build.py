@@ -1,6 +1,6 @@
 """Precision "bf16x3" (split-bf16 matrix products on fp32 operands) without a GPU: the public surface accepts it, the Python
-enum matches the header, and the two new kernels cross-compile for gfx950 scratch-free, within their register budget, on
-the bf16 matrix instruction and never on the fp32 one."""
+enum matches the header, and the two split kernels cross-compile for gfx950 scratch-free, within their register budget, on
+the bf16 matrix instruction and never on the fp32 one -- while the fp32 instantiations of the same GEMM body stay on the fp32 one."""
 import os
 import re
 import shutil
@@ -63,13 +63,20 @@ def _body(asm, name):
     return asm[start.end():asm.index("s_endpgm", start.end())]
 
 
-# (source, kernel, expected instantiations, VGPR + AGPR budget per lane: 2 waves / SIMD for the 256-thread GEMM tile (two
-# workgroups per CU), 2 / SIMD for the single-wave attention kernel)
+# The split GEMM is gemm_kernel<float, ..., X3>: the fp32 instantiations (mangled gemm_kernelIf...) whose last two template
+# arguments W8, X3 are false, true; X3 = false ends in ...ELb0EEEv.
+_GEMM_F32 = r"gemm_kernelIf\S*ELb[01]EEEvNS0_7GemmDevE$"
+_GEMM_X3 = r"gemm_kernelIf\S*ELb0ELb1EEEvNS0_7GemmDevE$"
+
+
+# (source, kernel (regular expression on the mangled name), expected instantiations, VGPR + AGPR budget per lane: 2 waves / SIMD
+# for the 256-thread GEMM tile (two workgroups per CU), 2 / SIMD for the single-wave attention kernel)
 @needs_hipcc
-@pytest.mark.parametrize("src,kernel,count,budget", [("gemm.hip", "gemm_x3_kernel", 10, 256), ("attention.hip", "attn_x3_kernel", 6, 256)])
+@pytest.mark.parametrize("src,kernel,count,budget", [pytest.param("gemm.hip", _GEMM_X3, 10, 256, id="gemm.hip-gemm_kernel_X3-10-256"),
+                                                     ("attention.hip", "attn_x3_kernel", 6, 256)])
 def test_split_kernels_compile_on_the_bf16_matrix_instruction(src, kernel, count, budget):
     asm, remarks = _compile(src)
-    res = {k: v for k, v in _usage(remarks).items() if kernel in k}
+    res = {k: v for k, v in _usage(remarks).items() if re.search(kernel, k)}
     assert len(res) == count, sorted(res)
     for name, v in res.items():
         assert v.get("ScratchSize", 0) == 0, (name, v)
@@ -77,3 +84,16 @@ def test_split_kernels_compile_on_the_bf16_matrix_instruction(src, kernel, count
         body = _body(asm, name)
         assert "v_mfma_f32_32x32x16_bf16" in body, name
         assert "v_mfma_f32_32x32x2_f32" not in body, name
+
+
+@needs_hipcc
+def test_fp32_ring_kernels_stay_on_the_fp32_matrix_instruction():
+    """The converse: X3 is a flag of the one ring-tile body, so every fp32 instantiation WITHOUT it must still be the exact
+    fp32 product."""
+    asm, remarks = _compile("gemm.hip")
+    f32 = [k for k in _usage(remarks) if re.search(_GEMM_F32, k) and not re.search(_GEMM_X3, k)]
+    assert f32, "no fp32 gemm_kernel instantiation found"
+    for name in f32:
+        body = _body(asm, name)
+        assert "v_mfma_f32_32x32x2_f32" in body, name
+        assert "v_mfma_f32_32x32x16_bf16" not in body, name

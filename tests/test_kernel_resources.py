@@ -49,7 +49,7 @@ def _usage(src):
 def test_hot_kernels_use_no_scratch(src, patterns):
     res = _usage(src)
     # the scalar-epilogue fallback instantiations (VEC = false: N % 4 != 0) are not on the benchmark's path
-    hot = {k: v for k, v in res.items() if any(p in k for p in patterns) and "ELb0ELb1ELb0EEEv" not in k}
+    hot = {k: v for k, v in res.items() if any(p in k for p in patterns) and "ELb0ELb1ELb0ELb0EEEv" not in k}
     assert hot, f"no kernel of {src} matched {patterns}"
     for k, v in hot.items():
         # the fp8-WEIGHT instantiations of the round-2 persistent kernel (gemm_persistent_kernel<.., W8 = true>: precision fp8w and the

@@ -1364,16 +1364,9 @@ static int launch_mfma4_qg(const AttnDev& d, const AttnArgs& a, hipStream_t st) 
   const size_t sh = NSTG * (64 * D * 2) + NSTG * (D * VT4_STRIDE * 2) + (size_t)nt * 64 * 4 + (size_t)((nt + 3) & ~3) * 4 +
                     (MODE == ATTN_T5 ? (size_t)(128 * QG + nt * 64) * 4 : 0);
   if (sh > 160 * 1024) return (int)hipErrorInvalidValue;
-  static PerDeviceOnce attr;   // per instantiation, per device
-  {
-    const hipError_t e = attr.ensure([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_mfma4_kernel<D, MODE, QG>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-    if (e != hipSuccess) return (int)e;
-  }
   const int bh8 = (a.B * a.H + 7) / 8;
   dim3 grid((unsigned)(bh8 * 8 * nq), 1, 1);
-  hipLaunchKernelGGL((attn_mfma4_kernel<D, MODE, QG>), grid, dim3(256), sh, st, d);
-  return (int)hipGetLastError();
+  return launch_dyn_lds<attn_mfma4_kernel<D, MODE, QG>>(grid, dim3(256), 160 * 1024, sh, st, d);
 }
 template <int D, int MODE>
 static int launch_mfma4(const AttnDev& d, const AttnArgs& a, hipStream_t st) {
@@ -1395,14 +1388,7 @@ static int launch_split(const AttnDev& d, const AttnArgs& a, hipStream_t st) {
   const size_t comb = (size_t)4 * (D / 32 * 16 + 2) * 64 * 4;
   if (sh < comb) sh = comb;
   if (sh > 160 * 1024) return (int)hipErrorInvalidValue;
-  static PerDeviceOnce attr;   // per instantiation, per device
-  {
-    const hipError_t e = attr.ensure([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_split_kernel<D, MODE>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-    if (e != hipSuccess) return (int)e;
-  }
-  hipLaunchKernelGGL((attn_split_kernel<D, MODE>), dim3((unsigned)(((a.B * a.H + 15) / 16) * 16)), dim3(256), sh, st, d);
-  return (int)hipGetLastError();
+  return launch_dyn_lds<attn_split_kernel<D, MODE>>(dim3((unsigned)(((a.B * a.H + 15) / 16) * 16)), dim3(256), 160 * 1024, sh, st, d);
 }
 
 int launch_attn_mfma(const AttnArgs& a, hipStream_t st) {

@@ -31,6 +31,20 @@ struct PerDeviceOnce {
   }
 };
 
+// Launch `Kernel` with `launch_bytes` of dynamic LDS after raising its limit to `attr_bytes` on the current device (attr_bytes = 0:
+// the default limit of 48 KiB suffices, no attribute call). One PerDeviceOnce per kernel instantiation. Returns a hipError_t as int.
+template <auto Kernel, typename... Args>
+int launch_dyn_lds(dim3 grid, dim3 block, size_t attr_bytes, size_t launch_bytes, hipStream_t st, const Args&... args) {
+  static PerDeviceOnce attr;
+  if (attr_bytes) {
+    const hipError_t e = attr.ensure([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)attr_bytes); });
+    if (e != hipSuccess) return (int)e;
+  }
+  hipLaunchKernelGGL(Kernel, grid, block, launch_bytes, st, args...);
+  return (int)hipGetLastError();
+}
+
 __device__ __forceinline__ float bf16_to_f32(bf16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
 
 // round-to-nearest-even; lowers to the gfx950 hardware conversion (v_cvt_pk_bf16_f32)

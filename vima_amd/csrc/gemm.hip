@@ -178,10 +178,10 @@ __device__ __forceinline__ f32x16_t mma(const Frag<float>& w, const Frag<float>&
   return acc;
 }
 
-// Split-bf16 operands of gemm_x3_kernel (precision "bf16x3"): a Frag<float> holds k = hi*8 + e, e = 0..7, of a 16-k step in
+// Split-bf16 operands of gemm_kernel<float, ..., X3 = true> (precision "bf16x3"): a Frag<float> holds k = hi*8 + e, e = 0..7, of a 16-k step in
 // lane (i = lane&31, hi = lane>>5) -- exactly the operand map of v_mfma_f32_32x32x16_bf16 -- so the fp32 LDS tile and its
-// fragment reads are reused unchanged and each fragment is split once per k-step (split_bf16x8), then feeds all of its
-// MI / NI blocks. Three bf16 MFMAs per block at 3/16 of the cost of the eight fp32 ones; the two small correction terms
+// fragment reads are reused unchanged and each fragment is split once per k-step (split_bf16x8, in gemm_kernel's mma_block), then
+// feeds all of its MI / NI blocks. Three bf16 MFMAs per block at 3/16 of the cost of the eight fp32 ones; the two small correction terms
 // go first so that the large term is added last.
 struct FragX3 {
   bf16x8_t h, l;
@@ -214,17 +214,22 @@ __device__ __forceinline__ f32x16_t mma8(const Frag8& w, const Frag8& a, f32x16_
   return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(w.v, a.v, acc, 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
 }
 
+// 24 per-32-column partial sums of one row (E = 768) in a fixed order: six independent 16-byte loads (a scalar loop serialises
+// the load latencies); pairs of 32-column partials are summed first -- the same add every producer shape would do for a
+// 64-column group
+__device__ __forceinline__ float ln_tree24(const float* q) {
+  const float4 a = load4(q), b = load4(q + 4), c = load4(q + 8), d = load4(q + 12), e = load4(q + 16), f = load4(q + 20);
+  const float s0 = a.x + a.y, s1 = a.z + a.w, s2 = b.x + b.y, s3 = b.z + b.w, s4 = c.x + c.y, s5 = c.z + c.w;
+  const float s6 = d.x + d.y, s7 = d.z + d.w, s8 = e.x + e.y, s9 = e.z + e.w, s10 = f.x + f.y, s11 = f.z + f.w;
+  return (((s0 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7))) + ((s8 + s9) + (s10 + s11));
+}
+
 // fused RMSNorm row scale: rsqrt(mean of squares + eps) from the producer's per-64-column partial sums (fixed order)
 __device__ __forceinline__ float rms_row_scale(const float* ssq, int parts, int row, float invk, float eps) {
   const float* q = ssq + (long long)row * parts;
   float t;
-  if (parts == 24) {   // E = 768: six independent 16-byte loads (a scalar loop serialises the load latencies); pairs of
-    // 32-column partials are summed first -- the same add every producer shape would do for a 64-column group
-    const float4 a = load4(q), b = load4(q + 4), c = load4(q + 8), d = load4(q + 12), e = load4(q + 16), f = load4(q + 20);
-    const float s0 = a.x + a.y, s1 = a.z + a.w, s2 = b.x + b.y, s3 = b.z + b.w, s4 = c.x + c.y, s5 = c.z + c.w;
-    const float s6 = d.x + d.y, s7 = d.z + d.w, s8 = e.x + e.y, s9 = e.z + e.w, s10 = f.x + f.y, s11 = f.z + f.w;
-    t = (((s0 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7))) + ((s8 + s9) + (s10 + s11));
-  } else {
+  if (parts == 24) t = ln_tree24(q);
+  else {
     t = 0.f;
     for (int j = 0; j < parts; ++j) t += q[j];
   }
@@ -233,12 +238,6 @@ __device__ __forceinline__ float rms_row_scale(const float* ssq, int parts, int 
 
 // fused LayerNorm (mean AND variance): mean and 1 / sqrt(var + eps) of row `row` from the producer's per-32-column partial sums and
 // partial sums of squares (GemmArgs::sum_out / ssq_out), summed in rms_row_scale's fixed order; var = E[x^2] - mean^2 in fp32
-__device__ __forceinline__ float ln_tree24(const float* q) {
-  const float4 a = load4(q), b = load4(q + 4), c = load4(q + 8), d = load4(q + 12), e = load4(q + 16), f = load4(q + 20);
-  const float s0 = a.x + a.y, s1 = a.z + a.w, s2 = b.x + b.y, s3 = b.z + b.w, s4 = c.x + c.y, s5 = c.z + c.w;
-  const float s6 = d.x + d.y, s7 = d.z + d.w, s8 = e.x + e.y, s9 = e.z + e.w, s10 = f.x + f.y, s11 = f.z + f.w;
-  return (((s0 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7))) + ((s8 + s9) + (s10 + s11));
-}
 __device__ __forceinline__ void ln_row_stats(const float* sum, const float* ssq, int parts, int row, float invk, float eps, float& mean, float& rstd) {
   const float* qs = sum + (long long)row * parts;
   const float* qq = ssq + (long long)row * parts;
@@ -302,9 +301,9 @@ struct GemmDev {
 };
 
 // ACT >= 0: compile-time activation; ACT == -1: runtime p.act. VEC: 4-wide vector epilogue. ASMLDS: inline-asm LDS-DMA.
-// gemm_x3_kernel below is a copy of this body for fp32 operands (split-bf16 products): a fix to the pipeline or to the fp32
-// epilogues here belongs there too.
-template <typename T, typename TL, int ACT, bool VEC, bool ASMLDS, bool W8 = false>
+// X3 (precision "bf16x3", fp32 operands): the products run in split-bf16 -- mma_block splits the fp32 fragments into FragX3 where
+// they are consumed and issues three bf16 MFMAs per block; LDS tiles, pipeline, epilogues and launch geometry are the fp32 kernel's.
+template <typename T, typename TL, int ACT, bool VEC, bool ASMLDS, bool W8 = false, bool X3 = false>
 __global__ __launch_bounds__(TL::THREADS, TL::MINW) void gemm_kernel(const GemmDev p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int RB = TL::RB, NS = TL::NS, CPR = TL::CPR;
@@ -312,6 +311,7 @@ __global__ __launch_bounds__(TL::THREADS, TL::MINW) void gemm_kernel(const GemmD
   constexpr int RBW = W8 ? RB / 2 : RB, CPRW = RBW / 16, PWN = W8 ? TL::PW / 2 : TL::PW;
   constexpr int ESW = W8 ? 1 : (int)sizeof(T);
   static_assert(!W8 || (sizeof(T) == 2 && ASMLDS && VEC && TL::PW % 2 == 0), "fp8 weights: bf16 path, asm LDS-DMA, vector epilogue");
+  static_assert(!X3 || (sizeof(T) == 4 && !W8), "split-bf16 products: fp32 operands");
   constexpr int BK = RB / (int)sizeof(T);
   constexpr int EPC = KCfg<T>::EPC;
   constexpr int KSTEPS = BK / 16;
@@ -456,11 +456,19 @@ __global__ __launch_bounds__(TL::THREADS, TL::MINW) void gemm_kernel(const GemmD
     // MFMAs of k-step buffer cb for mi in [mi0, mi1); when `dma`, the pieces of `slice` are issued into `stage` one
     // (PPM) per MFMA, in MFMA order
     auto mma_block = [&](int mi0, int mi1, int cb, bool dma, int stage, int slice) {
+      FragX3 xa[X3 ? MI : 1], xw[X3 ? NI : 1];   // split where the fragments are consumed: their ds_reads were issued a k-step earlier
+      if constexpr (X3) {
+#pragma unroll
+        for (int mi = mi0; mi < mi1; ++mi) xa[mi].split(fa[cb][mi]);
+#pragma unroll
+        for (int ni = 0; ni < NI; ++ni) xw[ni].split(fw[cb][ni]);
+      }
 #pragma unroll
       for (int mi = mi0; mi < mi1; ++mi)
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni) {
-          acc[mi][ni] = mma(fw[cb][ni], fa[cb][mi], acc[mi][ni]);
+          if constexpr (X3) acc[mi][ni] = mma(xw[ni], xa[mi], acc[mi][ni]);
+          else acc[mi][ni] = mma(fw[cb][ni], fa[cb][mi], acc[mi][ni]);
           if (dma) {
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -616,7 +624,8 @@ __global__ __launch_bounds__(TL::THREADS, TL::MINW) void gemm_kernel(const GemmD
             const int nl = ni * 32 + 8 * q + 4 * hi;
             float4 v = make_float4(acc[mi][ni][4 * q] * rsc, acc[mi][ni][4 * q + 1] * rsc, acc[mi][ni][4 * q + 2] * rsc, acc[mi][ni][4 * q + 3] * rsc);
             const int nb = n0 + wn * WCOLS + nl;
-            if (p.wscale && nb < p.N) { const float4 sc = load4(p.wscale + nb); v.x *= sc.x; v.y *= sc.y; v.z *= sc.z; v.w *= sc.w; }
+            // (wscale is set for fp8 weights only; the split-bf16 instantiations leave the dead test out)
+            if constexpr (!X3) if (p.wscale && nb < p.N) { const float4 sc = load4(p.wscale + nb); v.x *= sc.x; v.y *= sc.y; v.z *= sc.z; v.w *= sc.w; }
             if (bias && nb < p.N) { const float4 b = load4(bias + nb); v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w; }
             if (act != ACT_NONE) { v.x = apply_act_t<T>(v.x, act); v.y = apply_act_t<T>(v.y, act); v.z = apply_act_t<T>(v.z, act); v.w = apply_act_t<T>(v.w, act); }
             *reinterpret_cast<float4*>(stage + l31 * LDE + nl) = v;
@@ -723,370 +732,7 @@ __global__ __launch_bounds__(TL::THREADS, TL::MINW) void gemm_kernel(const GemmD
           for (int e = 0; e < 4; ++e) v[e] *= rsc;
         }
         if constexpr (VEC) {   // N % 4 == 0 => n + 3 < N
-          if (p.wscale) { const float4 sc = load4(p.wscale + n); v[0] *= sc.x; v[1] *= sc.y; v[2] *= sc.z; v[3] *= sc.w; }
-          if (bias) { const float4 b = load4(bias + n); v[0] += b.x; v[1] += b.y; v[2] += b.z; v[3] += b.w; }
-          if (act != ACT_NONE) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = apply_act_t<T>(v[e], act);
-          }
-          if (mul) { const float4 g = load4(mul + (long long)m * p.ldmul + n); v[0] *= g.x; v[1] *= g.y; v[2] *= g.z; v[3] *= g.w; }
-          if (res) { const float4 r4 = load4(res + (long long)m * p.ldres + n); v[0] += r4.x; v[1] += r4.y; v[2] += r4.z; v[3] += r4.w; }
-          if (resT) { const float4 r4 = load4(resT + (long long)m * p.ldresT + n); v[0] += r4.x; v[1] += r4.y; v[2] += r4.z; v[3] += r4.w; }
-          const float4 o = make_float4(v[0], v[1], v[2], v[3]);
-          if (out32) store4(out32 + orow * p.ld32 + n, o);
-          if (outT) {
-            if (p.split_n) {
-              if (n < p.split_n) store4(reinterpret_cast<T*>(p.outT_lo) + (long long)m * p.ldT_lo + n, o);
-              else store4(outT + orow * p.ldT + (n - p.split_n), o);
-            } else store4(outT + orow * p.ldT + n, o);
-          }
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int ne = n + e;
-            if (ne >= p.N) break;
-            float x = v[e];
-            if (bias) x += bias[ne];
-            x = apply_act_t<T>(x, act);
-            if (mul) x *= Elem<T>::load(mul + (long long)m * p.ldmul + ne);
-            if (res) x += res[(long long)m * p.ldres + ne];
-            if (resT) x += Elem<T>::load(resT + (long long)m * p.ldresT + ne);
-            if (out32) out32[orow * p.ld32 + ne] = x;
-            if (outT) Elem<T>::store(outT + orow * p.ldT + ne, x);
-          }
-        }
-      }
-    }
-  }
-}
-
-// precision "bf16x3": gemm_kernel<float, TL, ACT, VEC, ASMLDS> with the products in split-bf16 (FragX3 on the fp32 fragments)
-// -- same LDS tiles, pipeline, epilogues and launch geometry. A separate body rather than a template flag of gemm_kernel, so that
-// the existing kernels keep their names and their code.
-template <typename TL, int ACT, bool VEC, bool ASMLDS>
-__global__ __launch_bounds__(TL::THREADS, TL::MINW) void gemm_x3_kernel(const GemmDev p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  using T = float;
-  constexpr int RB = TL::RB, NS = TL::NS, CPR = TL::CPR;
-  // W operand geometry: bf16 / fp32 rows like A, or fp8 rows of half the bytes (half the LDS-DMA pieces per K-slice)
-  constexpr int BK = RB / (int)sizeof(T);
-  constexpr int EPC = KCfg<T>::EPC;
-  constexpr int KSTEPS = BK / 16;
-  constexpr int MI = TL::MI, NI = TL::NI, NW = TL::NW;
-  static_assert(KSTEPS >= 2 && (KSTEPS % 2) == 0, "fragment double buffer assumes an even number of k-steps");
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int hi = lane >> 5;
-  const int l31 = lane & 31;
-
-  // XCD-aware tile mapping (block b runs on XCD b % 8): one XCD walks all n-tiles of its A panel back to back
-  const int bid = blockIdx.x;
-  int tm, tn;
-  if (p.raster == 2) {
-    tn = bid % p.ntiles;
-    tm = bid / p.ntiles;
-  } else {
-    const int xcd = bid & 7;
-    const int idx = bid >> 3;
-    if (p.raster == 0) {
-      tn = idx % p.ntiles;
-      tm = (idx / p.ntiles) * 8 + xcd;
-    } else {
-      const int mtx = (p.mtiles + 7) >> 3;                 // A panels per XCD
-      const int full = p.ntiles / p.ngroup;                // complete n-groups
-      const int per_group = mtx * p.ngroup;
-      int g = idx / per_group, rem, ng;
-      if (g < full) { rem = idx - g * per_group; ng = p.ngroup; }
-      else { g = full; rem = idx - full * per_group; ng = p.ntiles - full * p.ngroup; }
-      tn = g * p.ngroup + rem % ng;
-      tm = (rem / ng) * 8 + xcd;
-    }
-  }
-  if (tm >= p.mtiles) return;
-  const int z = blockIdx.y;
-  const int m0 = tm * TL::BM, n0 = tn * TL::BN;
-
-  const T* A = reinterpret_cast<const T*>(p.A) + (long long)z * p.bsA;
-  const char* W = reinterpret_cast<const char*>(p.W) + (long long)z * p.bsW * (long long)sizeof(T);
-  // 8 slots per workgroup: 0-3 shader-clock stamps, 4/5 constant-rate (100 MHz) real-time at start/end, 6 HW_ID, 7 XCC_ID
-  auto stamp = [&](int slot) {
-    if (p.dbg && tid == 0) {
-      long long* d = p.dbg + (long long)blockIdx.x * 8;
-      d[slot] = (long long)__builtin_readcyclecounter();
-      if (slot == 0) {
-        d[4] = (long long)__builtin_amdgcn_s_memrealtime();
-        d[6] = (long long)__builtin_amdgcn_s_getreg((31 << 11) | 4);    // HW_REG_HW_ID
-        d[7] = (long long)__builtin_amdgcn_s_getreg((31 << 11) | 20);   // HW_REG_XCC_ID
-      }
-      if (slot == 3) d[5] = (long long)__builtin_amdgcn_s_memrealtime();
-    }
-  };
-  stamp(0);
-
-  // per-lane source pointers of this wave's LDS-DMA pieces of one K-slice (piece = 1 KiB = 1024/RB tile rows)
-  const T* srcA[TL::PA];
-  const char* srcW[TL::PW];
-#pragma unroll
-  for (int i = 0; i < TL::PA; ++i) {
-    const int s = (i * NW + w) * 64 + lane;
-    const int r = s / CPR, pp = s % CPR;
-    const int c = pp ^ swz<RB>(r);
-    int ra = m0 + r; ra = ra < p.M ? ra : p.M - 1;
-    srcA[i] = A + (long long)ra * p.lda + c * EPC;
-  }
-#pragma unroll
-  for (int i = 0; i < TL::PW; ++i) {
-    const int s = (i * NW + w) * 64 + lane;
-    const int r = s / CPR, pp = s % CPR;
-    const int c = pp ^ swz<RB>(r);
-    int rw = n0 + r; rw = rw < p.N ? rw : p.N - 1;
-    srcW[i] = W + ((long long)rw * p.ldw) * (long long)sizeof(T) + c * 16;
-  }
-
-  f32x16_t acc[MI][NI];
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.0f;
-
-  const int wm = w / TL::WN, wn = w % TL::WN;
-  const int arow = wm * (MI * 32) + l31;   // + mi*32
-  const int wrow = wn * (NI * 32) + l31;   // + ni*32
-  const int nk = p.K / BK;
-  const unsigned smem_base = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
-
-  // one 1-KiB LDS-DMA piece j of K-slice kt into `stage` (j < PA: A tile rows, else W tile rows)
-  constexpr int NP = TL::PA + TL::PW;
-  auto issue_piece = [&](int stage, int kt, int j) {
-    const int i = j < TL::PA ? j : j - TL::PA;
-    const int off = stage * TL::STAGE_BYTES + (j < TL::PA ? 0 : TL::A_BYTES) + (i * NW + w) * 1024;
-    const void* src = j < TL::PA ? (const void*)(srcA[i] + kt * BK) : (const void*)(srcW[i] + kt * RB);
-    if constexpr (ASMLDS) glds16_asm(src, smem_base + off);
-    else glds16(src, smem + off);
-  };
-
-  // Software pipeline (NS LDS stages in a ring, fragments double-buffered in registers):
-  //   slice kt, steps kk = 0 .. KSTEPS-2 : prefetch fragments of step kk+1 (same stage)      | MFMAs of step kk
-  //   last step                          : counted vmcnt + lgkmcnt(0), s_barrier -> every wave has finished READING
-  //                                        stage kt % NS and the DMA of slice kt+1 has landed; then prefetch the
-  //                                        fragments of slice kt+1 / step 0 and issue the DMA of slice kt+NS into the
-  //                                        stage just freed, one piece between two MFMAs   | MFMAs of the last step
-  // so the barrier, the LDS refill latency after it and the VMEM issue are covered by the last step's MFMAs (whose
-  // operands are already in registers). VMEM loads retire in order, so `vmcnt(n * NP)` = "all but the n youngest slices".
-  auto wait_slices_and_barrier = [&](int younger) {   // `younger` slices of DMA may stay in flight (wave-uniform)
-    if constexpr (ASMLDS) {
-      if (younger <= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(NP) : "memory");
-      else if (younger == 2 || NS <= 3) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(2 * NP) : "memory");
-      else if (younger == 3 || NS <= 4) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(NS > 3 ? 3 * NP : 0) : "memory");
-      else asm volatile("s_waitcnt vmcnt(%0)" ::"i"(NS > 4 ? 4 * NP : 0) : "memory");
-      __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0) via the builtin: keeps hipcc's scoreboard exact
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-    } else {
-      wait_all_and_barrier();
-    }
-  };
-  static_assert(NS >= 2 && NS <= 5 && (NS - 1) * NP <= 63, "ring depth (vmcnt is a 6-bit counter)");
-  const int npro = nk < NS ? nk : NS;
-  for (int t = 0; t < npro; ++t) {
-#pragma unroll
-    for (int j = 0; j < NP; ++j) issue_piece(t, t, j);
-  }
-  wait_slices_and_barrier(npro - 1);   // start as soon as slice 0 has landed
-  stamp(1);
-  Frag<T> fa[2][MI], fw[2][NI];
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi) fa[0][mi].template load<RB>(smem, arow + mi * 32, 0, hi);
-#pragma unroll
-  for (int ni = 0; ni < NI; ++ni) fw[0][ni].template load<RB>(smem + TL::A_BYTES, wrow + ni * 32, 0, hi);
-  // The two waves that share a SIMD (w and w + NW/2 of an 8-wave workgroup) run the SAME instruction stream in lock
-  // step after every barrier; if both fetch fragments at the same moment the matrix pipe idles, then both compete
-  // for it. The second half of the waves therefore issues its fragment prefetch in the MIDDLE of each step's MFMAs.
-  auto main_loop = [&](auto late_tag) {
-    constexpr bool LATE = decltype(late_tag)::value;
-    constexpr int PPM = (NP + MI * NI - 1) / (MI * NI);
-    // MFMAs of k-step buffer cb for mi in [mi0, mi1); when `dma`, the pieces of `slice` are issued into `stage` one
-    // (PPM) per MFMA, in MFMA order
-    auto mma_block = [&](int mi0, int mi1, int cb, bool dma, int stage, int slice) {
-      FragX3 xa[MI], xw[NI];   // split where the fragments are consumed: their ds_reads were issued a k-step earlier
-#pragma unroll
-      for (int mi = mi0; mi < mi1; ++mi) xa[mi].split(fa[cb][mi]);
-#pragma unroll
-      for (int ni = 0; ni < NI; ++ni) xw[ni].split(fw[cb][ni]);
-#pragma unroll
-      for (int mi = mi0; mi < mi1; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni) {
-          acc[mi][ni] = mma(xw[ni], xa[mi], acc[mi][ni]);
-          if (dma) {
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int j = (mi * NI + ni) * PPM; j < (mi * NI + ni + 1) * PPM && j < NP; ++j) issue_piece(stage, slice, j);
-            __builtin_amdgcn_sched_barrier(0);
-          }
-        }
-    };
-    int cur = 0;
-    for (int kt = 0; kt < nk; ++kt) {
-      const int nxt = cur + 1 == NS ? 0 : cur + 1;
-      const char* sA = smem + cur * TL::STAGE_BYTES;
-      const char* sW = sA + TL::A_BYTES;
-      const char* nA = smem + nxt * TL::STAGE_BYTES;
-      const char* nW = nA + TL::A_BYTES;
-#pragma unroll
-      for (int kk = 0; kk < KSTEPS; ++kk) {
-        const int cb = kk & 1, nb = cb ^ 1;
-        if (kk + 1 < KSTEPS) {   // prefetch the next step's fragments while this step's MFMAs run
-          if constexpr (LATE) {
-            __builtin_amdgcn_sched_barrier(0);
-            mma_block(0, MI / 2, cb, false, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-          }
-#pragma unroll
-          for (int mi = 0; mi < MI; ++mi) fa[nb][mi].template load<RB>(sA, arow + mi * 32, kk + 1, hi);
-#pragma unroll
-          for (int ni = 0; ni < NI; ++ni) fw[nb][ni].template load<RB>(sW, wrow + ni * 32, kk + 1, hi);
-          // pin the order: [ds_reads] then [MFMAs]; without this hipcc re-serialises read -> wait -> 2 MFMAs
-          __builtin_amdgcn_sched_barrier(0);
-          mma_block(LATE ? MI / 2 : 0, MI, cb, false, 0, 0);
-          __builtin_amdgcn_sched_barrier(0);
-        } else {
-          // slices issued so far: up to min(nk-1, kt+NS-1); younger than kt+1 may stay in flight
-          int last = kt + NS - 1;
-          last = last < nk - 1 ? last : nk - 1;
-          wait_slices_and_barrier(last - (kt + 1));
-          if (kt + 1 < nk) {
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi) fa[nb][mi].template load<RB>(nA, arow + mi * 32, 0, hi);
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni) fw[nb][ni].template load<RB>(nW, wrow + ni * 32, 0, hi);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-          // the DMA pieces of slice kt+NS go into the stage just freed, ONE BY ONE BETWEEN the MFMAs
-          const bool more = kt + NS < nk;
-          mma_block(0, MI, cb, more, cur, kt + NS);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      cur = nxt;
-    }
-  };
-  if (kDephase && NW == 8 && w >= NW / 2) main_loop(std::true_type{});
-  else main_loop(std::false_type{});
-  stamp(2);
-  // (the barrier inside the last slice already guarantees that no wave reads the stage buffers any more, so the LDS
-  // epilogue below may reuse them)
-
-  // ------------------------------------------------------------------ epilogue
-  // acc[mi][ni][4q+e] = C[m = m0 + wm*MI*32 + mi*32 + l31][n = n0 + wn*NI*32 + ni*32 + 8q + 4hi + e]
-  const float* bias = p.bias ? p.bias + (long long)z * p.bsBias : nullptr;
-  const T* mul = p.mul ? reinterpret_cast<const T*>(p.mul) + (long long)z * p.bsMul : nullptr;
-  const float* res = p.res ? p.res + (long long)z * p.bsRes : nullptr;
-  // residual in the operand type (batch 1 only): residual GEMMs have no activation, so the activation instantiations
-  // (GELU's erf is register-hungry: the extra live values spilled there) do not carry this code
-  constexpr bool kStreamEpi = ACT == ACT_NONE || ACT == -1;
-  const T* resT = kStreamEpi ? reinterpret_cast<const T*>(p.resT) : nullptr;
-  float* out32 = p.out32 ? p.out32 + (long long)z * p.bs32 : nullptr;
-  T* outT = p.outT ? reinterpret_cast<T*>(p.outT) + (long long)z * p.bsT : nullptr;
-  const int act = ACT >= 0 ? ACT : p.act;
-
-  if constexpr (VEC) {
-    if (p.epi_lds) {
-      // LDS-transposed epilogue. The MFMA layout gives a lane 4 consecutive columns of ONE row, i.e. a store
-      // instruction touches 32 different rows with 16-32 B each (32 partial cache lines per instruction: the write
-      // path, not HBM, then bounds the epilogue, ~7 us per 256x256 tile). Each wave therefore bounces its
-      // 32-row x 64-column slabs through a private 16 KiB LDS region (free after the main loop) and finishes the
-      // epilogue row-contiguously: 16 lanes cover one 64-column row segment, so every global access (gate `mul`,
-      // residual, fp32 / bf16 stores) is a full 128/256-byte line.
-      constexpr int WCOLS = NI * 32;                        // columns of the wave tile
-      constexpr int LDE = WCOLS + 4;                        // padded fp32 row stride: conflict-free ds_write_b128
-      constexpr int LPR = WCOLS / 4;                        // lanes per row in the read-back phase
-      constexpr int RPI = 64 / LPR;                         // rows per wave-instruction
-      static_assert(TL::SMEM_BYTES / NW >= 32 * LDE * 4, "per-wave LDS slab for the epilogue");
-      float* stage = reinterpret_cast<float*>(smem + w * (TL::SMEM_BYTES / NW));
-      const int rr = lane / LPR, cc = (lane % LPR) * 4;
-      const int n = n0 + wn * WCOLS + cc;
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi) {
-        float rsc = 1.0f;   // fused RMSNorm: scale of this lane's accumulator row
-        if (p.rs_ssq) {
-          int mr = m0 + wm * (MI * 32) + mi * 32 + l31; mr = mr < p.M ? mr : p.M - 1;
-          rsc = rms_row_scale(p.rs_ssq, p.rs_parts, mr, p.rs_invk, p.rs_eps);
-        }
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int nl = ni * 32 + 8 * q + 4 * hi;
-            float4 v = make_float4(acc[mi][ni][4 * q] * rsc, acc[mi][ni][4 * q + 1] * rsc, acc[mi][ni][4 * q + 2] * rsc, acc[mi][ni][4 * q + 3] * rsc);
-            const int nb = n0 + wn * WCOLS + nl;
-            if (bias && nb < p.N) { const float4 b = load4(bias + nb); v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w; }
-            if (act != ACT_NONE) { v.x = apply_act_t<T>(v.x, act); v.y = apply_act_t<T>(v.y, act); v.z = apply_act_t<T>(v.z, act); v.w = apply_act_t<T>(v.w, act); }
-            *reinterpret_cast<float4*>(stage + l31 * LDE + nl) = v;
-          }
-#pragma unroll
-        for (int it = 0; it < 32 / RPI; ++it) {
-          const int r = it * RPI + rr;
-          float4 v = *reinterpret_cast<const float4*>(stage + r * LDE + cc);
-          const int m = m0 + wm * (MI * 32) + mi * 32 + r;
-          float sq = 0.f, sm = 0.f;
-          if (m < p.M && n < p.N) {
-            long long orow = m;
-            if (p.rb > 0) orow = (long long)(m / p.rb) * p.s_hi + (long long)(m % p.rb) * p.s_lo + p.ro;
-            if (mul) { const float4 g = load4(mul + (long long)m * p.ldmul + n); v.x *= g.x; v.y *= g.y; v.z *= g.z; v.w *= g.w; }
-            if (res) { const float4 r4 = load4(res + (long long)m * p.ldres + n); v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w; }
-            if (resT) { const float4 r4 = load4(resT + (long long)m * p.ldresT + n); v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w; }
-            if (out32) store4(out32 + orow * p.ld32 + n, v);
-            if (outT) {
-              if (p.split_n) {
-                if (n < p.split_n) store4(reinterpret_cast<T*>(p.outT_lo) + (long long)m * p.ldT_lo + n, v);
-                else store4(outT + orow * p.ldT + (n - p.split_n), v);
-              } else store4(outT + orow * p.ldT + n, v);
-            }
-            sq = sumsq4(v);
-            sm = (v.x + v.y) + (v.z + v.w);
-          }
-          if (p.ssq_out) {   // wave-uniform; 8 consecutive lanes hold 32 columns of one row: butterfly, one partial per 32 columns
-            sq += __shfl_xor(sq, 1, 64); sq += __shfl_xor(sq, 2, 64); sq += __shfl_xor(sq, 4, 64);
-            if ((lane & 7) == 0 && m < p.M && n < p.N) p.ssq_out[(long long)m * (p.N >> 5) + (n >> 5)] = sq;
-            if (p.sum_out) {   // fused LayerNorm: the row's partial SUMS as well (same columns, same tree)
-              sm += __shfl_xor(sm, 1, 64); sm += __shfl_xor(sm, 2, 64); sm += __shfl_xor(sm, 4, 64);
-              if ((lane & 7) == 0 && m < p.M && n < p.N) p.sum_out[(long long)m * (p.N >> 5) + (n >> 5)] = sm;
-            }
-          }
-        }
-      }
-      stamp(3);
-      return;
-    }
-  }
-
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi) {
-    const int m = m0 + wm * (MI * 32) + mi * 32 + l31;
-    if (m >= p.M) continue;
-    long long orow = m;
-    if (p.rb > 0) orow = (long long)(m / p.rb) * p.s_hi + (long long)(m % p.rb) * p.s_lo + p.ro;
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int n = n0 + wn * (NI * 32) + ni * 32 + 8 * q + 4 * hi;
-        if (n >= p.N) continue;
-        float v[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = acc[mi][ni][4 * q + e];
-        if (p.rs_ssq) {
-          const float rsc = rms_row_scale(p.rs_ssq, p.rs_parts, m, p.rs_invk, p.rs_eps);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] *= rsc;
-        }
-        if constexpr (VEC) {   // N % 4 == 0 => n + 3 < N
+          if constexpr (!X3) if (p.wscale) { const float4 sc = load4(p.wscale + n); v[0] *= sc.x; v[1] *= sc.y; v[2] *= sc.z; v[3] *= sc.w; }
           if (bias) { const float4 b = load4(bias + n); v[0] += b.x; v[1] += b.y; v[2] += b.z; v[3] += b.w; }
           if (act != ACT_NONE) {
 #pragma unroll
@@ -2285,28 +1931,21 @@ VIMA_KNOB(gemm_flat, gemm_flat, "VIMA_GEMM_FLAT", g_env_flat, 1)
 
 inline bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
-template <typename T, typename TL, int ACT, bool VEC, bool ASMLDS, bool W8 = false>
-int launch_inst(const GemmDev& d, dim3 grid, hipStream_t st) {
-  static PerDeviceOnce attr;   // per instantiation, per device
-  {
-    const hipError_t e = attr.ensure([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<T, TL, ACT, VEC, ASMLDS, W8>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, TL::SMEM_ALLOC); });
-    if (e != hipSuccess) return (int)e;
+// f(std::integral_constant<int, ACT>{}) for the activation `act`: the launchers whose kernels exist for all four of them
+template <typename F>
+int dispatch_act(int act, F&& f) {
+  switch (act) {
+    case ACT_NONE: return f(std::integral_constant<int, ACT_NONE>{});
+    case ACT_RELU: return f(std::integral_constant<int, ACT_RELU>{});
+    case ACT_GELU: return f(std::integral_constant<int, ACT_GELU>{});
+    case ACT_QUICKGELU: return f(std::integral_constant<int, ACT_QUICKGELU>{});
+    default: return (int)hipErrorInvalidValue;
   }
-  hipLaunchKernelGGL((gemm_kernel<T, TL, ACT, VEC, ASMLDS, W8>), grid, dim3(TL::THREADS), TL::SMEM_ALLOC, st, d);
-  return (int)hipGetLastError();
 }
 
-template <typename TL, int ACT, bool VEC, bool ASMLDS>
-int launch_inst_x3(const GemmDev& d, dim3 grid, hipStream_t st) {
-  static PerDeviceOnce attr;   // per instantiation, per device
-  {
-    const hipError_t e = attr.ensure([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_x3_kernel<TL, ACT, VEC, ASMLDS>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, TL::SMEM_ALLOC); });
-    if (e != hipSuccess) return (int)e;
-  }
-  hipLaunchKernelGGL((gemm_x3_kernel<TL, ACT, VEC, ASMLDS>), grid, dim3(TL::THREADS), TL::SMEM_ALLOC, st, d);
-  return (int)hipGetLastError();
+template <typename T, typename TL, int ACT, bool VEC, bool ASMLDS, bool W8 = false, bool X3 = false>
+int launch_inst(const GemmDev& d, dim3 grid, hipStream_t st) {
+  return launch_dyn_lds<gemm_kernel<T, TL, ACT, VEC, ASMLDS, W8, X3>>(grid, dim3(TL::THREADS), TL::SMEM_ALLOC, TL::SMEM_ALLOC, st, d);
 }
 
 template <typename T, typename TL, bool ASMLDS>
@@ -2328,51 +1967,47 @@ int launch_tile(GemmDev d, const GemmArgs& a, bool vec, hipStream_t st) {
 #ifndef VIMA_GEMM_LAB
   if constexpr (sizeof(T) == 4) {
     if (a.x3) {   // split-bf16 products, same instantiation choice as the fp32 kernel
-      if (!vec) return launch_inst_x3<TL, -1, false, ASMLDS>(d, grid, st);
-      switch (a.act) {
-        case ACT_NONE: return launch_inst_x3<TL, ACT_NONE, true, ASMLDS>(d, grid, st);
-        case ACT_RELU: return launch_inst_x3<TL, ACT_RELU, true, ASMLDS>(d, grid, st);
-        case ACT_GELU: return launch_inst_x3<TL, ACT_GELU, true, ASMLDS>(d, grid, st);
-        case ACT_QUICKGELU: return launch_inst_x3<TL, ACT_QUICKGELU, true, ASMLDS>(d, grid, st);
-        default: return (int)hipErrorInvalidValue;
-      }
+      if (!vec) return launch_inst<T, TL, -1, false, ASMLDS, false, true>(d, grid, st);
+      return dispatch_act(a.act, [&](auto act) { return launch_inst<T, TL, decltype(act)::value, true, ASMLDS, false, true>(d, grid, st); });
     }
   }
   if constexpr (sizeof(T) == 2) {
-    if (a.w8) {   // fp8 weights: always the asm LDS-DMA pipeline and the vector epilogue (checked by launch_t)
-      switch (a.act) {
-        case ACT_NONE: return launch_inst<T, TL, ACT_NONE, true, true, true>(d, grid, st);
-        case ACT_RELU: return launch_inst<T, TL, ACT_RELU, true, true, true>(d, grid, st);
-        case ACT_GELU: return launch_inst<T, TL, ACT_GELU, true, true, true>(d, grid, st);
-        case ACT_QUICKGELU: return launch_inst<T, TL, ACT_QUICKGELU, true, true, true>(d, grid, st);
-        default: return (int)hipErrorInvalidValue;
-      }
-    }
+    if (a.w8)   // fp8 weights: always the asm LDS-DMA pipeline and the vector epilogue (checked by launch_t)
+      return dispatch_act(a.act, [&](auto act) { return launch_inst<T, TL, decltype(act)::value, true, true, true>(d, grid, st); });
   }
   if (!vec) return launch_inst<T, TL, -1, false, ASMLDS>(d, grid, st);
 #endif
-  switch (a.act) {
-    case ACT_NONE: return launch_inst<T, TL, ACT_NONE, true, ASMLDS>(d, grid, st);
-    case ACT_RELU: return launch_inst<T, TL, ACT_RELU, true, ASMLDS>(d, grid, st);
-    case ACT_GELU: return launch_inst<T, TL, ACT_GELU, true, ASMLDS>(d, grid, st);
-    case ACT_QUICKGELU: return launch_inst<T, TL, ACT_QUICKGELU, true, ASMLDS>(d, grid, st);
-    default: return (int)hipErrorInvalidValue;
-  }
+  return dispatch_act(a.act, [&](auto act) { return launch_inst<T, TL, decltype(act)::value, true, ASMLDS>(d, grid, st); });
 }
 
-int g_num_cu = 0;
+// 256x256 persistent kernels: the specialised epilogue for the combinations the policy uses (0 = none of them)
+inline int persistent_epi(const GemmArgs& a, const GemmDev& d) {
+  if (a.rb != 0) return 0;
+  if (d.wide8 && !a.mul && !a.res && !a.resT && !a.ssq_out) return 1;
+  if (d.wide8 && a.mul && a.outT && !a.out8 && !a.res && !a.resT && !a.rs_ssq && !a.ssq_out) return 2;
+  if (!d.wide8 && a.out32 && !a.mul && !a.rs_ssq && !a.resT) return 3;   // fp32 (+ operand-type) output, with or without a residual
+  if (d.wide8 && a.resT && !a.mul && !a.res && !a.rs_ssq) return 4;
+  return 0;
+}
+
+// n-tiles per n-group of a persistent raster: W panels (BN rows of K elements) of one group <= `VIMA_GEMM_NGROUP_KB` (default 2560 KiB)
+// so that they stay resident in an XCD's L2, in equal groups. Only for short K: every extra group re-reads the whole A matrix (measured:
+// 131072 x 768 x 3072 in three groups 1167 -> 999 TFLOP/s; 131072 x 3072 x 768 in two groups: same time, W no longer re-streamed from
+// beyond L2)
+inline int ngroup_for(int BN, int K, int bytes_per_elem, int ntiles) {
+  static const int kb = env_int("VIMA_GEMM_NGROUP_KB", 2560);
+  const long long panel = (long long)BN * K * bytes_per_elem;
+  if (kb <= 0 || K > 1536 || (long long)ntiles * panel <= (long long)kb * 1024) return ntiles;
+  int ng = (int)((long long)kb * 1024 / panel);
+  if (ng < 1) ng = 1;
+  const int groups = (ntiles + ng - 1) / ng;
+  return (ntiles + groups - 1) / groups;
+}
 
 template <int ACT, int EPI, bool W8>
 int launch_persistent_w(const GemmDev& d, int grid, hipStream_t st) {
   constexpr int SMEM = TileL::SMEM_BYTES + TileL::NW * 4096;   // ring + epilogue slabs = 160 KiB
-  static PerDeviceOnce attr;   // per instantiation, per device
-  {
-    const hipError_t e = attr.ensure([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_persistent_kernel<ACT, EPI, W8>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, SMEM); });
-    if (e != hipSuccess) return (int)e;
-  }
-  hipLaunchKernelGGL((gemm_persistent_kernel<ACT, EPI, W8>), dim3((unsigned)grid), dim3(TileL::THREADS), SMEM, st, d);
-  return (int)hipGetLastError();
+  return launch_dyn_lds<gemm_persistent_kernel<ACT, EPI, W8>>(dim3((unsigned)grid), dim3(TileL::THREADS), SMEM, SMEM, st, d);
 }
 template <int ACT, int EPI>
 int launch_persistent_inst(const GemmDev& d, int grid, hipStream_t st) {
@@ -2385,26 +2020,14 @@ int launch_persistent_inst(const GemmDev& d, int grid, hipStream_t st) {
 
 int launch_persistent(GemmDev d, const GemmArgs& a, hipStream_t st) {
   if (a.split_n) return -1;   // (the column-split output is not part of the 256x256 epilogues)
-  if (g_num_cu == 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-    g_num_cu = n / 8 * 8;
-  }
   d.mtiles = (d.M + TileL::BM - 1) / TileL::BM;
   d.ntiles = (d.N + TileL::BN - 1) / TileL::BN;
   d.vtotal = (d.mtiles + 7) / 8 * 8 * d.ntiles;
   d.raster = 0; d.ngroup = 1; d.epi_lds = 1;
   d.dbg = a.tune ? a.tune->gemm_dbg : nullptr;
-  const int grid = d.vtotal < g_num_cu ? d.vtotal : g_num_cu;
+  const int grid = d.vtotal < num_cu() ? d.vtotal : num_cu();
   // specialised epilogues for the combinations the policy uses; everything else takes the generic instantiation
-  int epi = 0;
-  if (a.rb == 0) {
-    if (d.wide8 && !a.mul && !a.res && !a.resT && !a.ssq_out) epi = 1;
-    else if (d.wide8 && a.mul && a.outT && !a.out8 && !a.res && !a.resT && !a.rs_ssq && !a.ssq_out) epi = 2;
-    else if (!d.wide8 && a.out32 && !a.mul && !a.rs_ssq && !a.resT) epi = 3;   // fp32 (+ operand-type) output, with or without a residual
-    else if (d.wide8 && a.resT && !a.mul && !a.res && !a.rs_ssq) epi = 4;
-  }
+  const int epi = persistent_epi(a, d);
   if (a.resT && epi != 4) return -1;   // one-tile-per-workgroup kernel
   if (a.hm_D) {   // head-major output: its own instantiation (as a run-time branch of EPI 1 it cost every row-major launch ~9 %)
     if (epi != 1 || a.act != ACT_NONE) return (int)hipErrorInvalidValue;
@@ -2424,14 +2047,7 @@ int launch_persistent(GemmDev d, const GemmArgs& a, hipStream_t st) {
 template <int ACT, int EPI, bool F8>
 int launch_pp_inst2(const GemmDev& d, int grid, hipStream_t st) {
   constexpr int SMEM = 8 * 16384 + TileL::NW * 4096;   // eight half-tile slots + epilogue slabs = 160 KiB
-  static PerDeviceOnce attr;   // per instantiation, per device
-  {
-    const hipError_t e = attr.ensure([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pp_kernel<ACT, EPI, F8>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, SMEM); });
-    if (e != hipSuccess) return (int)e;
-  }
-  hipLaunchKernelGGL((gemm_pp_kernel<ACT, EPI, F8>), dim3((unsigned)grid), dim3(TileL::THREADS), SMEM, st, d);
-  return (int)hipGetLastError();
+  return launch_dyn_lds<gemm_pp_kernel<ACT, EPI, F8>>(dim3((unsigned)grid), dim3(TileL::THREADS), SMEM, SMEM, st, d);
 }
 template <int ACT, int EPI>
 int launch_pp_inst(const GemmDev& d, int grid, hipStream_t st) {
@@ -2449,51 +2065,26 @@ int launch_pp(GemmDev d, const GemmArgs& a, hipStream_t st) {
   if (a.split_n) return -1;
   if (a.a8) { if (!a.w8 || a.K % 256 != 0) return -1; }
   else if (a.w8 || (a.K / 64) % 2 != 0 || a.out8) return -1;   // (an fp8 copy of a bf16-operand GEMM's output: launch_persistent)
-  if (g_num_cu == 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-    g_num_cu = n / 8 * 8;
-    if (kLab) { const int lim = env_int("VIMA_GEMM_LAB_CUS", 0); if (lim >= 8 && lim < g_num_cu) g_num_cu = lim / 8 * 8; }   // lab only: run the persistent grid on a part of the chip
-  }
   d.mtiles = (d.M + TileL::BM - 1) / TileL::BM;
   d.ntiles = (d.N + TileL::BN - 1) / TileL::BN;
   d.vtotal = (d.mtiles + 7) / 8 * 8 * d.ntiles;
   d.raster = a.a8 ? 8 : 0; d.epi_lds = 1;     // raster 8: marker for the fp8-operand instantiation (the kernel ignores `raster`)
-  d.ngroup = d.ntiles;
-  {   // W panels of one n-group <= `VIMA_GEMM_NGROUP_KB` (default 2560 KiB) so that they stay resident in an XCD's L2
-    static int kb = -1;
-    if (kb < 0) kb = env_int("VIMA_GEMM_NGROUP_KB", 2560);
-    const long long panel = (long long)TileL::BN * a.K * (a.a8 ? 1 : 2);
-    // only for short K: every extra group re-reads the whole A matrix (measured: 131072 x 768 x 3072 in three groups
-    // 1167 -> 999 TFLOP/s; 131072 x 3072 x 768 in two groups: same time, W no longer re-streamed from beyond L2)
-    if (kb > 0 && a.K <= 1536 && (long long)d.ntiles * panel > (long long)kb * 1024) {
-      int ng = (int)((long long)kb * 1024 / panel);
-      if (ng < 1) ng = 1;
-      const int groups = (d.ntiles + ng - 1) / ng;
-      d.ngroup = (d.ntiles + groups - 1) / groups;    // equal groups
-    }
-  }
+  d.ngroup = ngroup_for(TileL::BN, a.K, a.a8 ? 1 : 2, d.ntiles);
   d.dbg = a.tune ? a.tune->gemm_dbg : nullptr;
   // The XCD raster pads the A panels to a multiple of 8 (panel tm lives on XCD tm % 8): with mtiles % 8 small and a grid of about one tile per CU
   // the panels of the last group pile up on a few XCDs -- M = 2304 (an incremental env step at batch 256: 9 panels) x 24 n-tiles gave XCD 0 48 tiles
   // for its 32 workgroups, i.e. TWO rounds for 216 tiles (49 us instead of 30). Where the plain enumeration needs fewer rounds and the problem is
   // small enough for L2 placement not to matter (<= 2 tiles per workgroup) the raster is dropped.
   d.flat = 0;
+  const int ncu = num_cu();
   {
     const long long tiles = (long long)d.mtiles * d.ntiles;
-    const long long per_xcd = (long long)((d.mtiles + 7) / 8) * d.ntiles, wg_xcd = g_num_cu / 8;
-    const long long rounds_raster = (per_xcd + wg_xcd - 1) / wg_xcd, rounds_flat = (tiles + g_num_cu - 1) / g_num_cu;
-    if (tiles <= 2LL * g_num_cu && rounds_flat < rounds_raster && gemm_flat(a.tune)) { d.flat = 1; d.vtotal = (int)tiles; }
+    const long long per_xcd = (long long)((d.mtiles + 7) / 8) * d.ntiles, wg_xcd = ncu / 8;
+    const long long rounds_raster = (per_xcd + wg_xcd - 1) / wg_xcd, rounds_flat = (tiles + ncu - 1) / ncu;
+    if (tiles <= 2LL * ncu && rounds_flat < rounds_raster && gemm_flat(a.tune)) { d.flat = 1; d.vtotal = (int)tiles; }
   }
-  const int grid = d.vtotal < g_num_cu ? d.vtotal : g_num_cu;
-  int epi = 0;
-  if (a.rb == 0) {
-    if (d.wide8 && !a.mul && !a.res && !a.resT && !a.ssq_out) epi = 1;
-    else if (d.wide8 && a.mul && a.outT && !a.out8 && !a.res && !a.resT && !a.rs_ssq && !a.ssq_out) epi = 2;
-    else if (!d.wide8 && a.out32 && !a.mul && !a.rs_ssq && !a.resT) epi = 3;   // fp32 (+ operand-type) output, with or without a residual
-    else if (d.wide8 && a.resT && !a.mul && !a.res && !a.rs_ssq) epi = 4;
-  }
+  const int grid = d.vtotal < ncu ? d.vtotal : ncu;
+  const int epi = persistent_epi(a, d);
   if (a.resT && epi != 4) return -1;
   if (a.pair32) {   // GEGLU pair over block-interleaved weights (launch_t has validated the form): its own epilogue
     if (a.a8 || a.act != ACT_GELU) return -1;
@@ -2516,14 +2107,7 @@ int launch_pp(GemmDev d, const GemmArgs& a, hipStream_t st) {
 
 template <int ACT, int EPI>
 int launch_wide_inst(const GemmDev& d, int grid, hipStream_t st) {
-  static PerDeviceOnce attr;   // per instantiation, per device
-  {
-    const hipError_t e = attr.ensure([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_wide_kernel<ACT, EPI>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, TileW::SMEM_BYTES); });
-    if (e != hipSuccess) return (int)e;
-  }
-  hipLaunchKernelGGL((gemm_wide_kernel<ACT, EPI>), dim3((unsigned)grid), dim3(TileW::THREADS), TileW::SMEM_BYTES, st, d);
-  return (int)hipGetLastError();
+  return launch_dyn_lds<gemm_wide_kernel<ACT, EPI>>(dim3((unsigned)grid), dim3(TileW::THREADS), TileW::SMEM_BYTES, TileW::SMEM_BYTES, st, d);
 }
 
 // 256 x 384 persistent kernel (option gemm_wide): returns -1 when the problem does not fit it (caller falls back)
@@ -2535,19 +2119,13 @@ int launch_wide(GemmDev d, const GemmArgs& a, hipStream_t st) {
   if (!a.resT && !a.ssq_out) epi = 1;
   else if (a.resT && !a.rs_ssq && a.act == ACT_NONE) epi = 4;
   if (!epi) return -1;
-  if (g_num_cu == 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-    g_num_cu = n / 8 * 8;
-  }
   d.mtiles = d.M / TileW::BM;
   d.ntiles = d.N / TileW::BN;
   if ((long long)d.mtiles * d.ntiles < 128) return -1;
   d.vtotal = (d.mtiles + 7) / 8 * 8 * d.ntiles;
   d.raster = 0; d.ngroup = 1; d.epi_lds = 1;
   d.dbg = a.tune ? a.tune->gemm_dbg : nullptr;
-  const int grid = d.vtotal < g_num_cu ? d.vtotal : g_num_cu;
+  const int grid = d.vtotal < num_cu() ? d.vtotal : num_cu();
   switch (a.act * 8 + epi) {
     case ACT_NONE * 8 + 1: return launch_wide_inst<ACT_NONE, 1>(d, grid, st);
     case ACT_RELU * 8 + 1: return launch_wide_inst<ACT_RELU, 1>(d, grid, st);
@@ -2559,14 +2137,7 @@ int launch_wide(GemmDev d, const GemmArgs& a, hipStream_t st) {
 
 template <int ACT, int EPI, int MIH>
 int launch_q4_inst(const GemmDev& d, int grid, hipStream_t st) {
-  static PerDeviceOnce attr;   // per instantiation, per device
-  {
-    const hipError_t e = attr.ensure([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_q4_kernel<ACT, EPI, MIH>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, Q4T<MIH>::SMEM_BYTES); });
-    if (e != hipSuccess) return (int)e;
-  }
-  hipLaunchKernelGGL((gemm_q4_kernel<ACT, EPI, MIH>), dim3((unsigned)grid), dim3(Q4::THREADS), Q4T<MIH>::SMEM_BYTES, st, d);
-  return (int)hipGetLastError();
+  return launch_dyn_lds<gemm_q4_kernel<ACT, EPI, MIH>>(dim3((unsigned)grid), dim3(Q4::THREADS), Q4T<MIH>::SMEM_BYTES, Q4T<MIH>::SMEM_BYTES, st, d);
 }
 
 // four-wave kernel (option gemm_q4: 1 = 256 x 384 tile, 2 = 128 x 384 tile): returns -1 when the problem does not fit it (caller falls back to the 256x256 kernels)
@@ -2582,32 +2153,14 @@ int launch_q4(GemmDev d, const GemmArgs& a, hipStream_t st) {
   else if (a.resT && a.act == ACT_NONE && !a.hm_D) epi = 4;
   if (!epi) return -1;
   if (epi == 5 && (a.act != ACT_NONE || a.hm_L % QC::BM != 0)) return -1;
-  if (g_num_cu == 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-    g_num_cu = n / 8 * 8;
-    if (kLab) { const int lim = env_int("VIMA_GEMM_LAB_CUS", 0); if (lim >= 8 && lim < g_num_cu) g_num_cu = lim / 8 * 8; }
-  }
   d.mtiles = d.M / QC::BM;
   d.ntiles = d.N / QC::BN;
   if ((long long)d.mtiles * d.ntiles < 128) return -1;
   d.vtotal = (d.mtiles + 7) / 8 * 8 * d.ntiles;
   d.raster = 0; d.epi_lds = 1; d.flat = 0;
-  d.ngroup = d.ntiles;
-  {   // n-groups whose W panels stay in an XCD's L2 (see launch_pp)
-    static int kb = -1;
-    if (kb < 0) kb = env_int("VIMA_GEMM_NGROUP_KB", 2560);
-    const long long panel = (long long)QC::BN * a.K * 2;
-    if (kb > 0 && a.K <= 1536 && (long long)d.ntiles * panel > (long long)kb * 1024) {
-      int ng = (int)((long long)kb * 1024 / panel);
-      if (ng < 1) ng = 1;
-      const int groups = (d.ntiles + ng - 1) / ng;
-      d.ngroup = (d.ntiles + groups - 1) / groups;
-    }
-  }
+  d.ngroup = ngroup_for(QC::BN, a.K, 2, d.ntiles);   // n-groups whose W panels stay in an XCD's L2
   d.dbg = a.tune ? a.tune->gemm_dbg : nullptr;
-  const int grid = d.vtotal < g_num_cu ? d.vtotal : g_num_cu;
+  const int grid = d.vtotal < num_cu() ? d.vtotal : num_cu();
   if (epi == 5) return launch_q4_inst<ACT_NONE, 5, MIH>(d, grid, st);
   switch (a.act * 8 + epi) {
     case ACT_NONE * 8 + 1: return launch_q4_inst<ACT_NONE, 1, MIH>(d, grid, st);
@@ -2621,15 +2174,8 @@ int launch_q4(GemmDev d, const GemmArgs& a, hipStream_t st) {
 #ifndef VIMA_GEMM_LAB
 // ------------------------------------------------------------------------------------------------ resident-K tiles
 template <typename RT, int ACT>
-int launch_resident_inst(const GemmDev& d, dim3 grid, hipStream_t st) {
-  static PerDeviceOnce attr;   // per instantiation, per device
-  {
-    const hipError_t e = attr.ensure([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_resident_kernel<RT, ACT>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, RT::NCH * RT::CHUNK); });
-    if (e != hipSuccess) return (int)e;
-  }
-  hipLaunchKernelGGL((gemm_resident_kernel<RT, ACT>), grid, dim3(RT::THREADS), (size_t)d.res_nch * RT::CHUNK, st, d);
-  return (int)hipGetLastError();
+int launch_resident_inst(const GemmDev& d, dim3 grid, hipStream_t st) {   // the limit is the tile's maximum, the launch takes what this problem's chunk buffers need
+  return launch_dyn_lds<gemm_resident_kernel<RT, ACT>>(grid, dim3(RT::THREADS), RT::NCH * RT::CHUNK, (size_t)d.res_nch * RT::CHUNK, st, d);
 }
 template <typename RT>
 dim3 resident_geometry(GemmDev& d, const GemmArgs& a);
@@ -2641,13 +2187,7 @@ int launch_resident_act(GemmDev d, const GemmArgs& a, hipStream_t st) {   // one
 template <typename RT>
 int launch_resident_tile(GemmDev d, const GemmArgs& a, hipStream_t st) {
   const dim3 grid = resident_geometry<RT>(d, a);
-  switch (a.act) {
-    case ACT_NONE: return launch_resident_inst<RT, ACT_NONE>(d, grid, st);
-    case ACT_RELU: return launch_resident_inst<RT, ACT_RELU>(d, grid, st);
-    case ACT_GELU: return launch_resident_inst<RT, ACT_GELU>(d, grid, st);
-    case ACT_QUICKGELU: return launch_resident_inst<RT, ACT_QUICKGELU>(d, grid, st);
-    default: return (int)hipErrorInvalidValue;
-  }
+  return dispatch_act(a.act, [&](auto act) { return launch_resident_inst<RT, decltype(act)::value>(d, grid, st); });
 }
 template <typename RT>
 dim3 resident_geometry(GemmDev& d, const GemmArgs& a) {
@@ -2701,25 +2241,12 @@ int launch_resident(const GemmDev& d, const GemmArgs& a, int force, hipStream_t 
 // ------------------------------------------------------------------------------------------------ skinny (M <= 32)
 #ifndef VIMA_GEMM_LAB
 template <typename ST, int ACT>
-int launch_skinny_inst(const GemmDev& d, dim3 grid, hipStream_t st) {
-  static PerDeviceOnce attr;   // per instantiation, per device
-  if (ST::SMEM > 48 * 1024) {
-    const hipError_t e = attr.ensure([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_kernel<ST, ACT>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, ST::SMEM); });
-    if (e != hipSuccess) return (int)e;
-  }
-  hipLaunchKernelGGL((gemm_skinny_kernel<ST, ACT>), grid, dim3(ST::THREADS), (size_t)ST::SMEM, st, d);
-  return (int)hipGetLastError();
+int launch_skinny_inst(const GemmDev& d, dim3 grid, hipStream_t st) {   // the limit is raised only where the tile needs more than the default 48 KiB
+  return launch_dyn_lds<gemm_skinny_kernel<ST, ACT>>(grid, dim3(ST::THREADS), ST::SMEM > 48 * 1024 ? ST::SMEM : 0, ST::SMEM, st, d);
 }
 template <typename ST>
 int launch_skinny_act(const GemmDev& d, const GemmArgs& a, dim3 grid, hipStream_t st) {
-  switch (a.act) {
-    case ACT_NONE: return launch_skinny_inst<ST, ACT_NONE>(d, grid, st);
-    case ACT_RELU: return launch_skinny_inst<ST, ACT_RELU>(d, grid, st);
-    case ACT_GELU: return launch_skinny_inst<ST, ACT_GELU>(d, grid, st);
-    case ACT_QUICKGELU: return launch_skinny_inst<ST, ACT_QUICKGELU>(d, grid, st);
-    default: return (int)hipErrorInvalidValue;
-  }
+  return dispatch_act(a.act, [&](auto act) { return launch_skinny_inst<ST, decltype(act)::value>(d, grid, st); });
 }
 // bf16 problems of at most 32 rows with a vector-aligned epilogue and no fp8 operands; < 0 = not taken. The number of waves (= the K split)
 // depends on K only.
@@ -2948,7 +2475,7 @@ int launch_t(const GemmArgs& a, hipStream_t st) {
       if (mode == 3) {
         mode = 0;
         if (a.M % 128 == 0 && a.N % 384 == 0 && a.M % 256 == 0 && a.N % 256 == 0) {
-          const long long ncu = 256;
+          const long long ncu = num_cu();
           const long long r_pp = ((long long)(a.M / 256) * (a.N / 256) + ncu - 1) / ncu;
           const long long r_h = ((long long)(a.M / 128) * (a.N / 384) + ncu - 1) / ncu;
           if (r_h * 80 <= r_pp * 93) mode = 2;
@@ -3019,6 +2546,20 @@ int launch_t(const GemmArgs& a, hipStream_t st) {
 }
 
 }  // namespace
+
+// CUs the persistent grids and the round-counting rules plan with: the current device's count at the first call, rounded down to
+// a multiple of the 8 XCDs (256 where the query fails)
+int num_cu() {
+  static const int ncu = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8)
+      n = 256;
+    n = n / 8 * 8;
+    if (kLab) { const int lim = env_int("VIMA_GEMM_LAB_CUS", 0); if (lim >= 8 && lim < n) n = lim / 8 * 8; }   // lab only: run the persistent grids on a part of the chip
+    return n;
+  }();
+  return ncu;
+}
 
 int launch_gemm(const GemmArgs& a, bool is_bf16, hipStream_t st) {
 #ifdef VIMA_GEMM_LAB

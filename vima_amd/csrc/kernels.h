@@ -108,9 +108,9 @@ struct GemmArgs {
   // out (profiling): which kernel the launcher chose = kind * 1000 + (act + 1) * 10 + epi ; kind 1 gemm_pp_kernel,
   // 2 gemm_persistent_kernel, 3 gemm_wide_kernel, 4..7 gemm_kernel with the 256x256 / 128x128 / 64x64 / 32x64 tile (epi 0),
   // 8 two-pass split-K, 10 / 11 / 12 gemm_resident_kernel with the 32x32 / 64x32 / 64x64 tile, 15 / 16 its DUAL (GEGLU pair) form on the 32x32 / 64x64 tile,
-  // 17 / 18 gemm_skinny_kernel (M <= 32) / its DUAL form, 19 / 20 gemm_q4_kernel, 21 gemm_x3_kernel (128x128 tile), 23 two-pass split-K over it
+  // 17 / 18 gemm_skinny_kernel (M <= 32) / its DUAL form, 19 / 20 gemm_q4_kernel, 21 gemm_kernel<float, ..., X3> (128x128 tile), 23 two-pass split-K over it
   int* kernel_id = nullptr;
-  // precision "bf16x3" (fp32 operands only): the products run in split-bf16 on gemm_x3_kernel -- each fp32 operand is hi + lo
+  // precision "bf16x3" (fp32 operands only): the products run in split-bf16 on gemm_kernel<float, ..., X3> -- each fp32 operand is hi + lo
   // (two bf16), a.b ~ hi_a.hi_b + hi_a.lo_b + lo_a.hi_b on v_mfma_f32_32x32x16_bf16 -- instead of v_mfma_f32_32x32x2_f32.
   // Same tiles, epilogues and split-K plan as the fp32 path.
   int x3 = 0;
@@ -132,6 +132,8 @@ struct GemmArgs {
 };
 // returns hipError_t as int; is_bf16 selects the operand type
 int launch_gemm(const GemmArgs& a, bool is_bf16, hipStream_t st);
+// CUs the persistent GEMM grids plan with (the device's count rounded down to a multiple of 8; queried once)
+int num_cu();
 // Bytes of split-K scratch this problem wants (0: single pass). Deterministic two-pass split-K: pass 1 = the same GEMM
 // kernel over S K-ranges writing fp32 partials, pass 2 = gemm_reduce_kernel (sum in split order + the full epilogue).
 size_t gemm_splitk_bytes(const GemmArgs& a, bool is_bf16);

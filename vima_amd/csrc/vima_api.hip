@@ -1314,7 +1314,8 @@ int t5_stack(Run& R, float* x, const uint8_t* mask, int B, int L, float* out32, 
   // side are then slower than the one (batch 32: 9.10 -> 8.78 ms, batch 40: 10.57 -> 10.28; batch 24 / 48 / 64 the other way round: profiles/r06_dual_stream_thresholds.txt).
   // Option dual_t5_rows > 0 replaces the rule by a plain minimum row count.
   const long long t5_rows = (long long)B * L, t5_tiles768 = (t5_rows + 255) / 256 * (kT5Model / 256);
-  const bool one_round = h->dual_t5_rows == 0 && t5_tiles768 > 168 && t5_tiles768 <= 256;
+  // (169 .. 256 on the 256 CUs of an MI355X; the lower bound, about two thirds of a round, scales with the chip as the round does)
+  const bool one_round = h->dual_t5_rows == 0 && t5_tiles768 > num_cu() * 168 / 256 && t5_tiles768 <= num_cu();
   const bool dual = h->dual_stream && B >= 2 && t5_rows >= h->dual_t5_rows && !one_round;
   const int nb[2] = {dual ? B - B / 2 : B, dual ? B / 2 : 0};
   T5Buf buf[2];

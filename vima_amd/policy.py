@@ -538,6 +538,7 @@ class VIMAPolicy(nn.Module):
                    16: "vima::gemm_resident_kernel<RTile<64, 64, 2, 2, 1, true>> (GEGLU pair)",
                    17: "vima::gemm_skinny_kernel", 18: "vima::gemm_skinny_kernel (GEGLU pair)", 19: "vima::gemm_q4_kernel", 20: "vima::gemm_q4_kernel",
                    21: "vima::gemm_x3_kernel<Tile<128, 128>>", 23: "vima::gemm_x3_kernel (two-pass split-K)"}
+    # (kinds 21 / 23 run gemm_kernel<float, ..., X3>; the labels are the keys recorded profiles and their readers use for these kinds and stay)
 
     def _gemm_kernel_name(self, kid: int) -> str:
         kind, rest = divmod(int(kid), 1000)
