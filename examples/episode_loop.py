@@ -2,13 +2,15 @@
 the VIMA-Bench simulator (not installable offline): prompt encoded once per episode, then per env step
 observation tokens -> decoder -> action distribution -> embedded action for the next step.
 
-    python examples/episode_loop.py [--model 200M] [--batch 1] [--steps 8] [--refeed] [--frames]
+    python examples/episode_loop.py [--model 200M] [--batch 1] [--steps 8] [--refeed] [--frames] [--device-actions]
 
 --refeed reproduces the reference loop literally (the whole history goes through `forward` every step); the default
 uses `forward_step`, which processes only the newest tokens against the episode caches and gives the same predictions.
 --frames starts every env step from raw camera frames + segmentation maps (what env.step() returns in the reference) and
 runs the GPU image preprocessing (`vima_amd.preprocess.prepare_obs` -> vima_crop_objects: mask -> bbox -> crop -> 32x32
 INTER_AREA) instead of feeding ready-made crops; batch 1 like the reference loop.
+--device-actions selects the action on the GPU: `policy.act` (vima_act: action head, mode, de-discretisation and action embedding
+in one native call) instead of forward_action_decoder -> mode -> forward_action_token -> _de_discretize_actions.
 """
 import argparse
 import os
@@ -29,6 +31,7 @@ def main():
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--refeed", action="store_true")
     ap.add_argument("--frames", action="store_true")
+    ap.add_argument("--device-actions", action="store_true")
     args = ap.parse_args()
     if args.frames:
         args.batch = 1
@@ -74,10 +77,15 @@ def run_episode(policy, args, observations, prompt_tokens, prompt_masks):
         else:
             predicted = policy.forward_step(obs_token, obs_mask, act_cache[-1] if act_cache else None, prompt_tokens,
                                             prompt_masks, step=t)
-        dists = policy.forward_action_decoder(predicted.unsqueeze(0))
-        actions = {k: v.mode() for k, v in dists.items()}                         # discrete bins, [1,B,n]
-        act_cache.append(policy.forward_action_token(actions))                    # [1,B,E] for the next step
-        continuous = policy._de_discretize_actions(actions)                       # what env.step() would receive
+        if args.device_actions:                                                   # the four stages of the else branch as ONE native call
+            sel = policy.act(predicted.unsqueeze(0))
+            act_cache.append(sel.action_token)                                    # [1,B,E] for the next step
+            continuous = sel.continuous                                           # what env.step() would receive
+        else:
+            dists = policy.forward_action_decoder(predicted.unsqueeze(0))
+            actions = {k: v.mode() for k, v in dists.items()}                     # discrete bins, [1,B,n]
+            act_cache.append(policy.forward_action_token(actions))
+            continuous = policy._de_discretize_actions(actions)
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) / args.steps * 1e3
     return (f"{args.model} batch {B}: {args.steps} env steps, {ms:.2f} ms per step ({'history re-fed' if args.refeed else 'incremental'}); "

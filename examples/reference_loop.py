@@ -4,6 +4,7 @@ as a function: ONE episode of
     prompt -> forward_prompt_assembly (once) ; per env step: frames -> prepare_obs -> forward_obs_token -> forward over the
     whole history (or forward_step, the incremental form) -> forward_action_decoder -> mode -> forward_action_token (next
     step's history) -> _de_discretize_actions -> scale to the task's action bounds -> env.step
+    (device_actions=True: the five stages after `forward` are ONE call, `policy.act`, on the GPU)
 
 with the environment, the tokenizer and the two image-preprocessing functions passed in. With `vima_amd.preprocess.prepare_obs`
 / `prepare_prompt_images` and a `vima_amd` policy everything from the camera frames on runs on the GPU; the call sequence --
@@ -11,7 +12,7 @@ every policy method, its arguments and keyword names -- is the reference loop's:
 reference's own `main()` (compiled from its source with `ast`) and this function against the same recording policy and
 requires identical call logs, then the GPU test runs this function on the box where /root/reference does not exist.
 
-    python examples/reference_loop.py [--model 20M] [--steps 6] [--incremental]     (synthetic environment, random weights)
+    python examples/reference_loop.py [--model 20M] [--steps 6] [--incremental] [--device-actions]     (synthetic environment, random weights)
 """
 from __future__ import annotations
 
@@ -34,9 +35,11 @@ def encode_prompt(prompt, prompt_assets, *, tokenizer, placeholders, prepare_pro
     return [token_type], word_batch, image_batch
 
 
-def run_episode(policy, env, *, tokenizer, placeholders, prepare_obs, prepare_prompt_images, device, views=VIEWS, incremental=False):
+def run_episode(policy, env, *, tokenizer, placeholders, prepare_obs, prepare_prompt_images, device, views=VIEWS, incremental=False,
+                device_actions=False):
     """One episode; returns the per-step records {"discrete": {key: int64 [n]}, "continuous": {key: float32 [n]}} (what
-    `env.step` received is `continuous`)."""
+    `env.step` received is `continuous`). `device_actions=True` (vima_amd policies only) replaces forward_action_decoder -> mode ->
+    forward_action_token -> _de_discretize_actions -> rescale / clamp by ONE call of `policy.act`, which does all of it on the GPU."""
     device = torch.device(device)
     obs = env.reset()
     env.render()
@@ -67,14 +70,19 @@ def run_episode(policy, env, *, tokenizer, placeholders, prepare_obs, prepare_pr
             acts = torch.stack(hist_act).unsqueeze(1) if hist_act else None             # [T - 1, 1, E]
             predicted = policy.forward(obs_token=toks, action_token=acts, prompt_token=prompt_tokens,
                                        prompt_token_mask=prompt_masks, obs_mask=msks)[-1].unsqueeze(0)         # [1, 1, E]
-        dists = policy.forward_action_decoder(predicted)
-        discrete = {k: d.mode() for k, d in dists.items()}
-        hist_act.append(policy.forward_action_token(discrete)[0, 0])
-        cont = policy._de_discretize_actions(discrete)
-        for k in ("pose0_position", "pose1_position"):
-            cont[k] = torch.clamp(cont[k] * (high - low) + low, min=low, max=high)
-        for k in ("pose0_rotation", "pose1_rotation"):
-            cont[k] = torch.clamp(cont[k] * 2 - 1, min=-1, max=1)
+        if device_actions:
+            sel = policy.act(predicted, action_bounds=meta["action_bounds"])
+            discrete, cont = sel.actions, sel.continuous
+            hist_act.append(sel.action_token[0, 0])
+        else:
+            dists = policy.forward_action_decoder(predicted)
+            discrete = {k: d.mode() for k, d in dists.items()}
+            hist_act.append(policy.forward_action_token(discrete)[0, 0])
+            cont = policy._de_discretize_actions(discrete)
+            for k in ("pose0_position", "pose1_position"):
+                cont[k] = torch.clamp(cont[k] * (high - low) + low, min=low, max=high)
+            for k in ("pose0_rotation", "pose1_rotation"):
+                cont[k] = torch.clamp(cont[k] * 2 - 1, min=-1, max=1)
         to_env = {k: v.cpu().numpy()[0, 0] for k, v in cont.items()}
         records.append({"discrete": {k: v[0, 0].cpu() for k, v in discrete.items()}, "continuous": to_env})
         obs, _, done, _ = env.step(to_env)
@@ -96,12 +104,14 @@ def main():
     ap.add_argument("--model", default="20M")
     ap.add_argument("--steps", type=int, default=6)
     ap.add_argument("--incremental", action="store_true")
+    ap.add_argument("--device-actions", action="store_true")
     args = ap.parse_args()
     cfg = syn.config(args.model)
     policy = VIMAPolicy(**cfg.ctor_kwargs(), precision="bf16", device="cuda:0")
     policy.load_state_dict(syn.make_state_dict(cfg, 0, head_gain=0.5), strict=True)
     recs = run_episode(policy, SyntheticEnv(n_steps=args.steps), tokenizer=FixedTokenizer(), placeholders=placeholders(),
-                       prepare_obs=prepare_obs, prepare_prompt_images=prepare_prompt_images, device="cuda:0", incremental=args.incremental)
+                       prepare_obs=prepare_obs, prepare_prompt_images=prepare_prompt_images, device="cuda:0", incremental=args.incremental,
+                       device_actions=args.device_actions)
     for t, r in enumerate(recs):
         print(t, {k: v.tolist() for k, v in r["discrete"].items()})
 

@@ -163,13 +163,42 @@ int vima_decode_restart(VimaHandle* h, const uint8_t* restart, int B, const floa
 
 /* VIMAPolicy.forward_action_decoder (vima_policy.py:264-265 -> action_decoder.py:51-52,165-166): tokens f32 [R,E]
  * -> raw logits f32 [R,700] = concat over keys (pose0_position, pose0_rotation, pose1_position, pose1_rotation) of
- * the 12 MLP outputs; the MultiCategorical wrapper (dists.py) stays on the host side. */
+ * the 12 MLP outputs. The distribution over them (dists.py MultiCategorical: mode / sample / log_prob / entropy) is available on
+ * the device from vima_action_select and vima_act below; the Python MultiCategorical wrapper of forward_action_decoder remains
+ * as the reference's host-side interface. */
 int vima_action_head(VimaHandle* h, const float* tokens, int R, float* out_logits, vima_stream_t stream);
 
 /* VIMAPolicy.forward_action_token (vima_policy.py:261-262 -> :301-322 -> action_embd.py:29-56): discrete bin
  * indices i64, keys in sorted order: pose0_position [R,2], pose0_rotation [R,4], pose1_position [R,2],
  * pose1_rotation [R,4] -> out f32 [R,E]. */
 int vima_action_embed(VimaHandle* h, const int64_t* const idx[4], int R, float* out, vima_stream_t stream);
+
+/* Action selection on the device (additive, ABI version unchanged): what the eval loop does between the logits and env.step
+ * (MultiCategorical.mode / sample / log_prob / entropy, dists.py:7-28; _de_discretize_actions, vima_policy.py:301-322; the rescaling to
+ * the task's action bounds, scripts/example.py:213-234) as ONE launch of act_select_kernel, one workgroup per row. No handle: there
+ * are no weights involved. logits f32 [R,700] (the layout of vima_action_head); the 12 segments are (50,100 | 50 x4 | 50,100 | 50 x4).
+ *   u       f32 [R,12] uniforms or NULL. NULL: every bin is the mode = the FIRST index of the segment's maximum (torch.argmax of the
+ *           logits, exact comparisons). Otherwise the inverse-CDF sample: bin = number of bins whose inclusive cumulative probability
+ *           cumsum(exp(x - max)) / sum (fp32) is <= clamp(u, [0, 1)), clamped to n - 1. Bins are always in [0, n), whatever the logits hold.
+ *   bounds  HOST float[4] = {low[0], low[1], high[0], high[1]} of the position keys (meta["action_bounds"]) or NULL; read during the call.
+ *   idx     four DEVICE arrays i64 [R,2], [R,4], [R,2], [R,4] (required): the bins, exactly what vima_action_embed takes.
+ *   cont    f32 [R,12] or NULL: (float)bin / n_bins (division by 50 / 100 like _de_discretize_actions); with bounds, positions
+ *           clamp(x * (high - low) + low, low, high) and rotations clamp(x * 2 - 1, -1, 1), every operation rounded to fp32 on its own
+ *           (no fused multiply-add), i.e. the values of the torch expressions of the reference loop, bit for bit.
+ *   log_prob, entropy  f32 [R,4] or NULL: per key, summed over the key's 2 / 4 dimensions (MultiCategorical.log_prob(bins) / .entropy());
+ *           log p = x - (max + log sum exp(x - max)). */
+int vima_action_select(const float* logits, int R, const float* u, const float* bounds, int64_t* const idx[4], float* cont,
+                       float* log_prob, float* entropy, vima_stream_t stream);
+
+/* One call from the predicted action tokens to everything the env-step loop needs, without host synchronisation: the launches of
+ * vima_action_head (tokens f32 [R,E] -> logits, bit-equal; written to logits_out f32 [R,700] when it is not NULL), then
+ * act_select_kernel as in vima_action_select (u, bounds, idx, cont, log_prob, entropy as above) which also computes the first layer
+ * of the action embedding from the bins it chose, then the rest of vima_action_embed (the batched 4 x (256 -> 256) GEMM and the post
+ * layer; identity for E = 1024) -> token f32 [R,E], bit-identical to vima_action_embed on idx. token NULL skips the embedding.
+ * Every policy_kind and precision. With option "graphs" the call is captured like the two it chains: the key holds every pointer and
+ * the VALUES of the bounds; u is read from device memory at replay, so new uniforms written in place take effect. */
+int vima_act(VimaHandle* h, const float* tokens, int R, const float* u, const float* bounds, float* logits_out, int64_t* const idx[4],
+             float* cont, float* log_prob, float* entropy, float* token, vima_stream_t stream);
 
 /* ---- baseline policies (policy_kind != VIMA_POLICY_VIMA) ---------------------------------------- */
 /* Tokens one frame pair contributes: Q = 1 (GPT), 16 (GATO: 8 patches x 2 views), 4 (FLAMINGO: Perceiver latents); feature
@@ -340,7 +369,7 @@ int vima_prof_read_gemm_launches(VimaHandle* h, int max_n, int32_t* ids, int32_t
 /* bytes currently held by the workspace arena */
 int64_t vima_workspace_bytes(VimaHandle* h);
 /* hipGraph replay (vima_set_option(h, "graphs", 1)): the per-env-step entry points (vima_obs_encode, vima_decode,
- * vima_decode_step, vima_action_head, vima_action_embed) capture their launch sequence the second time the same call
+ * vima_decode_step, vima_action_head, vima_action_embed, vima_act) capture their launch sequence the second time the same call
  * (shapes, pointers, options) is seen and replay it afterwards -- at small batch a step is ~1300 microsecond kernels and
  * the host launch rate is the bound. Results are bit-identical to eager execution. Counts since handle creation. */
 int vima_graph_stats(VimaHandle* h, int64_t* replays, int64_t* captures);

@@ -74,6 +74,8 @@ PROTOTYPES = {
                                        vp, vp]),
     "vima_action_head": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, vp]),
     "vima_action_embed": (ctypes.c_int, [vp, vp * 4, ctypes.c_int, vp, vp]),
+    "vima_action_select": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.POINTER(c_f32), vp * 4, vp, vp, vp, vp]),
+    "vima_act": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, ctypes.POINTER(c_f32), vp, vp * 4, vp, vp, vp, vp, vp]),
     "vima_op_linear": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       vp, vp]),
     "vima_op_layernorm": (ctypes.c_int, [vp, vp, vp, vp, c_f32, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),

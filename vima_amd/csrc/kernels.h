@@ -180,6 +180,26 @@ int launch_bbox_l1(const long long* bbox, const float* W, const float* b, void* 
 // first action-embedding layer for one key: x = idx / bins ; relu(W[256,K] x + b) -> T [R, ldo] at column col0
 int launch_action_l1(const long long* idx, int K, const float* W, const float* b, void* outT, int R, int ldo,
                      int col0, bool is_bf16, hipStream_t st);
+// action selection (action_select.hip), one launch per batch of rows: logits f32 [R,700] -> per segment (kHeadBins) the mode (first
+// index of the maximum) or, with u f32 [R,12], the inverse-CDF sample; idx[k] i64 [R,2|4] in the layout launch_action_l1 reads;
+// optional cont f32 [R,12] = bin / bins (has_bounds: positions clamp(x * (high - low) + low, low, high), rotations clamp(x * 2 - 1,
+// -1, 1), each operation rounded on its own), logp / ent f32 [R,4] per key; with t1 (operand type [R,1024]) also the first
+// action-embedding layer of the four keys (w0[k] f32 [256, 2|4], b0[k] f32 [256]), bit-identical to launch_action_l1 on idx
+struct ActSelectArgs {
+  const float* logits = nullptr;
+  const float* u = nullptr;
+  int R = 0;
+  int has_bounds = 0;
+  float low[2] = {0.f, 0.f}, high[2] = {1.f, 1.f};
+  long long* idx[4] = {nullptr, nullptr, nullptr, nullptr};
+  float* cont = nullptr;
+  float* logp = nullptr;
+  float* ent = nullptr;
+  void* t1 = nullptr;
+  const float* w0[4] = {nullptr, nullptr, nullptr, nullptr};
+  const float* b0[4] = {nullptr, nullptr, nullptr, nullptr};
+};
+int launch_act_select(const ActSelectArgs& a, bool is_bf16, hipStream_t st);
 // out[r, :] += table[sel[r / group]][:]   (obs_fusion end-effector term)
 int launch_add_row_table(float* out, int rows, int E, const float* table, const long long* sel, int group,
                          hipStream_t st);

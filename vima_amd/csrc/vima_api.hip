@@ -1545,6 +1545,68 @@ int run_graphed(VimaHandle* h, std::string key, hipStream_t user, F&& fn) {
   return rc;
 }
 
+// The launch sequence of vima_action_head (shared with vima_act): cast, the stacked first layers, the batched second layers, the
+// grouped (or looped) last layers -> out_logits f32 [Rn,700]
+int action_head_run(Run& R, const float* tokens, int Rn, float* out_logits) {
+  VimaHandle* h = R.h;
+  const int E = h->cfg.embed_dim;
+  const int HH = kNumHeadsOut * kHeadHidden;
+  void* tT = R.wsT((size_t)Rn * E);
+  void* h1 = R.wsT((size_t)Rn * HH);
+  void* h2 = R.wsT((size_t)Rn * HH);
+  if (R.err) return R.err;
+  OTHER(R, launch_cast(tokens, tT, (long long)Rn * E, h->bf16, R.st), "cast");
+  R.linear(tT, E, h->head1, Rn, ACT_RELU, nullptr, 0, nullptr, 0, nullptr, 0, h1, HH);
+  GemmArgs a;   // 12 independent 512x512 layers as one batched launch
+  a.A = h1; a.lda = HH; a.bsA = kHeadHidden; a.W = h->head2_W; a.ldw = kHeadHidden; a.bsW = (long long)kHeadHidden * kHeadHidden;
+  a.M = Rn; a.N = kHeadHidden; a.K = kHeadHidden; a.batch = kNumHeadsOut; a.bias = h->head2_b; a.bsBias = kHeadHidden;
+  a.act = ACT_RELU; a.outT = h2; a.ldT = HH; a.bsT = kHeadHidden;
+  R.gemm(a);
+  if (h->head3_Wall && gemm_grouped_ok(&h->tune)) {   // the 12 last layers (512 -> 50 / 100 bins) as ONE grouped launch, bit-identical to the loop below
+    GemmArgs b;
+    b.A = h2; b.lda = HH; b.bsA = kHeadHidden; b.W = h->head3_Wall; b.ldw = kHeadHidden; b.M = Rn; b.N = 100; b.K = kHeadHidden;
+    b.batch = kNumHeadsOut; b.grp_col = h->head3_col; b.bias = h->head3_ball; b.out32 = out_logits; b.ld32 = kLogits;
+    R.gemm(b);
+    return R.err;
+  }
+  int col = 0;
+  for (int j = 0; j < kNumHeadsOut; ++j) {
+    GemmArgs b;
+    b.A = R.offT(h2, (long long)j * kHeadHidden); b.lda = HH; R.setW(b, h->head3[j]);
+    b.M = Rn; b.N = kHeadBins[j]; b.K = kHeadHidden; b.bias = h->head3[j].b;
+    b.out32 = out_logits + col; b.ld32 = kLogits;
+    R.gemm(b);
+    col += kHeadBins[j];
+  }
+  return R.err;
+}
+
+// The rest of vima_action_embed after its first layer t1 (operand type [Rn,1024]; shared with vima_act): the batched 4 x (256 -> 256)
+// GEMM and the post layer -> out f32 [Rn,E]
+int action_embed_tail(Run& R, void* t1, int Rn, float* out) {
+  VimaHandle* h = R.h;
+  const int E = h->cfg.embed_dim;
+  GemmArgs a;
+  a.A = t1; a.lda = 1024; a.bsA = 256; a.W = h->act1_W; a.ldw = 256; a.bsW = 256 * 256; a.M = Rn; a.N = 256; a.K = 256; a.batch = 4;
+  a.bias = h->act1_b; a.bsBias = 256;
+  if (E == 1024) {   // Identity post layer: the concatenated 4 x 256 outputs ARE the token
+    a.out32 = out; a.ld32 = 1024; a.bs32 = 256;
+    return R.gemm(a);
+  }
+  void* t2 = R.wsT((size_t)Rn * 1024);
+  if (R.err) return R.err;
+  a.outT = t2; a.ldT = 1024; a.bsT = 256;
+  R.gemm(a);
+  return R.linear(t2, 1024, h->act_post, Rn, ACT_NONE, nullptr, 0, nullptr, 0, out, E, nullptr, 0);
+}
+
+// host bounds {low[2], high[2]} of the position keys into the kernel's argument block
+void set_bounds(ActSelectArgs& s, const float* bounds) {
+  if (!bounds) return;
+  s.has_bounds = 1;
+  s.low[0] = bounds[0]; s.low[1] = bounds[1]; s.high[0] = bounds[2]; s.high[1] = bounds[3];
+}
+
 #include "baselines.inc"
 
 }  // namespace
@@ -2370,36 +2432,7 @@ int vima_action_head(VimaHandle* h, const float* tokens, int Rn, float* out_logi
   if (int e = check_ready(h)) return e;
   if (Rn <= 0) return 0;
   Run R{h, st};
-  const int E = h->cfg.embed_dim;
-  const int HH = kNumHeadsOut * kHeadHidden;
-  void* tT = R.wsT((size_t)Rn * E);
-  void* h1 = R.wsT((size_t)Rn * HH);
-  void* h2 = R.wsT((size_t)Rn * HH);
-  if (R.err) return R.err;
-  OTHER(R, launch_cast(tokens, tT, (long long)Rn * E, h->bf16, R.st), "cast");
-  R.linear(tT, E, h->head1, Rn, ACT_RELU, nullptr, 0, nullptr, 0, nullptr, 0, h1, HH);
-  GemmArgs a;   // 12 independent 512x512 layers as one batched launch
-  a.A = h1; a.lda = HH; a.bsA = kHeadHidden; a.W = h->head2_W; a.ldw = kHeadHidden; a.bsW = (long long)kHeadHidden * kHeadHidden;
-  a.M = Rn; a.N = kHeadHidden; a.K = kHeadHidden; a.batch = kNumHeadsOut; a.bias = h->head2_b; a.bsBias = kHeadHidden;
-  a.act = ACT_RELU; a.outT = h2; a.ldT = HH; a.bsT = kHeadHidden;
-  R.gemm(a);
-  if (h->head3_Wall && gemm_grouped_ok(&h->tune)) {   // the 12 last layers (512 -> 50 / 100 bins) as ONE grouped launch, bit-identical to the loop below
-    GemmArgs b;
-    b.A = h2; b.lda = HH; b.bsA = kHeadHidden; b.W = h->head3_Wall; b.ldw = kHeadHidden; b.M = Rn; b.N = 100; b.K = kHeadHidden;
-    b.batch = kNumHeadsOut; b.grp_col = h->head3_col; b.bias = h->head3_ball; b.out32 = out_logits; b.ld32 = kLogits;
-    R.gemm(b);
-    return R.err;
-  }
-  int col = 0;
-  for (int j = 0; j < kNumHeadsOut; ++j) {
-    GemmArgs b;
-    b.A = R.offT(h2, (long long)j * kHeadHidden); b.lda = HH; R.setW(b, h->head3[j]);
-    b.M = Rn; b.N = kHeadBins[j]; b.K = kHeadHidden; b.bias = h->head3[j].b;
-    b.out32 = out_logits + col; b.ld32 = kLogits;
-    R.gemm(b);
-    col += kHeadBins[j];
-  }
-  return R.err;
+  return action_head_run(R, tokens, Rn, out_logits);
   });
 }
 
@@ -2411,23 +2444,69 @@ int vima_action_embed(VimaHandle* h, const int64_t* const idx[4], int Rn, float*
   if (int e = check_ready(h)) return e;
   if (Rn <= 0) return 0;
   Run R{h, st};
-  const int E = h->cfg.embed_dim;
   void* t1 = R.wsT((size_t)Rn * 1024);
-  void* t2 = R.wsT((size_t)Rn * 1024);
   if (R.err) return R.err;
   for (int k = 0; k < 4; ++k)
     OTHER(R, launch_action_l1((const long long*)idx[k], kActDims[k], h->act0[k].w0, h->act0[k].b0, t1, Rn, 1024, k * 256, h->bf16, R.st),
           "action_l1");
-  GemmArgs a;
-  a.A = t1; a.lda = 1024; a.bsA = 256; a.W = h->act1_W; a.ldw = 256; a.bsW = 256 * 256; a.M = Rn; a.N = 256; a.K = 256; a.batch = 4;
-  a.bias = h->act1_b; a.bsBias = 256;
-  if (E == 1024) {   // Identity post layer: the concatenated 4 x 256 outputs ARE the token
-    a.out32 = out; a.ld32 = 1024; a.bs32 = 256;
-    return R.gemm(a);
+  return action_embed_tail(R, t1, Rn, out);
+  });
+}
+
+int vima_action_select(const float* logits, int Rn, const float* u, const float* bounds, int64_t* const idx[4], float* cont,
+                       float* log_prob, float* entropy, vima_stream_t stream) {
+  if (Rn <= 0) return 0;
+  if (!logits || !idx || !idx[0] || !idx[1] || !idx[2] || !idx[3]) return fail("vima_action_select: null argument");
+  // the launch goes to the device that owns the logits (not necessarily the current one: the call has no handle)
+  int cur_dev = 0, out_dev = 0;
+  hipPointerAttribute_t pa;
+  HIPCK(hipGetDevice(&cur_dev));
+  out_dev = cur_dev;
+  if (hipPointerGetAttributes(&pa, logits) == hipSuccess) out_dev = pa.device;
+  else (void)hipGetLastError();
+  struct DeviceGuard {
+    int back; bool active;
+    ~DeviceGuard() { if (active) (void)hipSetDevice(back); }
+  } guard{cur_dev, false};
+  if (out_dev != cur_dev) {
+    HIPCK(hipSetDevice(out_dev));
+    guard.active = true;
   }
-  a.outT = t2; a.ldT = 1024; a.bsT = 256;
-  R.gemm(a);
-  return R.linear(t2, 1024, h->act_post, Rn, ACT_NONE, nullptr, 0, nullptr, 0, out, E, nullptr, 0);
+  ActSelectArgs s;
+  s.logits = logits; s.u = u; s.R = Rn; set_bounds(s, bounds);
+  for (int k = 0; k < 4; ++k) s.idx[k] = (long long*)idx[k];
+  s.cont = cont; s.logp = log_prob; s.ent = entropy;
+  const int e = launch_act_select(s, false, (hipStream_t)stream);
+  if (e) return fail(std::string("act_select launch failed: ") + hipGetErrorString((hipError_t)e), e);
+  return 0;
+}
+
+int vima_act(VimaHandle* h, const float* tokens, int Rn, const float* u, const float* bounds, float* logits_out, int64_t* const idx[4],
+             float* cont, float* log_prob, float* entropy, float* token, vima_stream_t stream) {
+  if (!h) return fail("null handle");
+  if (!tokens || !idx || !idx[0] || !idx[1] || !idx[2] || !idx[3]) return fail("vima_act: null argument");
+  uint32_t bb[4] = {0, 0, 0, 0};   // the VALUES of the bounds are kernel arguments: part of the graph key
+  if (bounds) memcpy(bb, bounds, sizeof bb);
+  const std::string key = gkey("act", {(long long)(uintptr_t)tokens, Rn, (long long)(uintptr_t)u, bounds ? 1 : 0, (long long)bb[0], (long long)bb[1],
+                                       (long long)bb[2], (long long)bb[3], (long long)(uintptr_t)logits_out, (long long)(uintptr_t)idx[0],
+                                       (long long)(uintptr_t)idx[1], (long long)(uintptr_t)idx[2], (long long)(uintptr_t)idx[3],
+                                       (long long)(uintptr_t)cont, (long long)(uintptr_t)log_prob, (long long)(uintptr_t)entropy,
+                                       (long long)(uintptr_t)token});
+  return run_graphed(h, key, (hipStream_t)stream, [&](hipStream_t st) -> int {
+  if (int e = check_ready(h)) return e;
+  if (Rn <= 0) return 0;
+  Run R{h, st};
+  float* logits = logits_out ? logits_out : R.ws<float>((size_t)Rn * kLogits);
+  void* t1 = token ? R.wsT((size_t)Rn * 1024) : nullptr;
+  if (R.err) return R.err;
+  if (action_head_run(R, tokens, Rn, logits)) return R.err;
+  ActSelectArgs s;
+  s.logits = logits; s.u = u; s.R = Rn; set_bounds(s, bounds);
+  for (int k = 0; k < 4; ++k) { s.idx[k] = (long long*)idx[k]; s.w0[k] = h->act0[k].w0; s.b0[k] = h->act0[k].b0; }
+  s.cont = cont; s.logp = log_prob; s.ent = entropy; s.t1 = t1;
+  OTHER(R, launch_act_select(s, h->bf16, R.st), "act_select");
+  if (!token || R.err) return R.err;
+  return action_embed_tail(R, t1, Rn, token);
   });
 }
 

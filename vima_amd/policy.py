@@ -8,6 +8,7 @@ Mirrors the method surface, argument meaning, return shapes and error behaviour 
     forward_obs_token             vima_policy.py:242-259   -> vima_obs_encode
     forward_action_token          vima_policy.py:261-262   -> vima_action_embed
     forward_action_decoder        vima_policy.py:264-265   -> vima_action_head (+ MultiCategorical wrapper)
+    act                           (no reference counterpart: head + mode / sample + de-discretise + embed) -> vima_act
     discretize_action             vima_policy.py:267-299
     _de_discretize_actions        vima_policy.py:301-322
     load_state_dict(strict=True)  vima/__init__.py:11-14   -> vima_set_param / vima_finalize_params
@@ -474,6 +475,37 @@ class VIMAPolicy(nn.Module):
         arr = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in idx])
         _lib.check(self._lib.vima_action_embed(self._handle, arr, R, _ptr(out), self._stream()))
         return out.view(*lead, self.embed_dim)
+
+    def act(self, predicted_action_tokens: torch.Tensor, *, sample: bool = False, generator=None, uniforms=None,
+            action_bounds=None, return_logits: bool = False):
+        """Predicted action tokens [..., E] -> `actions.ActionSelection` in ONE native call (vima_act), no host synchronisation:
+        the action head, then per action dimension the mode (default; torch.argmax of the logits) or an inverse-CDF sample
+        (`sample=True`: `uniforms` [..., 12] in [0, 1), drawn with torch.rand(R, 12, generator=generator) on the device when not
+        given), and from the chosen bins
+
+            actions       {key: int64 [..., 2|4]}    what forward_action_decoder(...)[key].mode() / .sample() return
+            continuous    {key: float32 [..., 2|4]}  _de_discretize_actions(actions); with `action_bounds` ({"low": [2], "high": [2]})
+                                                     rescaled and clamped like the reference loop (scripts/example.py:213-234)
+            action_token  float32 [..., E]           forward_action_token(actions), bit for bit
+            log_prob / entropy  {key: float32 [...]} dists[key].log_prob(actions[key]) / dists[key].entropy()
+            logits        float32 [..., 700] with return_logits=True (== action_logits(...)), else None."""
+        from . import actions as _actions
+        self._ready()
+        dev = self._device
+        lead = predicted_action_tokens.shape[:-1]
+        t = predicted_action_tokens.to(device=dev, dtype=torch.float32).reshape(-1, self.embed_dim).contiguous()
+        R = t.shape[0]
+        if uniforms is None and sample:
+            uniforms = torch.rand(R, _actions.N_DIMS, generator=generator, device=dev, dtype=torch.float32)
+        u = _actions.uniforms_arg(uniforms, R, dev)
+        idx, cont, logp, ent = _actions.alloc_outputs(R, dev)
+        token = torch.empty(R, self.embed_dim, dtype=torch.float32, device=dev)
+        logits = torch.empty(R, N_LOGITS, dtype=torch.float32, device=dev) if return_logits else None
+        arr = (ctypes.c_void_p * 4)(*[x.data_ptr() for x in idx])
+        _lib.check(self._lib.vima_act(self._handle, _ptr(t), R, _ptr(u), _actions.bounds_array(action_bounds), _ptr(logits), arr,
+                                      _ptr(cont), _ptr(logp), _ptr(ent), _ptr(token), self._stream()))
+        return _actions.package(lead, idx, cont, logp, ent, token.view(*lead, self.embed_dim),
+                                logits.view(*lead, N_LOGITS) if logits is not None else None)
 
     def discretize_action(self, action):
         """vima_policy.py:267-299 (training-side helper; mutates `action` like the reference)."""
