@@ -148,7 +148,20 @@ int vima_decode(VimaHandle* h, const float* obs_tok, const uint8_t* obs_mask, co
  * The handle keeps the per-layer prompt K/V (built at step 0, so `prompt` must be valid there) and the self-attention
  * K/V, key mask and position counters of the history. out f32 [B,E] = the predicted action token of this step, equal
  * (up to floating-point reassociation) to row `step` of vima_decode on the full history. step 0 starts a new
- * episode; any other step must follow step-1 with the same B, Q, Lp. */
+ * episode; any other step must follow step-1 with the same B, Q, Lp.
+ * The histories of the B samples share ONE row index space of n_positions rows: step s writes rows s (Q + 1) - 1 .. of every sample, so a batch
+ * takes (n_positions + 1) / (Q + 1) steps after its step 0 (code 34 beyond), restarts or not.
+ * Option "decode_ring" = 1 turns that row space into a ring, for batches that never stop (vectorised environments): a step's Q + 1 rows go
+ * to the ring's write pointer, or to row 0 when they do not fit in front of row n_positions (the tail is skipped: a step's rows are never split).
+ * `step` keeps its meaning (previous + 1) and is unbounded. A call is legal iff every row it overwrites or skips is dead for every sample:
+ * age[b] + rows advanced <= n_positions, age[b] = ring rows advanced (skipped ones included) since sample b's episode began; otherwise it fails
+ * with code 34, names the first such sample, changes nothing, and succeeds once that sample has been restarted (vima_decode_restart gives a
+ * sample's rows back; vima_decode_steps_left tells in advance). A sample's own episode is thus still bounded by n_positions tokens, the
+ * position table and the reference's limit. The self-attention reads the written part of the ring with a WINDOWED causal rule (key j is
+ * "future" for the step's query i iff i + write pointer < j < write pointer + Q + 1; the rows behind the window hold older history): the
+ * predictions of a sample depend on its own episode only and equal those of the linear cache up to the order of the softmax sums. With
+ * option "graphs" the captured graphs are keyed on (write pointer, rows read, action slot), and one eager step warms them all; the set stops growing once the
+ * high-water mark of the ring has stopped moving (during the third lap). */
 int vima_decode_step(VimaHandle* h, const float* obs_tok, const uint8_t* obs_mask, const float* act_tok, int step, int B,
                      int Q, const float* prompt, int64_t stride_b, int64_t stride_l, const uint8_t* prompt_mask,
                      int Lp, float* out, vima_stream_t stream);
@@ -157,9 +170,18 @@ int vima_decode_step(VimaHandle* h, const float* obs_tok, const uint8_t* obs_mas
  * array of B bytes): its cached history is masked out, its position counter restarts at 0, its next step has no previous action, and
  * its rows of the per-layer prompt K/V cache are rebuilt from ITS row of `prompt` / `prompt_mask` (the new episode's prompt; layout and
  * strides as in vima_decode_step; rows of the other samples are not read). The batch then keeps calling vima_decode_step with
- * step + 1 (pass any act_tok row for restarted samples: it is ignored). n_positions still bounds the steps since the batch's step 0. */
+ * step + 1 (pass any act_tok row for restarted samples: it is ignored). n_positions still bounds the steps since the batch's step 0,
+ * except with option "decode_ring", where the restart also returns the sample's rows to the ring (its age restarts at 0).
+ * The flagged samples' prompt K/V are rebuilt TOGETHER (option "restart_batched", prompts of more than 32 tokens): one gather of their
+ * prompts, one GEMM of n_flagged x Lp rows and one scatter per layer, 2 + 2 x layers launches whatever the number of flagged samples; the
+ * cache receives the bits of the per-sample loop (option 0). */
 int vima_decode_restart(VimaHandle* h, const uint8_t* restart, int B, const float* prompt, int64_t stride_b, int64_t stride_l,
                         const uint8_t* prompt_mask, int Lp, vima_stream_t stream);
+
+/* Host-only (additive, ABI version unchanged): out_host[b], b < B = how many further vima_decode_step calls of the running episode batch would
+ * succeed if sample b ALONE were never restarted again (the row bookkeeping of vima_decode_step run forward; no device work, no state change).
+ * Without option "decode_ring" the number is the same for every sample: the steps left before the whole batch must start over. */
+int vima_decode_steps_left(VimaHandle* h, int B, int32_t* out_host);
 
 /* VIMAPolicy.forward_action_decoder (vima_policy.py:264-265 -> action_decoder.py:51-52,165-166): tokens f32 [R,E]
  * -> raw logits f32 [R,700] = concat over keys (pose0_position, pose0_rotation, pose1_position, pose1_rotation) of
@@ -267,6 +289,11 @@ int vima_op_layernorm(VimaHandle* h, const float* x, const float* gamma, const f
 int vima_op_attention(VimaHandle* h, const float* q, const float* k, const float* v, const uint8_t* kmask,
                       const float* relbias, int B, int H, int Lq, int Lk, int D, float scale, int mode, int impl,
                       float* out, vima_stream_t stream);
+/* the causal mode over a RING image k/v [B,Lk,H*D] (option "decode_ring"): the Lq queries sit at rows [q_off, q_off + Lq) and key j is "future"
+ * (score -1e4) for query i iff i + q_off < j < q_off + Lq; every other key, in front of or behind the window, is visible unless kmask hides it.
+ * q_off = 0, Lq = Lk is vima_op_attention mode 2, bit for bit. impl as above. */
+int vima_op_attention_window(VimaHandle* h, const float* q, const float* k, const float* v, const uint8_t* kmask, int B, int H, int Lq,
+                             int Lk, int D, float scale, int impl, int q_off, float* out, vima_stream_t stream);
 /* precision FP8: the calibrated activation scales (dequantisation scale = headroom x max |x| / 448, see VIMA_PRECISION_FP8) of group 0 the T5 stack [12 layers][4 sites:
  * stream before qkv, attention context, stream before wi, ReLU hidden], 1 the ViT [4 blocks][4 sites: ln_1 output, attention output,
  * ln_2 output, QuickGELU hidden], 2 the decoder's prompt K/V projection [1]; returns their number (0 before that group's calibrating
@@ -327,6 +354,10 @@ int vima_t5_bucket(int relative_position);
  *                                               it (sums / sums of squares per 32 columns from attention_out's epilogue, mean / rstd applied to the GELU'd factor
  *                                               in the GEGLU pair's epilogue, gamma folded into the weight) where a pair form exists for the row count --
  *                                               the operand is then bf16(a) instead of bf16(LN(a)): same precision class, different rounding point
+ *   rollouts:                "decode_ring"  [0] the episode caches' shared row index space is a ring (vima_decode_step): a batch steps without bound as long as
+ *                                               every sample is restarted before ITS episode exceeds n_positions rows; setting it ends a running episode
+ *                            "restart_batched" [1] vima_decode_restart rebuilds the prompt K / V of all flagged samples together (prompts of more than 32
+ *                                               tokens); 0 = one sample at a time: same bits, launches proportional to the number of flagged samples
  *   scheduling:              "dual_stream"  [1] independent halves of the work on an auxiliary HIP stream
  *                            "graphs"       [0] replay the per-step entry points as captured hipGraphs
  *                            "vit_chunk"    [16384] crops per ViT pass

@@ -66,6 +66,7 @@ PROTOTYPES = {
     "vima_decode_step": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, c_i64, c_i64, vp,
                                         ctypes.c_int, vp, vp]),
     "vima_decode_restart": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, c_i64, c_i64, vp, ctypes.c_int, vp]),
+    "vima_decode_steps_left": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(c_i32)]),
     "vima_rgb_tokens_per_image": (ctypes.c_int, [ctypes.POINTER(VimaConfig)]),
     "vima_rgb_encode": (ctypes.c_int, [vp, vp * 2, ctypes.c_int, vp, vp]),
     "vima_rgb_obs_encode": (ctypes.c_int, [vp, vp * 2, vp, ctypes.c_int, vp, vp]),
@@ -81,6 +82,8 @@ PROTOTYPES = {
     "vima_op_layernorm": (ctypes.c_int, [vp, vp, vp, vp, c_f32, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),
     "vima_op_attention": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_int, ctypes.c_int, c_f32, ctypes.c_int, ctypes.c_int, vp, vp]),
+    "vima_op_attention_window": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                c_f32, ctypes.c_int, ctypes.c_int, vp, vp]),
     "vima_t5_bucket": (ctypes.c_int, [ctypes.c_int]),
     "vima_fp8_e4m3_encode": (None, [vp, vp, c_i64]),
     "vima_set_option": (ctypes.c_int, [vp, ctypes.c_char_p, c_i64]),

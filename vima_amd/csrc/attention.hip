@@ -208,11 +208,13 @@ struct AttnDev {
   int Lkr;      // K / V / mask rows per sample in memory (>= Lk)
   long long k_bs, v_bs; int k_hs, v_hs;   // K / V batch and head strides in elements (AttnArgs; defaults Lkr * ld and D)
   int q_off;    // causal: query i sits at global position i + q_off
+  int win_end;  // causal: key j is "future" for query i iff i + q_off < j < win_end. Lk for a linear cache (the plain rule); in a RING cache the step's
+                // rows end at win_end = q_off + Lq and the rows from there on hold OLDER history, which stays visible
   long long* dbg;   // optional (4-wave kernel): per workgroup 8 accumulated shader-clock phase totals of wave 0
 };
 
 __device__ __forceinline__ float score_fixup(float dot, int mode, float scale, int i, int j, int Lk, bool masked,
-                                             const float* relbias_h) {
+                                             const float* relbias_h, int win_end) {
   // literal restatement of the reference's score arithmetic (order of operations preserved)
   const float madd = masked ? -FLT_MAX : 0.0f;
   float s;
@@ -222,7 +224,7 @@ __device__ __forceinline__ float score_fixup(float dot, int mode, float scale, i
     s = dot * scale + madd;
   } else {
     s = dot * scale;
-    if (j > i) s = -1e4f;
+    if (j > i && j < win_end) s = -1e4f;
     s = s + madd;
   }
   return s;
@@ -251,7 +253,7 @@ __global__ __launch_bounds__(64) void attn_generic_kernel(const AttnDev p) {
       d = fmaf(q[c], v.x, d); d = fmaf(q[c + 1], v.y, d); d = fmaf(q[c + 2], v.z, d); d = fmaf(q[c + 3], v.w, d);
     }
     const bool masked = p.kmask && !p.kmask[(long long)b * p.Lkr + j];
-    const float s = score_fixup(d, p.mode, p.scale, i + p.q_off, j, p.Lk, masked, rb);
+    const float s = score_fixup(d, p.mode, p.scale, i + p.q_off, j, p.Lk, masked, rb, p.win_end);
     sc[j] = s;
     mx = fmaxf(mx, s);
   }
@@ -355,7 +357,7 @@ __global__ __launch_bounds__(64) void attn_mfma_kernel(const AttnDev p) {
           v = s[r] * p.scale + madd;
         } else {
           v = s[r] * p.scale;
-          if (key > qi + p.q_off) v = -1e4f;
+          if (key > qi + p.q_off && key < p.win_end) v = -1e4f;
           v = v + madd;
         }
       } else {
@@ -500,7 +502,7 @@ __global__ __launch_bounds__(64) void attn_x3_kernel(const AttnDev p) {
           v = s[r] * p.scale + madd;
         } else {
           v = s[r] * p.scale;
-          if (key > qi + p.q_off) v = -1e4f;
+          if (key > qi + p.q_off && key < p.win_end) v = -1e4f;
           v = v + madd;
         }
       } else {
@@ -899,7 +901,7 @@ __global__ __launch_bounds__(256, QG > 1 ? 2 : (D == 32 ? 4 : 3)) void attn_mfma
             float v;
             if (MODE == ATTN_T5) v = __builtin_fmaf(sv, csc, bq[kl + e]);
             else if (MODE == ATTN_CROSS) v = sv * csc;
-            else v = (k0 + kl + 4 * hi + e > qi[g] + p.q_off) ? -1e4f * kLog2e : sv * csc;
+            else v = (k0 + kl + 4 * hi + e > qi[g] + p.q_off && k0 + kl + 4 * hi + e < p.win_end) ? -1e4f * kLog2e : sv * csc;
             x[sub][4 * gg + e] = v;
           }
         }
@@ -1185,7 +1187,7 @@ __global__ __launch_bounds__(256, D == 32 ? 4 : 2) void attn_split_kernel(const 
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           float v = s[4 * g + e] * csc;
-          if (MODE == ATTN_CAUSAL && key + e > qi + p.q_off) v = -1e4f * kLog2e;
+          if (MODE == ATTN_CAUSAL && key + e > qi + p.q_off && key + e < p.win_end) v = -1e4f * kLog2e;
           v = v + mav[e];
           x[4 * g + e] = v;
           mt = fmaxf(mt, v);
@@ -1288,6 +1290,7 @@ inline AttnDev to_dev(const AttnArgs& a) {
   d.k_bs = a.k_bs > 0 ? a.k_bs : (long long)d.Lkr * a.ldk; d.v_bs = a.v_bs > 0 ? a.v_bs : (long long)d.Lkr * a.ldv;
   d.k_hs = a.k_hs > 0 ? a.k_hs : a.D; d.v_hs = a.v_hs > 0 ? a.v_hs : a.D;
   d.q_off = a.q_off;
+  d.win_end = a.win_end > 0 ? a.win_end : a.Lk;
   d.dbg = a.tune ? a.tune->attn_dbg : nullptr;
   return d;
 }

@@ -540,14 +540,15 @@ __global__ __launch_bounds__(256) void restart_samples_kernel(const uint8_t* __r
 }
 
 // prompt + xattn_positions_embed[cumsum(prompt_mask) - 1]  (vima_policy.py:147, xattn_gpt.py:110-114) -> T [B, Lp, E]
+// With a sample list (batched vima_decode_restart) output block blockIdx.x is computed from sample list[blockIdx.x] of prompt / mask.
 template <typename T>
 __global__ __launch_bounds__(256) void prompt_pos_kernel(const float* __restrict__ prompt, long long sb, long long sl,
                                                           const uint8_t* __restrict__ mask,
                                                           const float* __restrict__ pos_table, int n_pos, T* out, int B,
-                                                          int Lp, int E, int slab) {
+                                                          int Lp, int E, int slab, const int* __restrict__ list) {
   extern __shared__ int pos_dyn[];
   __shared__ int part[256];
-  const int b = blockIdx.x;
+  const int b = list ? list[blockIdx.x] : blockIdx.x;   // source sample
   // cumsum(mask) - 1 over the Lp positions of sample b: each thread owns a contiguous run, block-wide exclusive scan of
   // the run totals (Hillis-Steele in LDS), then the local prefix -- no serial chain of dependent global loads
   const int per = (Lp + 255) / 256;
@@ -585,7 +586,7 @@ __global__ __launch_bounds__(256) void prompt_pos_kernel(const float* __restrict
     const int l = i / e4, c = (i % e4) * 4;
     const float4 a = *reinterpret_cast<const float4*>(prompt + b * sb + l * sl + c);
     const float4 p = *reinterpret_cast<const float4*>(pos_table + (long long)pos_dyn[l] * E + c);
-    store4(out + ((long long)b * Lp + l) * E + c, make_float4(a.x + p.x, a.y + p.y, a.z + p.z, a.w + p.w));
+    store4(out + ((long long)blockIdx.x * Lp + l) * E + c, make_float4(a.x + p.x, a.y + p.y, a.z + p.z, a.w + p.w));
   }
 }
 
@@ -836,6 +837,32 @@ int launch_rows_to_headmajor(const void* in, void* out, int L, int N, int D, boo
   return (int)hipGetLastError();
 }
 
+// K | V rows of n listed samples, in [n * L][N] (row-major, sample r = rows r L ..), to each sample's block of the prompt K / V cache (batched
+// vima_decode_restart): block list[r] of `out` (L * N elements per sample), row-major [L][N] (hm = 0) or head-major [N / D][L][D]; 16-byte chunks
+template <typename T>
+__global__ __launch_bounds__(256) void kv_scatter_kernel(const T* __restrict__ in, T* __restrict__ out, const int* __restrict__ list, int L, int N,
+                                                          int D, int hm) {
+  constexpr int EPC = 16 / (int)sizeof(T);
+  const int r = blockIdx.y;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int cpr = N / EPC;
+  if (i >= (long long)L * cpr) return;
+  const int l = (int)(i / cpr), n = (int)(i % cpr) * EPC;
+  const uint4 v = *reinterpret_cast<const uint4*>(in + ((long long)r * L + l) * N + n);
+  T* dst = out + (long long)list[r] * L * N;
+  *reinterpret_cast<uint4*>(dst + (hm ? ((long long)(n / D) * L + l) * D + n % D : (long long)l * N + n)) = v;
+}
+
+int launch_kv_scatter(const void* in, void* out, const int* list, int n, int L, int N, int D, int hm, bool is_bf16, hipStream_t st) {
+  const int epc = is_bf16 ? 8 : 4;
+  if (n <= 0 || L <= 0 || N <= 0) return 0;
+  if (N % epc || (hm && (D % epc || N % D)) || n > 65535) return (int)hipErrorInvalidValue;
+  const dim3 grid(nblk((long long)L * (N / epc), 256), (unsigned)n);
+  if (is_bf16) hipLaunchKernelGGL(kv_scatter_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)in, (bf16_t*)out, list, L, N, D, hm);
+  else hipLaunchKernelGGL(kv_scatter_kernel<float>, grid, dim3(256), 0, st, (const float*)in, (float*)out, list, L, N, D, hm);
+  return (int)hipGetLastError();
+}
+
 int launch_prompt_assemble_stats(const int* tok_src, const long long* word_ids, const float* word_table, const float* obj_tokens,
                                  const uint8_t* obj_mask, void* xT, float* ssq, uint8_t* mask, int rows, int E, bool is_bf16, hipStream_t st) {
   if (rows <= 0) return 0;
@@ -884,17 +911,17 @@ int launch_restart_samples(const uint8_t* flags, uint8_t* hist_mask, int* poscnt
 }
 
 int launch_prompt_pos(const float* prompt, long long sb, long long sl, const uint8_t* mask, const float* pos_table,
-                      int n_pos, void* outT, int B, int Lp, int E, bool is_bf16, hipStream_t st) {
+                      int n_pos, void* outT, int B, int Lp, int E, bool is_bf16, hipStream_t st, const int* list) {
   if (B <= 0 || Lp <= 0) return 0;
   if (E % 4 || sb % 4 || sl % 4) return (int)hipErrorInvalidValue;
   const size_t sh = (size_t)Lp * sizeof(int);
   const int slab = (long long)B * ((Lp + 63) / 64) >= 512 ? 64 : 8;
   if (is_bf16)
     hipLaunchKernelGGL(prompt_pos_kernel<bf16_t>, dim3(B, (Lp + slab - 1) / slab), dim3(256), sh, st, prompt, sb, sl, mask, pos_table, n_pos,
-                       (bf16_t*)outT, B, Lp, E, slab);
+                       (bf16_t*)outT, B, Lp, E, slab, list);
   else
     hipLaunchKernelGGL(prompt_pos_kernel<float>, dim3(B, (Lp + slab - 1) / slab), dim3(256), sh, st, prompt, sb, sl, mask, pos_table, n_pos,
-                       (float*)outT, B, Lp, E, slab);
+                       (float*)outT, B, Lp, E, slab, list);
   return (int)hipGetLastError();
 }
 

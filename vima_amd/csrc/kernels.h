@@ -226,8 +226,12 @@ int launch_dec_embed_step(const float* obs_tok, const uint8_t* obs_mask, const f
 // next action slot absent (fresh[b] = 1, consumed by launch_dec_embed_step)
 int launch_restart_samples(const uint8_t* flags, uint8_t* hist_mask, int* poscnt, uint8_t* fresh, int B, int Lmax, hipStream_t st);
 // prompt + xattn_positions_embed[cumsum(mask)-1] -> T [B*Lp, E]; input strides in elements (seq-first views ok)
+// list (DEVICE array [B], optional): output block r is computed from sample list[r] of prompt / mask instead of sample r
 int launch_prompt_pos(const float* prompt, long long sb, long long sl, const uint8_t* mask, const float* pos_table,
-                      int n_pos, void* outT, int B, int Lp, int E, bool is_bf16, hipStream_t st);
+                      int n_pos, void* outT, int B, int Lp, int E, bool is_bf16, hipStream_t st, const int* list = nullptr);
+// rows [n * L][N] of the operand type (sample r = rows r * L ..) -> block list[r] (DEVICE array [n]) of a cache of L * N elements per sample:
+// row-major [L][N] (hm = 0) or head-major [N / D][L][D] (the prompt K / V cache's two layouts)
+int launch_kv_scatter(const void* in, void* out, const int* list, int n, int L, int N, int D, int hm, bool is_bf16, hipStream_t st);
 // out[t,b,:] = x[b, (Q-1) + (Q+1) t, :]
 int launch_gather_pred(const float* x, float* out, int T, int B, int Q, int Lq, int E, hipStream_t st);
 
@@ -276,6 +280,9 @@ struct AttnArgs {
   // rule compares key j with the query's GLOBAL position i + q_off.
   int Lk_rows = 0;
   int q_off = 0;
+  // RING episode cache (option decode_ring): the step's rows are [q_off, q_off + Lq) = [q_off, win_end) of a ring image of Lk rows and key j is
+  // "future" for query i iff i + q_off < j < win_end -- rows from win_end on hold OLDER history of the episode. 0 = Lk: the plain causal rule.
+  int win_end = 0;
   const Tuning* tune = nullptr;   // the calling handle's knobs (nullptr: process defaults)
 };
 // generic exact kernel (any T); the MFMA flash kernel (bf16, D in {32,64})

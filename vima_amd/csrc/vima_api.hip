@@ -228,6 +228,14 @@ struct VimaHandle {
   uint8_t* ep_mask = nullptr; int* ep_poscnt = nullptr; size_t ep_aux_cap = 0;
   uint8_t* ep_fresh = nullptr;   // [B] 1 = the sample was restarted (vima_decode_restart): its next step has no previous action
   int ep_B = 0, ep_Q = 0, ep_Lmax = 0, ep_Lp = 0, ep_step = -1;
+  // option "decode_ring": the ONE row index space of the episode caches is a ring. Host bookkeeping (decode_prepare plans, decode_commit stores):
+  // ring_wp = next row to write, ring_hw = one past the highest row written since step 0 (rows beyond it hold hipMalloc garbage and are never
+  // read), ring_age[b] = ring rows advanced (skipped tail rows included) since sample b's episode began
+  int decode_ring = 0;
+  int ring_wp = 0, ring_hw = 0;
+  std::vector<int> ring_age;
+  int restart_batched = 1;                       // option "restart_batched": vima_decode_restart rebuilds the flagged samples' prompt K / V together (0: one sample at a time)
+  std::vector<int> restart_list;                 // host copy of the flagged sample indices (source of the upload)
   // hipGraph replay of the per-env-step entry points (option "graphs"): at small batch a step is ~1300 launches of
   // microsecond kernels and the HOST launch rate is the bound. The launch sequence of a call is captured the second time
   // the same (entry point, shapes, pointers, options, workspace generation) is seen and replayed afterwards.
@@ -1487,8 +1495,11 @@ std::string gkey(const char* name, std::initializer_list<long long> vals) {
 // be the legacy NULL stream, which cannot be captured). A key is captured the second time it is seen: the first, eager,
 // run sizes the workspace, creates events and sets the kernels' function attributes. Anything that fails during a
 // capture (e.g. the workspace had to grow) makes that key permanently eager.
+// warm (optional): the key under which that first eager run is counted, for families of calls whose launch sequences differ only in values baked
+// into the kernel arguments (ring mode of vima_decode_step: write pointer and keys read) -- one eager run warms the whole family and every member is
+// captured the first time it is seen.
 template <typename F>
-int run_graphed(VimaHandle* h, std::string key, hipStream_t user, F&& fn) {
+int run_graphed(VimaHandle* h, std::string key, hipStream_t user, F&& fn, std::string warm = std::string()) {
   if (!h->graph_mode || h->prof) return fn(user);
   HIPCK(hipSetDevice(h->device));
   if (!h->gstream) {
@@ -1498,7 +1509,8 @@ int run_graphed(VimaHandle* h, std::string key, hipStream_t user, F&& fn) {
   }
   HIPCK(hipEventRecord(h->ev_gin, user));
   HIPCK(hipStreamWaitEvent(h->gstream, h->ev_gin, 0));
-  key += gkey("", {(long long)h->state_gen, (long long)h->arena.gen, h->bf16 ? 1 : 0});
+  const std::string gen = gkey("", {(long long)h->state_gen, (long long)h->arena.gen, h->bf16 ? 1 : 0});
+  key += gen;
   int rc = 0;
   auto it = h->graphs.find(key);
   if (it != h->graphs.end()) {
@@ -1506,13 +1518,14 @@ int run_graphed(VimaHandle* h, std::string key, hipStream_t user, F&& fn) {
     ++h->graph_replays;
     if (hipGraphLaunch(it->second.exec, h->gstream) != hipSuccess) rc = fail("hipGraphLaunch failed");
   } else {
-    int& seen = h->graph_seen[key];
-    if (seen < 1) {
+    int& seen = h->graph_seen[warm.empty() ? key : warm + gen];
+    int& dead = h->graph_seen[key];   // -1: this key stays eager (the same entry as `seen` without a warm key)
+    if (seen < 1 || dead < 0) {
       if (seen == 0) seen = 1;
       rc = fn(h->gstream);
     } else if (hipStreamBeginCapture(h->gstream, hipStreamCaptureModeRelaxed) != hipSuccess) {
       (void)hipGetLastError();
-      seen = -1;
+      dead = -1;
       rc = fn(h->gstream);
     } else {
       const uint64_t gen0 = h->arena.gen;
@@ -1534,7 +1547,7 @@ int run_graphed(VimaHandle* h, std::string key, hipStream_t user, F&& fn) {
         if (hipGraphLaunch(exec, h->gstream) != hipSuccess) rc = fail("hipGraphLaunch failed");
       } else {
         (void)hipGetLastError();
-        seen = -1;
+        dead = -1;
         rc = e ? e : fn(h->gstream);   // nothing ran during the failed capture
       }
       if (g) (void)hipGraphDestroy(g);
@@ -1784,6 +1797,8 @@ int vima_set_option(VimaHandle* h, const char* key, int64_t value) {
   else if (k == "geglu_pair") h->geglu_pair = (int)value;
   else if (k == "ln_fuse") h->ln_fuse = (int)value;
   else if (k == "kv_headmajor") { h->kv_headmajor = (int)value; h->kv_valid = false; h->ep_step = -1; }   // the next decode rebuilds the cache in the chosen layout; a running episode (vima_decode_step) ends: start a new one with step 0
+  else if (k == "decode_ring") { h->decode_ring = value != 0; h->ep_step = -1; }   // a running episode (vima_decode_step) ends: start a new one with step 0
+  else if (k == "restart_batched") h->restart_batched = (int)value;
   else if (k == "t5_fuse_rms") h->t5_fuse_rms = (int)value;
   else if (k == "stream_T") h->stream_T = (int)value;
   else if (k == "fp8_headroom_pct") { h->fp8_headroom_pct = value < 100 ? 100 : (int)value; h->fp8_ready = false; h->vit8_ready = false; h->kv8_ready = false; }
@@ -1979,7 +1994,14 @@ int vima_prompt_encode(VimaHandle* h, const int64_t* word_ids, int n_words, cons
 // tokens of env step `step` are processed against the episode's cached self-attention K/V) share three stages:
 // decode_prepare (validation, cache (re)allocation, state invalidation -- host only), decode_launch (the pure launch
 // sequence: eager, captured or replayed) and decode_commit (host state after a successful launch).
-struct DecodePlan { bool inc; int has_act, L_hist, Lq, Lmax, kv_mode; };
+// row: first episode-cache row this call writes (= the history length L_hist, or the ring's write pointer); Lk / win_end: keys the self-attention reads and
+// the end of its causal window (AttnArgs); ring / advance / wp / hw: the ring bookkeeping decode_commit stores
+struct DecodePlan { bool inc; int has_act, row, Lq, Lmax, kv_mode, Lk, win_end; bool ring; int advance, wp, hw; };
+
+// One step of the ring's bookkeeping: Lq rows at write pointer wp of a ring of Lmax rows. A step's rows are never split across the wrap: when they do not
+// fit, the tail [wp, Lmax) is skipped (and counts as advanced) and the rows go to [0, Lq).
+struct RingStep { int row, advance; };
+static RingStep ring_next(int wp, int Lq, int Lmax) { return wp + Lq > Lmax ? RingStep{0, Lmax - wp + Lq} : RingStep{wp, Lq}; }
 
 static int decode_prepare(VimaHandle* h, const float* act_tok, int T, int B, int Q, int L_act, int Lp, int kv_cache_mode, int step,
                           DecodePlan& P) {
@@ -1996,7 +2018,8 @@ static int decode_prepare(VimaHandle* h, const float* act_tok, int T, int B, int
   const int L_hist = inc && step > 0 ? step * (Q + 1) - 1 : 0;     // tokens already in the episode cache
   const int Lq = inc ? Q + has_act : T * Q + L_act;                // tokens processed by this call, per sample
   const int Lmax = h->cfg.n_positions;
-  if (L_hist + Lq > h->cfg.n_positions) return fail("vima_decode: history longer than n_positions", 34);
+  const bool ring = inc && h->decode_ring != 0;
+  if (ring ? Lq > Lmax : L_hist + Lq > h->cfg.n_positions) return fail("vima_decode: history longer than n_positions", 34);
   if (Lp > h->cfg.xattn_n_positions)   // xattn_gpt.py:110 assert
     return fail("AssertionError: prompt_tokens.size(1) <= xattn_n_positions (" + std::to_string(Lp) + " > " +
                 std::to_string(h->cfg.xattn_n_positions) + ")", 33);
@@ -2005,6 +2028,13 @@ static int decode_prepare(VimaHandle* h, const float* act_tok, int T, int B, int
     if (step > 0 && !(h->ep_step == step - 1 && h->ep_B == B && h->ep_Q == Q && h->ep_Lp == Lp && h->kv_valid))
       return fail("vima_decode_step: step " + std::to_string(step) + " does not continue the episode state (last step " +
                   std::to_string(h->ep_step) + "); start an episode with step 0");
+    if (ring && step > 0) {   // legal iff every row about to be overwritten or skipped is dead for every sample
+      const RingStep rs = ring_next(h->ring_wp, Lq, Lmax);
+      for (int b = 0; b < B; ++b)
+        if (h->ring_age[b] + rs.advance > Lmax)
+          return fail("vima_decode_step: the episode of sample " + std::to_string(b) + " is longer than n_positions (" + std::to_string(h->ring_age[b]) + " + " +
+                      std::to_string(rs.advance) + " ring rows > " + std::to_string(Lmax) + "): restart it with vima_decode_restart", 34);
+    }
     kv_cache_mode = step == 0 ? 1 : 2;
     if (step == 0) {
       const size_t need = (size_t)h->cfg.xf_n_layers * B * Lmax * 2 * E * h->esz();
@@ -2041,13 +2071,24 @@ static int decode_prepare(VimaHandle* h, const float* act_tok, int T, int B, int
     }
   }
   if (!inc) h->ep_step = -1;   // a full-history call may rebuild the prompt cache: the episode state no longer matches
-  P = DecodePlan{inc, has_act, L_hist, Lq, Lmax, kv_cache_mode};
+  P = DecodePlan{inc, has_act, L_hist, Lq, Lmax, kv_cache_mode, L_hist + Lq, 0, ring, 0, 0, 0};
+  if (ring) {
+    const RingStep rs = step > 0 ? ring_next(h->ring_wp, Lq, Lmax) : RingStep{0, Lq};
+    P.row = rs.row; P.advance = rs.advance; P.wp = rs.row + Lq;
+    P.hw = step > 0 && h->ring_hw > P.wp ? h->ring_hw : P.wp;
+    P.Lk = P.hw; P.win_end = P.wp;
+  }
   return 0;
 }
 
 static void decode_commit(VimaHandle* h, const DecodePlan& P, int B, int Q, int Lp, int step) {
   if (P.kv_mode == 1) { h->kv_valid = true; h->kv_B = B; h->kv_Lp = Lp; }
   if (P.inc) { h->ep_step = step; h->ep_B = B; h->ep_Q = Q; h->ep_Lp = Lp; h->ep_Lmax = P.Lmax; }
+  if (P.ring) {
+    if (step == 0) h->ring_age.assign((size_t)B, 0);
+    for (int& a : h->ring_age) a += P.advance;
+    h->ring_wp = P.wp; h->ring_hw = P.hw;
+  }
 }
 
 static int decode_launch(VimaHandle* h, const float* obs_tok, const uint8_t* obs_mask, const float* act_tok, int T, int B, int Q,
@@ -2056,8 +2097,8 @@ static int decode_launch(VimaHandle* h, const float* obs_tok, const uint8_t* obs
   if (int e = check_ready(h)) return e;
   const int E = h->cfg.embed_dim;
   const bool inc = P.inc;
-  const int has_act = P.has_act, L_hist = P.L_hist, Lq = P.Lq, Lmax = P.Lmax, kv_cache_mode = P.kv_mode;
-  if (inc && L_hist == 0) {
+  const int has_act = P.has_act, L_hist = P.row, Lq = P.Lq, Lmax = P.Lmax, kv_cache_mode = P.kv_mode;
+  if (inc && !has_act) {   // step 0
     HIPCK(hipMemsetAsync(h->ep_poscnt, 0, (size_t)B * sizeof(int), stream));
     HIPCK(hipMemsetAsync(h->ep_fresh, 0, (size_t)B, stream));
   }
@@ -2215,7 +2256,8 @@ static int decode_launch(VimaHandle* h, const float* obs_tok, const uint8_t* obs
     s.scale = 1.0f / sqrtf((float)(E / Hs)); s.mode = ATTN_CAUSAL;
     if (inc) {
       // q of the new tokens; their k / v rows are APPENDED to the layer's episode cache by the GEMM's row-remap epilogue
-      // (row b*Lq + i -> b*Lmax + L_hist + i); the new queries attend to history + themselves with a causal offset
+      // (row b*Lq + i -> b*Lmax + L_hist + i); the new queries attend to history + themselves with a causal offset. Ring mode: L_hist is the ring's
+      // write pointer, the keys are the whole written image [0, hw) and only the step's own rows [L_hist, L_hist + Lq) are causal (AttnArgs::win_end)
       void* cache = reinterpret_cast<char*>(h->ep_kv) + (size_t)i * B * Lmax * 2 * E * h->esz();
       if (h->bf16 && !D.c_attn.ws && E % 128 == 0 && !gemm_splitk_enabled(&h->tune)) {   // one launch: q columns dense, k | v columns appended to the cache
         GemmArgs gq;
@@ -2235,7 +2277,7 @@ static int decode_launch(VimaHandle* h, const float* obs_tok, const uint8_t* obs
       R.gemm(gk);
       }
       s.q = qkv; s.ldq = E; s.k = cache; s.ldk = 2 * E; s.v = R.offT(cache, E); s.ldv = 2 * E;
-      s.kmask = h->ep_mask; s.Lk = L_hist + Lq; s.Lk_rows = Lmax; s.q_off = L_hist;
+      s.kmask = h->ep_mask; s.Lk = P.Lk; s.Lk_rows = Lmax; s.q_off = L_hist; s.win_end = P.win_end;
     } else {
       R.linear(xT, E, D.c_attn, rq, ACT_NONE, nullptr, 0, nullptr, 0, nullptr, 0, qkv, 3 * E);
       s.q = qkv; s.ldq = 3 * E; s.k = R.offT(qkv, E); s.ldk = 3 * E; s.v = R.offT(qkv, 2 * E); s.ldv = 3 * E;
@@ -2281,12 +2323,18 @@ int vima_decode_step(VimaHandle* h, const float* obs_tok, const uint8_t* obs_mas
   if (step < 0) return fail("vima_decode_step: step must be >= 0");
   DecodePlan P;
   if (int e = decode_prepare(h, act_tok, 1, B, Q, 0, Lp, 0, step, P)) return e;
-  const std::string key = gkey("decode_step", {(long long)(uintptr_t)obs_tok, (long long)(uintptr_t)obs_mask, (long long)(uintptr_t)act_tok, step,
+  // ring mode: the launch sequence depends on (write pointer, keys read, action slot), not on the step number -- from the second lap on the write
+  // pointers repeat, so the set of captured graphs stays bounded however long the rollout runs
+  const long long kstep = P.ring ? -1 - (((long long)P.row * (P.Lmax + 1) + P.Lk) * 2 + P.has_act) : step;
+  const std::string key = gkey("decode_step", {(long long)(uintptr_t)obs_tok, (long long)(uintptr_t)obs_mask, (long long)(uintptr_t)act_tok, kstep,
                                                B, Q, (long long)(uintptr_t)prompt, stride_b, stride_l, (long long)(uintptr_t)prompt_mask,
                                                Lp, (long long)(uintptr_t)out, (long long)(uintptr_t)h->kv_cache, (long long)(uintptr_t)h->ep_kv});
+  // ... and one eager step with an action slot warms all of them (same shapes, same workspace, same kernels: the attention launcher picks by Lk < 64 / >= 64):
+  // each (write pointer, keys read) is captured when first seen
+  const std::string warm = P.ring && P.has_act ? gkey("decode_step_ring", {B, Q, Lp, P.Lk >= 64 ? 1 : 0}) : std::string();
   const int rc = run_graphed(h, key, (hipStream_t)stream, [&](hipStream_t st) {
     return decode_launch(h, obs_tok, obs_mask, act_tok, 1, B, Q, 0, prompt, stride_b, stride_l, prompt_mask, Lp, P, out, st);
-  });
+  }, warm);
   if (!rc) decode_commit(h, P, B, Q, Lp, step);
   return rc;
 }
@@ -2296,7 +2344,13 @@ int vima_decode_step(VimaHandle* h, const float* obs_tok, const uint8_t* obs_mas
 // cached history is masked out (the caches keep ONE row index space for the batch: the next step's tokens of all samples still land
 // at the same cache rows), its position counter restarts at 0, its next step carries no previous action, and its rows of the per-layer
 // prompt K/V cache are rebuilt from its row of `prompt` (the NEW prompts; rows of the other samples are not read). The batch keeps
-// stepping with vima_decode_step(step + 1, ...); n_positions bounds the number of steps since the last step 0 of the whole batch.
+// stepping with vima_decode_step(step + 1, ...); n_positions bounds the number of steps since the last step 0 of the whole batch -- unless the
+// row index space is a ring (option decode_ring), where a restart gives the sample's rows back (ring_age[b] = 0).
+// The prompt K / V rows of ALL flagged samples are rebuilt together (option restart_batched, prompts longer than 32 tokens): one gather of their
+// prompts + positions into [n_r * Lp, E], per layer one GEMM of n_r * Lp rows and one scatter into the cache (either layout) -- 1 + 2 NL launches
+// whatever n_r is, against n_r (1 + NL .. 2 NL) for the per-sample loop. The tile GEMM kernels agree bit for bit at every row count (option
+// gemm_skinny in the header), so the cache holds the loop's bits; at Lp <= 32 the loop's GEMMs run on gemm_skinny_kernel, whose summation order
+// differs, and the loop is kept. In precision fp8 this GEMM takes bf16 activations whatever its size (header, VIMA_PRECISION_FP8 (iv)).
 int vima_decode_restart(VimaHandle* h, const uint8_t* restart, int B, const float* prompt, int64_t stride_b, int64_t stride_l,
                         const uint8_t* prompt_mask, int Lp, vima_stream_t stream) {
   if (int e = check_ready(h)) return e;
@@ -2305,14 +2359,31 @@ int vima_decode_restart(VimaHandle* h, const uint8_t* restart, int B, const floa
     return fail("vima_decode_restart: no running episode batch with this B / Lp (start one with vima_decode_step(step = 0))");
   const int E = h->cfg.embed_dim, NL = h->cfg.xf_n_layers;
   Run R{h, (hipStream_t)stream};
+  h->restart_list.clear();
+  for (int b = 0; b < B; ++b)
+    if (restart[b]) h->restart_list.push_back(b);
+  const int n_r = (int)h->restart_list.size();
+  const bool batched = h->restart_batched != 0 && Lp > 32 && n_r > 0;
+  const int n_ws = batched ? n_r : 1;
   uint8_t* flags = R.ws<uint8_t>((size_t)B);
-  void* pT = R.wsT((size_t)Lp * E);
-  void* kvrow = h->kv_hm ? R.wsT((size_t)Lp * 2 * E) : nullptr;   // row-major K | V of one sample before the head-major transposition
+  int* list = batched ? R.ws<int>((size_t)n_r) : nullptr;
+  void* pT = R.wsT((size_t)n_ws * Lp * E);
+  void* kvrow = (h->kv_hm || batched) ? R.wsT((size_t)n_ws * Lp * 2 * E) : nullptr;   // row-major K | V before the scatter / the head-major transposition
   if (R.err) return R.err;
   HIPCK(hipMemcpyAsync(flags, restart, (size_t)B, hipMemcpyHostToDevice, R.st));
   OTHER(R, launch_restart_samples(flags, h->ep_mask, h->ep_poscnt, h->ep_fresh, B, h->ep_Lmax, R.st), "restart_samples");
   const size_t kv_layer_bytes = (size_t)B * Lp * 2 * E * h->esz();
-  for (int b = 0; b < B && !R.err; ++b) {
+  if (batched) {
+    HIPCK(hipMemcpyAsync(list, h->restart_list.data(), (size_t)n_r * sizeof(int), hipMemcpyHostToDevice, R.st));
+    OTHER(R, launch_prompt_pos(prompt, stride_b, stride_l, prompt_mask, h->xpos_emb, h->cfg.xattn_n_positions, pT, n_r, Lp, E, h->bf16, R.st, list),
+          "prompt_pos");
+    for (int i = 0; i < NL && !R.err; ++i) {
+      R.linear(pT, E, h->dec[i].kv, n_r * Lp, ACT_NONE, nullptr, 0, nullptr, 0, nullptr, 0, kvrow, 2 * E);
+      OTHER(R, launch_kv_scatter(kvrow, reinterpret_cast<char*>(h->kv_cache) + kv_layer_bytes * i, list, n_r, Lp, 2 * E, E / h->cfg.xattn_n_heads,
+                                 h->kv_hm ? 1 : 0, h->bf16, R.st), "kv_scatter");
+    }
+  }
+  for (int b = 0; b < B && !R.err && !batched; ++b) {
     if (!restart[b]) continue;
     OTHER(R, launch_prompt_pos(prompt + (long long)b * stride_b, stride_b, stride_l, prompt_mask + (long long)b * Lp, h->xpos_emb,
                                h->cfg.xattn_n_positions, pT, 1, Lp, E, h->bf16, R.st), "prompt_pos");
@@ -2326,7 +2397,31 @@ int vima_decode_restart(VimaHandle* h, const uint8_t* restart, int B, const floa
       }
     }
   }
+  if (!R.err && h->decode_ring && (int)h->ring_age.size() == B)
+    for (int b : h->restart_list) h->ring_age[b] = 0;   // the sample's rows are dead: the ring may overwrite them
   return R.err;
+}
+
+// Host-only: how many further vima_decode_step calls would succeed if sample b alone were never restarted (the bookkeeping of decode_prepare run forward).
+int vima_decode_steps_left(VimaHandle* h, int B, int32_t* out_host) {
+  if (!h || !out_host) return fail("vima_decode_steps_left: null argument");
+  if (!(h->ep_step >= 0 && h->ep_B == B)) return fail("vima_decode_steps_left: no running episode batch of this size (start one with vima_decode_step(step = 0))");
+  const int Lq = h->ep_Q + 1, Lmax = h->ep_Lmax;
+  if (!h->decode_ring) {   // step s needs (s + 1) (Q + 1) - 1 <= n_positions rows since the batch's step 0
+    const int last = (Lmax + 1) / Lq - 1;
+    for (int b = 0; b < B; ++b) out_host[b] = last > h->ep_step ? last - h->ep_step : 0;
+    return 0;
+  }
+  for (int b = 0; b < B; ++b) {
+    int n = 0, wp = h->ring_wp, age = h->ring_age[b];
+    for (;;) {
+      const RingStep rs = ring_next(wp, Lq, Lmax);
+      if (age + rs.advance > Lmax) break;
+      age += rs.advance; wp = rs.row + Lq; ++n;
+    }
+    out_host[b] = n;
+  }
+  return 0;
 }
 
 // ---- baseline policies --------------------------------------------------------------------------
@@ -2568,8 +2663,8 @@ int vima_op_layernorm(VimaHandle* h, const float* x, const float* gamma, const f
   return R.ln(x, E, gamma, beta, eps, rms, rows, E, out, nullptr);
 }
 
-int vima_op_attention(VimaHandle* h, const float* q, const float* k, const float* v, const uint8_t* kmask, const float* relbias,
-                      int B, int H, int Lq, int Lk, int D, float scale, int mode, int impl, float* out, vima_stream_t stream) {
+static int op_attention(VimaHandle* h, const float* q, const float* k, const float* v, const uint8_t* kmask, const float* relbias,
+                        int B, int H, int Lq, int Lk, int D, float scale, int mode, int impl, int q_off, int win_end, float* out, vima_stream_t stream) {
   if (!h) return fail("null handle");
   HIPCK(hipSetDevice(h->device));
   if (h->arena.reset()) return fail("workspace reset failed");
@@ -2583,6 +2678,7 @@ int vima_op_attention(VimaHandle* h, const float* q, const float* k, const float
   AttnArgs a;
   a.q = qT; a.ldq = H * D; a.k = kT; a.ldk = H * D; a.v = vT; a.ldv = H * D; a.out = oT; a.ldo = H * D;
   a.kmask = kmask; a.relbias = relbias; a.bias_far = h->op_bias_far; a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.D = D; a.scale = scale; a.mode = mode;
+  a.q_off = q_off; a.win_end = win_end;
   if (impl == 1 && !h->bf16 && !h->x3) return fail("vima_op_attention: the MFMA kernel needs bf16 or bf16x3 precision");
   if (R.attn(a, impl)) return R.err;
   if (h->bf16) {
@@ -2591,6 +2687,17 @@ int vima_op_attention(VimaHandle* h, const float* q, const float* k, const float
   }
   HIPCK(hipMemcpyAsync(out, oT, nq * 4, hipMemcpyDeviceToDevice, R.st));
   return 0;
+}
+
+int vima_op_attention(VimaHandle* h, const float* q, const float* k, const float* v, const uint8_t* kmask, const float* relbias,
+                      int B, int H, int Lq, int Lk, int D, float scale, int mode, int impl, float* out, vima_stream_t stream) {
+  return op_attention(h, q, k, v, kmask, relbias, B, H, Lq, Lk, D, scale, mode, impl, 0, 0, out, stream);
+}
+
+int vima_op_attention_window(VimaHandle* h, const float* q, const float* k, const float* v, const uint8_t* kmask, int B, int H, int Lq, int Lk,
+                             int D, float scale, int impl, int q_off, float* out, vima_stream_t stream) {
+  if (q_off < 0 || Lq <= 0 || q_off + Lq > Lk) return fail("vima_op_attention_window: the window [q_off, q_off + Lq) must lie inside the Lk keys");
+  return op_attention(h, q, k, v, kmask, nullptr, B, H, Lq, Lk, D, scale, ATTN_CAUSAL, impl, q_off, q_off + Lq, out, stream);
 }
 
 }  // extern "C"

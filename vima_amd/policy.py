@@ -417,7 +417,19 @@ class VIMAPolicy(nn.Module):
         _lib.check(self._lib.vima_decode_step(
             self._handle, _ptr(obs_token), _ptr(obs_mask), _ptr(prev_action_token), int(step), B, Q, _ptr(prompt_token),
             prompt_token.stride(1), prompt_token.stride(0), _ptr(prompt_token_mask), Lp, _ptr(out), self._stream()))
+        self._ep_B = B
         return out
+
+    def steps_left(self) -> torch.Tensor:
+        """torch.IntTensor[B] on the CPU: for every sample of the batch that is stepping with `forward_step`, how many further
+        `forward_step` calls would succeed if that sample alone were never restarted (host bookkeeping only: no device work, no
+        synchronisation). With `set_option("decode_ring", 1)` a rollout restarts (`restart_samples`) every sample whose entry reaches
+        0 and never resets the batch; without it all entries are equal: the steps left before the whole batch must start over."""
+        self._ready()
+        B = getattr(self, "_ep_B", 0)
+        out = torch.zeros(max(B, 1), dtype=torch.int32)
+        _lib.check(self._lib.vima_decode_steps_left(self._handle, B, ctypes.cast(out.data_ptr(), ctypes.POINTER(ctypes.c_int32))))
+        return out[:B]
 
     def restart_samples(self, restart, prompt_token: torch.Tensor, prompt_token_mask: torch.Tensor):
         """Per-sample episode restart inside a batch that is stepping with `forward_step` (batched environments finish their
