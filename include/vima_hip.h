@@ -180,7 +180,9 @@ int vima_decode_restart(VimaHandle* h, const uint8_t* restart, int B, const floa
 
 /* Host-only (additive, ABI version unchanged): out_host[b], b < B = how many further vima_decode_step calls of the running episode batch would
  * succeed if sample b ALONE were never restarted again (the row bookkeeping of vima_decode_step run forward; no device work, no state change).
- * Without option "decode_ring" the number is the same for every sample: the steps left before the whole batch must start over. */
+ * Without option "decode_ring" the number is the same for every sample: the steps left before the whole batch must start over.
+ * On a GPT / GATO handle the call reports the episode of vima_seq_prefill / vima_seq_decode_step: every entry is
+ * floor((n_positions - rows used) / (Q + 1)) (before step 0, which feeds Q rows only: floor((n_positions - rows used + 1) / (Q + 1))). */
 int vima_decode_steps_left(VimaHandle* h, int B, int32_t* out_host);
 
 /* VIMAPolicy.forward_action_decoder (vima_policy.py:264-265 -> action_decoder.py:51-52,165-166): tokens f32 [R,E]
@@ -244,6 +246,35 @@ int vima_rgb_prompt_encode(VimaHandle* h, const int64_t* word_ids, int n_words, 
  * (VIMAFlamingoPolicy.forward is vima_decode with an all-ones obs_mask.) */
 int vima_seq_decode(VimaHandle* h, const float* obs_tok, const float* act_tok, int T, int B, int L_act, const float* prompt,
                     int64_t stride_b, int64_t stride_l, const uint8_t* prompt_mask, int Lp, float* out, vima_stream_t stream);
+
+/* ---- incremental decoding of the decoder-only policies (additive, ABI version unchanged; VIMA_POLICY_GPT / VIMA_POLICY_GATO handles only,
+ * every other kind fails; not available with option "decode_ring") -------------------------------------------------------------------
+ * The rollout form of vima_seq_decode: the prompt is a sequence PREFIX that is consumed once, every env step then feeds only its own rows
+ * against a per-layer K | V cache [B][n_positions][2E] in the handle. HFGPT blocks are post-LN and act per row and the attention is causal,
+ * so the cached prefix is exact: step t returns row t of vima_seq_decode on the whole history (L_act = T - 1) up to summation order.
+ *
+ * vima_seq_prefill starts an episode batch: rows [0, Lp] ([prompt | prompt_sep_token], position ids min(l, nv - 1) / nv with nv = the
+ * sample's valid prompt tokens) go through the stack, every layer's K | V are left in rows [0, Lp] of the cache (copied from the call's
+ * dense q | k | v, which its attention reads), the key mask (prompt mask, 1 for the separator) and the per-sample position base nv + 1
+ * are stored. prompt / strides / mask as in vima_decode. Fails with code 34 when Lp + 1 > n_positions. */
+int vima_seq_prefill(VimaHandle* h, const float* prompt, int64_t stride_b, int64_t stride_l, const uint8_t* prompt_mask, int B, int Lp,
+                     vima_stream_t stream);
+/* One env step. step 0 follows vima_seq_prefill and feeds the Q observation tokens obs_tok f32 [B,Q,E] (act_tok ignored, may be NULL);
+ * step s > 0 feeds [a_{s-1}, o_s^1 .. o_s^Q] (act_tok f32 [B,E] required), Q + 1 rows at cache row Lp + 1 + s (Q + 1) - 1. Position ids
+ * continue the sample's counter, k | v of the new rows are appended to every layer's cache by the c_attn GEMM, the new queries attend to
+ * the cache with a causal offset. out f32 [B,E] = the last new row of every sample. Fails with code 34, changing nothing, when
+ * Lp + 1 + rows so far + rows of this call > n_positions (the bound of vima_seq_decode), and with code 1 when the call does not continue
+ * the episode state (no prefill, wrong B, wrong step number). With option "graphs" the call is captured and replayed (key: the pointers,
+ * B, the row offset, whether there is an action token), bit-identical to eager; no auxiliary stream is used. */
+int vima_seq_decode_step(VimaHandle* h, const float* obs_tok, const float* act_tok, int step, int B, float* out, vima_stream_t stream);
+/* Per-sample restart inside a running batch, the decoder-only form of vima_decode_restart: for every sample with restart[b] != 0 (HOST
+ * array [B]) the history rows [Lp + 1, current) are masked out, the position base is reset from ITS row of the new prompt, the next step's
+ * action slot becomes a masked row (zeros are embedded: that row of act_tok is never read) and rows [0, Lp] of every layer's cache are
+ * rebuilt. All flagged samples are rebuilt together: one prefill of n_flagged x (Lp + 1) rows and one scatter per layer by sample list,
+ * the same number of launches whatever n_flagged is. Lp must equal the episode's; rows of `prompt` of unflagged samples are not read. The
+ * batch keeps ONE row index space: a restart does not give rows back (vima_decode_steps_left). */
+int vima_seq_decode_restart(VimaHandle* h, const uint8_t* restart, int B, const float* prompt, int64_t stride_b, int64_t stride_l,
+                            const uint8_t* prompt_mask, int Lp, vima_stream_t stream);
 
 /* ---- image preprocessing in front of the policy ------------------------------------------- */
 /* The per-object work of prepare_obs / prepare_prompt (/root/reference/scripts/example.py:374-473 and :243-371; numpy +

@@ -73,6 +73,9 @@ PROTOTYPES = {
     "vima_rgb_prompt_encode": (ctypes.c_int, [vp, vp, ctypes.c_int, vp * 2, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp]),
     "vima_seq_decode": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, c_i64, c_i64, vp, ctypes.c_int,
                                        vp, vp]),
+    "vima_seq_prefill": (ctypes.c_int, [vp, vp, c_i64, c_i64, vp, ctypes.c_int, ctypes.c_int, vp]),
+    "vima_seq_decode_step": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]),
+    "vima_seq_decode_restart": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, c_i64, c_i64, vp, ctypes.c_int, vp]),
     "vima_action_head": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, vp]),
     "vima_action_embed": (ctypes.c_int, [vp, vp * 4, ctypes.c_int, vp, vp]),
     "vima_action_select": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.POINTER(c_f32), vp * 4, vp, vp, vp, vp]),

@@ -5,7 +5,8 @@
     VIMAFlamingoPolicy   vima/policy/vima_flamingo_policy.py  (Perceiver-resampled tokens + XAttnGPT)
 
 Same constructor arguments, method surface, return shapes and state_dict keys as the reference classes; the arithmetic runs
-in the HIP kernels (`vima_rgb_obs_encode`, `vima_rgb_prompt_encode`, `vima_seq_decode` / `vima_decode`, `vima_action_*`).
+in the HIP kernels (`vima_rgb_obs_encode`, `vima_rgb_prompt_encode`, `vima_seq_decode` / `vima_decode`, `vima_action_*`;
+rollouts: `vima_seq_prefill` / `vima_seq_decode_step` for gpt / gato, `vima_decode_step` for flamingo).
 No CPU fallback. Unlike VIMAPolicy these consume whole RGB frames `{"rgb": {view: u8 [..., 3, 64, 128]}}` and have no
 object masks (`forward` takes no `obs_mask`)."""
 from __future__ import annotations
@@ -150,13 +151,94 @@ class _BaselinePolicy(VIMAPolicy):
 
     def forward_step(self, obs_token, prev_action_token, prompt_token, prompt_token_mask, step: int):
         """Incremental decoding of one env step (see VIMAPolicy.forward_step). VIMAFlamingoPolicy decodes with XAttnGPT, so the
-        episode caches of `vima_decode_step` apply unchanged (every token valid); the decoder-only policies re-feed the history."""
+        episode caches of `vima_decode_step` apply unchanged (every token valid). The decoder-only policies step with
+        `seq_prefill` / `seq_step`: their prompt is a sequence prefix consumed once, not an operand passed every step."""
         if self.KIND != "flamingo":
-            raise NotImplementedError("incremental decoding needs the XAttnGPT episode caches: VIMAPolicy / VIMAFlamingoPolicy only")
+            raise NotImplementedError("forward_step needs the XAttnGPT episode caches (VIMAPolicy / VIMAFlamingoPolicy); the decoder-only "
+                                      "policies decode incrementally with seq_prefill / seq_step")
         if obs_token.dim() == 4:
             obs_token = obs_token[-1]
         ones = torch.ones(obs_token.shape[:2], dtype=torch.bool, device=self._device)
         return VIMAPolicy.forward_step(self, obs_token, ones, prev_action_token, prompt_token, prompt_token_mask, step)
+
+    # ------------------------------------------------------------------ incremental decoding (gpt / gato)
+    def _seq_only(self, what):
+        if self.KIND == "flamingo":
+            raise NotImplementedError(f"{what}: decoder-only policies (gpt / gato) only; VIMAFlamingoPolicy steps with forward_step")
+        self._ready()
+
+    def _seq_prompt(self, prompt_token, prompt_token_mask):
+        E = self.embed_dim
+        if prompt_token.dim() != 3 or prompt_token.shape[2] != E or prompt_token.dtype != torch.float32:
+            raise AssertionError(f"prompt_token must be float32 [Lp, B, {E}], got {prompt_token.dtype} {tuple(prompt_token.shape)}")
+        if tuple(prompt_token_mask.shape) != (prompt_token.shape[1], prompt_token.shape[0]):
+            raise AssertionError("prompt_token_mask shape does not match the prompt tokens")
+        if prompt_token.stride(-1) != 1:
+            prompt_token = prompt_token.contiguous()
+        return prompt_token.to(self._device), prompt_token_mask.to(device=self._device, dtype=torch.bool).contiguous()
+
+    def seq_prefill(self, prompt_token, prompt_token_mask):
+        """Start an episode batch of incremental decoding (no reference counterpart: its loop re-feeds the whole sequence to `forward`
+        every env step): prompt_token [Lp, B, E] + the separator run through the stack ONCE and every layer's K/V stay in the native
+        handle. Then call `seq_step` once per env step. A sample without any valid prompt token is refused like in `forward`."""
+        self._seq_only("seq_prefill")
+        prompt_token, prompt_token_mask = self._seq_prompt(prompt_token, prompt_token_mask)
+        if not bool(prompt_token_mask.any(dim=1).all()):
+            raise IndexError("index out of range in self (a sample has no valid prompt token: position id -1, vima_gato_policy.py:164)")
+        Lp, B = prompt_token.shape[0], prompt_token.shape[1]
+        _lib.check(self._lib.vima_seq_prefill(self._handle, _ptr(prompt_token), prompt_token.stride(1), prompt_token.stride(0),
+                                              _ptr(prompt_token_mask), B, Lp, self._stream()))
+        self._seq_t, self._ep_B = 0, B
+
+    def seq_step(self, obs_token, prev_action_token=None):
+        """One env step of the episode batch started by `seq_prefill`: obs_token [B, Q, E] ([B, E] or [B, 1, E] for GPT) and, from the
+        second step on, the embedded action of the previous step [B, E]. The step number is kept here. Returns the predicted action
+        token [B, E] == forward(<full history>)[step]. IndexError when the sequence would exceed n_positions, like `forward`."""
+        self._seq_only("seq_step")
+        Q, E = self._obj_xf_num_queries, self.embed_dim
+        if obs_token.dim() == 2:
+            obs_token = obs_token.unsqueeze(1)
+        if obs_token.dim() != 3 or obs_token.shape[1] != Q or obs_token.shape[2] != E or obs_token.dtype != torch.float32:
+            raise AssertionError(f"obs_token must be float32 [B, {Q}, {E}], got {obs_token.dtype} {tuple(obs_token.shape)}")
+        B = obs_token.shape[0]
+        step = getattr(self, "_seq_t", None)
+        if step is None:
+            raise _lib.VimaError("seq_step: no running episode (call seq_prefill first)")
+        obs_token = obs_token.to(device=self._device).contiguous()
+        if step > 0:
+            if prev_action_token is None:
+                raise AssertionError("seq_step: the previous action token is required from the second step on")
+            if prev_action_token.dim() == 3:
+                prev_action_token = prev_action_token[-1]
+            if tuple(prev_action_token.shape) != (B, E) or prev_action_token.dtype != torch.float32:
+                raise AssertionError(f"prev_action_token must be float32 [{B}, {E}], got {tuple(prev_action_token.shape)}")
+            prev_action_token = prev_action_token.to(device=self._device).contiguous()
+        else:
+            prev_action_token = None
+        out = torch.empty(B, E, dtype=torch.float32, device=self._device)
+        _lib.check(self._lib.vima_seq_decode_step(self._handle, _ptr(obs_token), _ptr(prev_action_token), step, B, _ptr(out), self._stream()))
+        self._seq_t = step + 1
+        return out
+
+    def seq_restart(self, restart, prompt_token, prompt_token_mask):
+        """Per-sample episode restart inside the stepping batch: every sample with `restart[b]` true forgets its history, takes its new
+        prompt from `prompt_token[:, b]` / `prompt_token_mask[b]` (same [Lp, B, E] / [B, Lp] layout and the same Lp as `seq_prefill`;
+        other samples' rows are not read) and its next `seq_step` ignores its row of `prev_action_token`. All flagged samples are
+        rebuilt in one batched prefill. The batch keeps stepping with `seq_step`; a restart does not give cache rows back
+        (`steps_left`): when they run out, start over with `seq_prefill`."""
+        self._seq_only("seq_restart")
+        prompt_token, prompt_token_mask = self._seq_prompt(prompt_token, prompt_token_mask)
+        flags = torch.as_tensor(restart).to(dtype=torch.uint8, device="cpu").contiguous()
+        Lp, B = prompt_token.shape[0], prompt_token.shape[1]
+        if flags.numel() != B:
+            raise AssertionError(f"restart must have one flag per sample ({B}), got {flags.numel()}")
+        if not bool(prompt_token_mask[flags.bool().to(self._device)].any(dim=1).all()):
+            raise IndexError("index out of range in self (a restarted sample has no valid prompt token: position id -1, vima_gato_policy.py:164)")
+        _lib.check(self._lib.vima_seq_decode_restart(self._handle, ctypes.c_void_p(flags.data_ptr()), B, _ptr(prompt_token),
+                                                     prompt_token.stride(1), prompt_token.stride(0), _ptr(prompt_token_mask), Lp, self._stream()))
+
+    # steps_left() is VIMAPolicy's: on a gpt / gato handle vima_decode_steps_left reports the episode of seq_prefill / seq_step (all entries
+    # equal: how many further seq_step calls fit into n_positions)
 
 
 class VIMAGPTPolicy(_BaselinePolicy):

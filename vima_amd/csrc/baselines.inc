@@ -152,7 +152,13 @@ int baseline_ready(VimaHandle* h, const char* fn) {
 
 // HFGPT.forward (gpt/gpt.py:45-80) on an assembled sequence: x32 / xT [B*L, E] (positions already added), key mask [B, L].
 // Post-LN blocks (gpt/gpt.py:231-246): a = attn(x); n = ln_1(x + a); h = ln_2(n + mlp(n)). Result in x32 (and xT).
-int hfgpt_stack(Run& R, float* x32, void* xT, const uint8_t* mask, int B, int L) {
+// kv_cache (vima_seq_prefill / vima_seq_decode_restart): every layer's k | v rows are also COPIED to rows [0, L) of the episode cache
+// [layer][kv_B][kv_Lmax][2E], block kv_list[r] (DEVICE array; nullptr: r) for the r-th sample of this call. A copy, not the c_attn GEMM's
+// row-remap epilogue: the attention of these rows reads the dense q | k | v of the call, so the remap would need the k | v columns twice (a
+// second GEMM launch per layer), while the copy is one HBM-bound pass over 2E columns, leaves the arithmetic of `vima_seq_decode` untouched
+// (same GEMM, same attention launch: the prefilled rows carry its bits) and serves the full prefill and the listed restart alike.
+int hfgpt_stack(Run& R, float* x32, void* xT, const uint8_t* mask, int B, int L, void* kv_cache = nullptr, const int* kv_list = nullptr,
+                int kv_B = 0, int kv_Lmax = 0) {
   VimaHandle* h = R.h;
   const int E = h->cfg.embed_dim, Hs = h->cfg.sattn_n_heads, rq = B * L;
   void* qkv = R.wsT((size_t)rq * 3 * E);
@@ -166,10 +172,64 @@ int hfgpt_stack(Run& R, float* x32, void* xT, const uint8_t* mask, int B, int L)
   for (int i = 0; i < h->cfg.xf_n_layers; ++i) {
     auto& D = h->dec[i];
     R.linear(xT, E, D.c_attn, rq, ACT_NONE, nullptr, 0, nullptr, 0, nullptr, 0, qkv, 3 * E);
+    if (kv_cache)
+      OTHER(R, launch_seq_kv_store(R.offT(qkv, E), 3 * E, R.offT(kv_cache, (long long)i * kv_B * kv_Lmax * 2 * E), kv_list, B, L, 2 * E, kv_Lmax,
+                                   h->bf16, R.st), "seq_kv_store");
     AttnArgs s;   // Attention._attn (gpt/gpt.py:268-301): /sqrt(d), w*b + -1e4*(1-b), + (1-mask)*finfo.min
     s.q = qkv; s.ldq = 3 * E; s.k = R.offT(qkv, E); s.ldk = 3 * E; s.v = R.offT(qkv, 2 * E); s.ldv = 3 * E;
     s.out = ctx; s.ldo = E; s.B = B; s.H = Hs; s.Lq = L; s.Lk = L; s.D = E / Hs; s.kmask = mask;
     s.scale = 1.0f / sqrtf((float)(E / Hs)); s.mode = ATTN_CAUSAL;
+    R.attn(s, h->attn_impl);
+    R.linear(ctx, E, D.c_proj, rq, ACT_NONE, nullptr, 0, x32, E, a32, E, nullptr, 0);   // x + a
+    R.ln(a32, E, D.ln1_g, D.ln1_b, 1e-5f, 0, rq, E, n32, nT);                           // n = ln_1(x + a)
+    R.linear(nT, E, D.mgate, rq, ACT_NONE, nullptr, 0, nullptr, 0, nullptr, 0, g, 4 * E);
+    R.linear(nT, E, D.fc, rq, ACT_GELU, g, 4 * E, nullptr, 0, nullptr, 0, u, 4 * E);     // gelu(c_fc(n)) * gated_layer(n)
+    R.linear(u, 4 * E, D.mproj, rq, ACT_NONE, nullptr, 0, n32, E, a32, E, nullptr, 0);  // n + m
+    R.ln(a32, E, D.ln2_g, D.ln2_b, 1e-5f, 0, rq, E, x32, xT);                           // h = ln_2(n + m)
+    if (R.err) return R.err;
+  }
+  return R.err;
+}
+
+// The same blocks for the rows of ONE env step against the episode cache (vima_seq_decode_step): x32 / xT [B * Lq, E] are the new rows at cache
+// rows [row, row + Lq) of every sample. c_attn appends their k | v to the layer's cache through the GEMM's row-remap epilogue (row b Lq + i ->
+// b Lmax + row + i; one launch with the q columns dense where decode_launch has that form, two otherwise) and the new queries attend to
+// [0, row + Lq) with the causal offset `row` and the cache's key mask. Everything after the attention acts per row, as in hfgpt_stack.
+int hfgpt_step_stack(Run& R, float* x32, void* xT, int B, int Lq, int row, int Lmax) {
+  VimaHandle* h = R.h;
+  const int E = h->cfg.embed_dim, Hs = h->cfg.sattn_n_heads, rq = B * Lq;
+  void* q = R.wsT((size_t)rq * E);
+  void* ctx = R.wsT((size_t)rq * E);
+  float* a32 = R.ws<float>((size_t)rq * E);
+  float* n32 = R.ws<float>((size_t)rq * E);
+  void* nT = R.wsT((size_t)rq * E);
+  void* g = R.wsT((size_t)rq * 4 * E);
+  void* u = R.wsT((size_t)rq * 4 * E);
+  if (R.err) return R.err;
+  for (int i = 0; i < h->cfg.xf_n_layers; ++i) {
+    auto& D = h->dec[i];
+    void* cache = R.offT(h->ep_kv, (long long)i * B * Lmax * 2 * E);
+    if (h->bf16 && !D.c_attn.ws && E % 128 == 0 && !gemm_splitk_enabled(&h->tune)) {
+      GemmArgs gq;
+      gq.A = xT; gq.lda = E; R.setW(gq, D.c_attn, 0); gq.M = rq; gq.N = 3 * E; gq.K = E; gq.bias = D.c_attn.b;
+      gq.outT_lo = q; gq.ldT_lo = E; gq.split_n = E;
+      gq.outT = cache; gq.ldT = 2 * E; gq.rb = Lq; gq.s_hi = Lmax; gq.s_lo = 1; gq.ro = row;
+      R.gemm(gq);
+    } else {
+      GemmArgs gq;
+      gq.A = xT; gq.lda = E; R.setW(gq, D.c_attn, 0); gq.M = rq; gq.N = E; gq.K = E; gq.bias = D.c_attn.b;
+      gq.outT = q; gq.ldT = E;
+      R.gemm(gq);
+      GemmArgs gk;
+      gk.A = xT; gk.lda = E; R.setW(gk, D.c_attn, E); gk.M = rq; gk.N = 2 * E; gk.K = E;
+      gk.bias = D.c_attn.b ? D.c_attn.b + E : nullptr;
+      gk.outT = cache; gk.ldT = 2 * E; gk.rb = Lq; gk.s_hi = Lmax; gk.s_lo = 1; gk.ro = row;
+      R.gemm(gk);
+    }
+    AttnArgs s;
+    s.q = q; s.ldq = E; s.k = cache; s.ldk = 2 * E; s.v = R.offT(cache, E); s.ldv = 2 * E;
+    s.out = ctx; s.ldo = E; s.B = B; s.H = Hs; s.Lq = Lq; s.Lk = row + Lq; s.Lk_rows = Lmax; s.q_off = row; s.D = E / Hs;
+    s.kmask = h->ep_mask; s.scale = 1.0f / sqrtf((float)(E / Hs)); s.mode = ATTN_CAUSAL;
     R.attn(s, h->attn_impl);
     R.linear(ctx, E, D.c_proj, rq, ACT_NONE, nullptr, 0, x32, E, a32, E, nullptr, 0);   // x + a
     R.ln(a32, E, D.ln1_g, D.ln1_b, 1e-5f, 0, rq, E, n32, nT);                           // n = ln_1(x + a)

@@ -247,6 +247,23 @@ int launch_broadcast_rows(const float* src, float* out, long long rows, int E, i
 int launch_seq_embed(const float* prompt, long long sb, long long sl, const uint8_t* pmask, const float* sep, const float* obs_tok,
                      const float* act_tok, const float* pos_table, int n_pos, float* x32, void* xT, uint8_t* mask, int B, int L, int Lp,
                      int Q, int E, bool is_bf16, hipStream_t st);
+// incremental decoding of the decoder-only policies. Episode state on the device: cache_mask [B][n_pos] (key mask at the cache's row stride),
+// posbase[b] (position id of sample b's next valid row), fresh[b] (1 after a restart: the next action slot is absent).
+// rows [0, Lp] ([prompt | sep] + positions) of n samples -> x32 / xT / mask [n, Lp + 1]; block r comes from sample list[r] (DEVICE array,
+// optional: identity) whose cache_mask rows [0, Lp] and posbase (= valid prompt tokens + 1) are written
+int launch_seq_embed_prefill(const float* prompt, long long sb, long long sl, const uint8_t* pmask, const float* sep, const float* pos_table,
+                             int n_pos, float* x32, void* xT, uint8_t* mask, uint8_t* cache_mask, int* posbase, const int* list, int n, int Lp,
+                             int E, bool is_bf16, hipStream_t st);
+// the rows of one env step ([prev action,] Q observation tokens) of every sample -> x32 / xT [B, Q + has_act, E]; positions continue posbase[b];
+// cache_mask[b][row0 + i] and posbase[b] are updated, fresh[b] is consumed (a fresh sample's action row: zeros, key mask 0, no position id)
+int launch_seq_embed_step(const float* obs_tok, const float* act_tok, const float* pos_table, int n_pos, float* x32, void* xT,
+                          uint8_t* cache_mask, int* posbase, uint8_t* fresh, int row0, int B, int Q, int has_act, int E, bool is_bf16,
+                          hipStream_t st);
+// for the n listed samples (DEVICE array): cache_mask[b][lo .. hi) = 0, fresh[b] = 1
+int launch_seq_restart(const int* list, int n, uint8_t* cache_mask, uint8_t* fresh, int lo, int hi, int n_pos, hipStream_t st);
+// rows [n * L] of width N (operand type, row stride ld_in) -> rows [0, L) of sample list[r]'s (optional: r's) block of a cache of Lmax rows per sample
+int launch_seq_kv_store(const void* in, long long ld_in, void* out, const int* list, int n, int L, int N, int Lmax, bool is_bf16,
+                        hipStream_t st);
 int launch_fill_u8(uint8_t* p, long long n, uint8_t v, hipStream_t st);
 
 // ---------------------------------------------------------------- attention

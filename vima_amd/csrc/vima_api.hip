@@ -228,6 +228,10 @@ struct VimaHandle {
   uint8_t* ep_mask = nullptr; int* ep_poscnt = nullptr; size_t ep_aux_cap = 0;
   uint8_t* ep_fresh = nullptr;   // [B] 1 = the sample was restarted (vima_decode_restart): its next step has no previous action
   int ep_B = 0, ep_Q = 0, ep_Lmax = 0, ep_Lp = 0, ep_step = -1;
+  // decoder-only episode (vima_seq_prefill / vima_seq_decode_step; GPT / GATO handles, which never run vima_decode_step: ep_kv / ep_mask / ep_poscnt /
+  // ep_fresh and ep_B / ep_Q / ep_Lp / ep_Lmax are theirs): seq_next = the step number the next call must carry, seq_row = cache rows in use
+  // (Lp + 1 + the rows of the steps so far) = the row the next step writes at
+  bool seq_live = false; int seq_next = 0, seq_row = 0;
   // option "decode_ring": the ONE row index space of the episode caches is a ring. Host bookkeeping (decode_prepare plans, decode_commit stores):
   // ring_wp = next row to write, ring_hw = one past the highest row written since step 0 (rows beyond it hold hipMalloc garbage and are never
   // read), ring_age[b] = ring rows advanced (skipped tail rows included) since sample b's episode began
@@ -1797,7 +1801,7 @@ int vima_set_option(VimaHandle* h, const char* key, int64_t value) {
   else if (k == "geglu_pair") h->geglu_pair = (int)value;
   else if (k == "ln_fuse") h->ln_fuse = (int)value;
   else if (k == "kv_headmajor") { h->kv_headmajor = (int)value; h->kv_valid = false; h->ep_step = -1; }   // the next decode rebuilds the cache in the chosen layout; a running episode (vima_decode_step) ends: start a new one with step 0
-  else if (k == "decode_ring") { h->decode_ring = value != 0; h->ep_step = -1; }   // a running episode (vima_decode_step) ends: start a new one with step 0
+  else if (k == "decode_ring") { h->decode_ring = value != 0; h->ep_step = -1; h->seq_live = false; }   // a running episode (vima_decode_step) ends: start a new one with step 0
   else if (k == "restart_batched") h->restart_batched = (int)value;
   else if (k == "t5_fuse_rms") h->t5_fuse_rms = (int)value;
   else if (k == "stream_T") h->stream_T = (int)value;
@@ -2003,6 +2007,26 @@ struct DecodePlan { bool inc; int has_act, row, Lq, Lmax, kv_mode, Lk, win_end; 
 struct RingStep { int row, advance; };
 static RingStep ring_next(int wp, int Lq, int Lmax) { return wp + Lq > Lmax ? RingStep{0, Lmax - wp + Lq} : RingStep{wp, Lq}; }
 
+// The episode caches for B samples of Lmax rows: per-layer self-attention K | V [layer][B][Lmax][2E], key mask [B][Lmax], position counter and
+// restart flag [B]. Grown (never shrunk) on demand; a reallocation invalidates the captured graphs.
+static int ep_reserve(VimaHandle* h, int B, int Lmax) {
+  const size_t need = (size_t)h->cfg.xf_n_layers * B * Lmax * 2 * h->cfg.embed_dim * h->esz();
+  if (h->ep_kv_bytes >= need && h->ep_aux_cap >= (size_t)B * Lmax) return 0;
+  HIPCK(hipDeviceSynchronize());
+  if (h->ep_kv) (void)hipFree(h->ep_kv);
+  if (h->ep_mask) (void)hipFree(h->ep_mask);
+  if (h->ep_poscnt) (void)hipFree(h->ep_poscnt);
+  if (h->ep_fresh) (void)hipFree(h->ep_fresh);
+  h->ep_kv = nullptr; h->ep_mask = nullptr; h->ep_poscnt = nullptr; h->ep_fresh = nullptr; h->ep_kv_bytes = 0; h->ep_aux_cap = 0;
+  HIPCK(hipMalloc(&h->ep_kv, need));
+  HIPCK(hipMalloc((void**)&h->ep_mask, (size_t)B * Lmax));
+  HIPCK(hipMalloc((void**)&h->ep_poscnt, (size_t)B * sizeof(int)));
+  HIPCK(hipMalloc((void**)&h->ep_fresh, (size_t)B));
+  h->ep_kv_bytes = need; h->ep_aux_cap = (size_t)B * Lmax;
+  ++h->state_gen;
+  return 0;
+}
+
 static int decode_prepare(VimaHandle* h, const float* act_tok, int T, int B, int Q, int L_act, int Lp, int kv_cache_mode, int step,
                           DecodePlan& P) {
   if (!h) return fail("null handle");
@@ -2037,21 +2061,7 @@ static int decode_prepare(VimaHandle* h, const float* act_tok, int T, int B, int
     }
     kv_cache_mode = step == 0 ? 1 : 2;
     if (step == 0) {
-      const size_t need = (size_t)h->cfg.xf_n_layers * B * Lmax * 2 * E * h->esz();
-      if (h->ep_kv_bytes < need || h->ep_aux_cap < (size_t)B * Lmax) {
-        HIPCK(hipDeviceSynchronize());
-        if (h->ep_kv) (void)hipFree(h->ep_kv);
-        if (h->ep_mask) (void)hipFree(h->ep_mask);
-        if (h->ep_poscnt) (void)hipFree(h->ep_poscnt);
-        if (h->ep_fresh) (void)hipFree(h->ep_fresh);
-        h->ep_kv = nullptr; h->ep_mask = nullptr; h->ep_poscnt = nullptr; h->ep_fresh = nullptr; h->ep_kv_bytes = 0; h->ep_aux_cap = 0;
-        HIPCK(hipMalloc(&h->ep_kv, need));
-        HIPCK(hipMalloc((void**)&h->ep_mask, (size_t)B * Lmax));
-        HIPCK(hipMalloc((void**)&h->ep_poscnt, (size_t)B * sizeof(int)));
-        HIPCK(hipMalloc((void**)&h->ep_fresh, (size_t)B));
-        h->ep_kv_bytes = need; h->ep_aux_cap = (size_t)B * Lmax;
-        ++h->state_gen;
-      }
+      if (int e = ep_reserve(h, B, Lmax)) return e;
       h->ep_step = -1;
     }
   }
@@ -2405,6 +2415,14 @@ int vima_decode_restart(VimaHandle* h, const uint8_t* restart, int B, const floa
 // Host-only: how many further vima_decode_step calls would succeed if sample b alone were never restarted (the bookkeeping of decode_prepare run forward).
 int vima_decode_steps_left(VimaHandle* h, int B, int32_t* out_host) {
   if (!h || !out_host) return fail("vima_decode_steps_left: null argument");
+  if (h->cfg.policy_kind == VIMA_POLICY_GPT || h->cfg.policy_kind == VIMA_POLICY_GATO) {   // the episode of vima_seq_prefill / vima_seq_decode_step
+    if (!(h->seq_live && h->ep_B == B))
+      return fail("vima_decode_steps_left: no running episode batch of this size (start one with vima_seq_prefill)");
+    // every step takes Q + 1 rows (after a restart the action slot is a masked row), except step 0 of the batch: Q
+    const int left = h->ep_Lmax - h->seq_row + (h->seq_next == 0 ? 1 : 0);
+    for (int b = 0; b < B; ++b) out_host[b] = left / (h->ep_Q + 1);
+    return 0;
+  }
   if (!(h->ep_step >= 0 && h->ep_B == B)) return fail("vima_decode_steps_left: no running episode batch of this size (start one with vima_decode_step(step = 0))");
   const int Lq = h->ep_Q + 1, Lmax = h->ep_Lmax;
   if (!h->decode_ring) {   // step s needs (s + 1) (Q + 1) - 1 <= n_positions rows since the batch's step 0
@@ -2517,6 +2535,106 @@ int vima_seq_decode(VimaHandle* h, const float* obs_tok, const float* act_tok, i
   if (hfgpt_stack(R, x32, xT, mask, B, L)) return R.err;
   // predicted = tokens_out[Lp + 1 + Q - 1 :: Q + 1] (vima_gato_policy.py:185-187)
   OTHER(R, launch_gather_pred(x32 + (size_t)(Lp + 1) * E, out, T, B, Q, L, E, R.st), "gather_pred");
+  return R.err;
+}
+
+// ---- incremental decoding of the decoder-only policies ------------------------------------------------------------------------------
+// HFGPT blocks are post-LN and act per row, the attention is causal (future keys get -1e4 in the reference: exp underflows to 0 in fp32), so
+// the K | V of a prefix are final once computed: the prompt rows run through the stack once (vima_seq_prefill), every env step feeds only its
+// own rows against the per-layer episode cache (vima_seq_decode_step) and equals the same rows of vima_seq_decode on the whole history.
+static int seq_ready(VimaHandle* h, const char* fn) {
+  if (int e = baseline_ready(h, fn)) return e;
+  if (h->cfg.policy_kind != VIMA_POLICY_GPT && h->cfg.policy_kind != VIMA_POLICY_GATO)
+    return fail(std::string(fn) + ": decoder-only policies (GPT / GATO) only; VIMAFlamingoPolicy steps with vima_decode_step");
+  if (h->decode_ring) return fail(std::string(fn) + ": option decode_ring is not available for the decoder-only policies (set it to 0)");
+  return 0;
+}
+
+int vima_seq_prefill(VimaHandle* h, const float* prompt, int64_t stride_b, int64_t stride_l, const uint8_t* prompt_mask, int B, int Lp,
+                     vima_stream_t stream) {
+  if (int e = seq_ready(h, "vima_seq_prefill")) return e;
+  if (!prompt || !prompt_mask) return fail("vima_seq_prefill: null argument");
+  if (B <= 0 || Lp <= 0) return fail("vima_seq_prefill: empty input");
+  const int E = h->cfg.embed_dim, Lmax = h->cfg.n_positions, L = Lp + 1;
+  if (L > Lmax)
+    return fail("vima_seq_prefill: prompt of " + std::to_string(Lp) + " tokens + separator exceeds n_positions " + std::to_string(Lmax), 34);
+  h->seq_live = false;   // from here on the caches belong to the new episode
+  if (int e = ep_reserve(h, B, Lmax)) return e;
+  Run R{h, (hipStream_t)stream};
+  float* x32 = R.ws<float>((size_t)B * L * E);
+  void* xT = R.wsT((size_t)B * L * E);
+  uint8_t* mask = R.ws<uint8_t>((size_t)B * L);
+  if (R.err) return R.err;
+  HIPCK(hipMemsetAsync(h->ep_fresh, 0, (size_t)B, R.st));
+  OTHER(R, launch_seq_embed_prefill(prompt, stride_b, stride_l, prompt_mask, h->sep_token, h->pos_emb, Lmax, x32, xT, mask, h->ep_mask,
+                                    h->ep_poscnt, nullptr, B, Lp, E, h->bf16, R.st), "seq_embed_prefill");
+  if (hfgpt_stack(R, x32, xT, mask, B, L, h->ep_kv, nullptr, B, Lmax)) return R.err;
+  h->seq_live = true; h->seq_next = 0; h->seq_row = L;
+  h->ep_B = B; h->ep_Q = rgb_tokens_per_image(h->cfg.policy_kind); h->ep_Lp = Lp; h->ep_Lmax = Lmax;
+  return 0;
+}
+
+static int seq_step_launch(VimaHandle* h, const float* obs_tok, const float* act_tok, int B, int Q, int has_act, int row, float* out,
+                           hipStream_t stream) {
+  if (int e = check_ready(h)) return e;
+  const int E = h->cfg.embed_dim, Lmax = h->ep_Lmax, Lq = Q + has_act;
+  Run R{h, stream};
+  float* x32 = R.ws<float>((size_t)B * Lq * E);
+  void* xT = R.wsT((size_t)B * Lq * E);
+  if (R.err) return R.err;
+  OTHER(R, launch_seq_embed_step(obs_tok, act_tok, h->pos_emb, Lmax, x32, xT, h->ep_mask, h->ep_poscnt, h->ep_fresh, row, B, Q, has_act, E,
+                                 h->bf16, R.st), "seq_embed_step");
+  if (hfgpt_step_stack(R, x32, xT, B, Lq, row, Lmax)) return R.err;
+  OTHER(R, launch_gather_pred(x32, out, 1, B, Lq, Lq, E, R.st), "gather_pred");   // the last new row of every sample
+  return R.err;
+}
+
+int vima_seq_decode_step(VimaHandle* h, const float* obs_tok, const float* act_tok, int step, int B, float* out, vima_stream_t stream) {
+  if (int e = seq_ready(h, "vima_seq_decode_step")) return e;
+  if (!obs_tok || !out) return fail("vima_seq_decode_step: null argument");
+  if (step < 0 || B <= 0) return fail("vima_seq_decode_step: step must be >= 0 and B > 0");
+  if (!(h->seq_live && h->seq_next == step && h->ep_B == B))
+    return fail("vima_seq_decode_step: step " + std::to_string(step) + " of " + std::to_string(B) + " samples does not continue the episode state (" +
+                (h->seq_live ? "next step " + std::to_string(h->seq_next) + " of " + std::to_string(h->ep_B) + " samples" : std::string("no episode")) +
+                "); start an episode with vima_seq_prefill");
+  const int has_act = step > 0 ? 1 : 0, Q = h->ep_Q, Lq = Q + has_act, row = h->seq_row;
+  if (has_act && !act_tok) return fail("vima_seq_decode_step: the previous action token is required for step > 0");
+  if (row + Lq > h->ep_Lmax)
+    return fail("vima_seq_decode_step: sequence of " + std::to_string(row + Lq) + " tokens exceeds n_positions " + std::to_string(h->ep_Lmax), 34);
+  const std::string key = gkey("seq_step", {(long long)(uintptr_t)obs_tok, (long long)(uintptr_t)act_tok, (long long)(uintptr_t)out, B, row, has_act,
+                                            (long long)(uintptr_t)h->ep_kv});
+  const int rc = run_graphed(h, key, (hipStream_t)stream, [&](hipStream_t st) {
+    return seq_step_launch(h, obs_tok, has_act ? act_tok : nullptr, B, Q, has_act, row, out, st);
+  });
+  if (!rc) { h->seq_next = step + 1; h->seq_row = row + Lq; }
+  return rc;
+}
+
+// All flagged samples are rebuilt TOGETHER: one compact prefill of n_flagged x (Lp + 1) rows through the stack, whose k | v copy per layer
+// scatters by the sample list -- 2 + launches of one stack pass, whatever the number of flagged samples.
+int vima_seq_decode_restart(VimaHandle* h, const uint8_t* restart, int B, const float* prompt, int64_t stride_b, int64_t stride_l,
+                            const uint8_t* prompt_mask, int Lp, vima_stream_t stream) {
+  if (int e = seq_ready(h, "vima_seq_decode_restart")) return e;
+  if (!restart || !prompt || !prompt_mask) return fail("vima_seq_decode_restart: null argument");
+  if (!(h->seq_live && h->ep_B == B && h->ep_Lp == Lp))
+    return fail("vima_seq_decode_restart: no running episode batch with this B / Lp (start one with vima_seq_prefill)");
+  const int E = h->cfg.embed_dim, Lmax = h->ep_Lmax, L = Lp + 1;
+  h->restart_list.clear();
+  for (int b = 0; b < B; ++b)
+    if (restart[b]) h->restart_list.push_back(b);
+  const int n_r = (int)h->restart_list.size();
+  if (n_r == 0) return 0;
+  Run R{h, (hipStream_t)stream};
+  int* list = R.ws<int>((size_t)n_r);
+  float* x32 = R.ws<float>((size_t)n_r * L * E);
+  void* xT = R.wsT((size_t)n_r * L * E);
+  uint8_t* mask = R.ws<uint8_t>((size_t)n_r * L);
+  if (R.err) return R.err;
+  HIPCK(hipMemcpyAsync(list, h->restart_list.data(), (size_t)n_r * sizeof(int), hipMemcpyHostToDevice, R.st));
+  OTHER(R, launch_seq_restart(list, n_r, h->ep_mask, h->ep_fresh, L, h->seq_row, Lmax, R.st), "seq_restart");
+  OTHER(R, launch_seq_embed_prefill(prompt, stride_b, stride_l, prompt_mask, h->sep_token, h->pos_emb, Lmax, x32, xT, mask, h->ep_mask,
+                                    h->ep_poscnt, list, n_r, Lp, E, h->bf16, R.st), "seq_embed_prefill");
+  hfgpt_stack(R, x32, xT, mask, n_r, L, h->ep_kv, list, B, Lmax);
   return R.err;
 }
 
