@@ -659,7 +659,8 @@ __global__ __launch_bounds__(256, QG > 1 ? 2 : (D == 32 ? 4 : 3)) void attn_mfma
   const int boff = qblk * QB + QB - 1;                         // index = key - qi + boff in [0, kpad + QB - 2]
   // T5 / cross mode: the mask enters as the S^T accumulators' initial value (see the key loop); its "minus infinity" for a masked key is then multiplied by
   // log2(e) (or the score scale) with the rest of the score, so it is -1e38 instead of finfo.min: it absorbs any score all the same (masked keys weigh exactly 0,
-  // a row without a single valid key still comes out uniform) and stays finite
+  // a row without a single valid key still comes out uniform) and stays finite -- for ANY caller-supplied scale: the table holds kMaskNeg / max(multiplier, 1),
+  // i.e. the scaled value is -1e38 at the most (stored as it was, -1e38, for every multiplier <= 1: the model's cross-attention scales)
   constexpr bool CINIT = MODE != ATTN_CAUSAL;
   constexpr float kMaskNeg = -1.0e38f;
   const int far = MODE == ATTN_T5 ? p.bias_far : 0;
@@ -742,6 +743,12 @@ __global__ __launch_bounds__(256, QG > 1 ? 2 : (D == 32 ? 4 : 3)) void attn_mfma
   {
     // key j = u * 256 + tid: wave w of pass u holds exactly tile 4 u + w, so the tile flag is a ballot
     const int npass = (kpad + 255) >> 8;
+    float mask_neg = MODE == ATTN_T5 ? kMaskNeg / kLog2e : -FLT_MAX;
+    if constexpr (MODE == ATTN_CROSS) {
+      float sc = p.scale;
+      asm volatile("" : "+s"(sc));   // opaque: a value of this prologue only, kept apart from the key loop's own scale * log2(e) (whose code stays as it was)
+      mask_neg = kMaskNeg / fmaxf(sc * kLog2e, 1.0f);
+    }
     const unsigned char* km = p.kmask ? reinterpret_cast<const unsigned char*>(p.kmask) + (long long)b * p.Lkr : nullptr;
     for (int u0 = 0; u0 < npass; u0 += 4) {
       unsigned char mk[4];
@@ -761,7 +768,7 @@ __global__ __launch_bounds__(256, QG > 1 ? 2 : (D == 32 ? 4 : 3)) void attn_mfma
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int j = (u0 + u) * 256 + tid;
-        const float v = j < p.Lk ? (mk[u] ? 0.0f : (CINIT ? kMaskNeg : -FLT_MAX)) : -INFINITY;
+        const float v = j < p.Lk ? (mk[u] ? 0.0f : mask_neg) : -INFINITY;
         if (j < kpad) madd[j] = v;
         const bool nz = j < kpad && v != 0.0f;
         const bool anyz = __any(nz);
