@@ -312,6 +312,25 @@ void vima_comm_destroy(VimaComm* c);
  * operand conversion is done internally. act: 0 none, 1 relu, 2 gelu(erf), 3 quickgelu. bias/mul/res may be NULL. */
 int vima_op_linear(VimaHandle* h, const float* A, const float* W, const float* bias, const float* mul,
                    const float* res, int M, int N, int K, int act, float* out, vima_stream_t stream);
+/* ONE GEMM launch described field for field (additive, ABI version unchanged; parity tests of the launcher's structured forms). Every field has the meaning of the
+ * GemmArgs field of the same name in vima_amd/csrc/kernels.h; strides are in elements. A, W, A2, W2, mul, resT, outT and outT_lo are
+ * DEVICE buffers in the handle's operand type (bf16 on BF16 / FP8W handles, fp32 on FP32 / BF16X3 handles), the others fp32 / int32
+ * device buffers; nothing is cast, widened or staged, and the launcher's own validation is the only one: a form or geometry it
+ * refuses is returned as an error with no output written. x3 = 1 asks for the split-bf16 products of a BF16X3 handle. The handle's
+ * GEMM options apply; *kernel_id (optional) receives the kernel the launcher chose (the ids of vima_prof_read_gemm_kernels).
+ * fp8 operands / outputs are not reachable through this entry. */
+typedef struct VimaGemmDesc {
+  const void* A; const void* W; const void* A2; const void* W2; const void* mul; const void* resT;
+  void* outT; void* outT_lo;
+  const float* bias; const float* res; const float* rs_ssq; const float* rs_sum; const float* rs_c;
+  float* out32; float* ssq_out; float* sum_out;
+  const int32_t* grp_col;
+  int64_t bsA, bsW, bsBias, bsMul, bsRes, bs32, bsT;
+  int32_t M, N, K, lda, ldw, lda2, ldw2, ldmul, ldres, ldresT, ld32, ldT, ldT_lo, batch, act;
+  int32_t hm_D, hm_L, pair32, rb, s_hi, s_lo, ro, split_n, rs_parts, x3;
+  float rs_invk, rs_eps;
+} VimaGemmDesc;
+int vima_op_gemm(VimaHandle* h, const VimaGemmDesc* desc, int* kernel_id, vima_stream_t stream);
 /* LayerNorm (rms=0) / T5 RMSNorm (rms=1) over rows of length E. */
 int vima_op_layernorm(VimaHandle* h, const float* x, const float* gamma, const float* beta, float eps, int rms,
                       int rows, int E, float* out, vima_stream_t stream);

@@ -22,6 +22,16 @@ class VimaConfig(ctypes.Structure):
                                      "xattn_n_positions", "n_positions", "precision", "policy_kind")]
 
 
+class VimaGemmDesc(ctypes.Structure):
+    """VimaGemmDesc of include/vima_hip.h (vima_op_gemm): the fields of GemmArgs (vima_amd/csrc/kernels.h), same names, same order as the header."""
+    _fields_ = ([(n, vp) for n in ("A", "W", "A2", "W2", "mul", "resT", "outT", "outT_lo", "bias", "res", "rs_ssq", "rs_sum", "rs_c",
+                                   "out32", "ssq_out", "sum_out", "grp_col")] +
+                [(n, c_i64) for n in ("bsA", "bsW", "bsBias", "bsMul", "bsRes", "bs32", "bsT")] +
+                [(n, c_i32) for n in ("M", "N", "K", "lda", "ldw", "lda2", "ldw2", "ldmul", "ldres", "ldresT", "ld32", "ldT", "ldT_lo", "batch", "act",
+                                      "hm_D", "hm_L", "pair32", "rb", "s_hi", "s_lo", "ro", "split_n", "rs_parts", "x3")] +
+                [(n, c_f32) for n in ("rs_invk", "rs_eps")])
+
+
 def _header_abi_version() -> int:
     """VIMA_ABI_VERSION the package was built against. The number lives in include/vima_hip.h; `vima_amd/csrc/build.sh` copies it into
     vima_amd/_abi.py next to the library, so that a deployment which ships only the package directory (+ the .so, or a VIMA_HIP_LIB
@@ -82,6 +92,7 @@ PROTOTYPES = {
     "vima_act": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, ctypes.POINTER(c_f32), vp, vp * 4, vp, vp, vp, vp, vp]),
     "vima_op_linear": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       vp, vp]),
+    "vima_op_gemm": (ctypes.c_int, [vp, ctypes.POINTER(VimaGemmDesc), ctypes.POINTER(ctypes.c_int), vp]),
     "vima_op_layernorm": (ctypes.c_int, [vp, vp, vp, vp, c_f32, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),
     "vima_op_attention": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_int, ctypes.c_int, c_f32, ctypes.c_int, ctypes.c_int, vp, vp]),

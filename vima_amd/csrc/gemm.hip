@@ -2536,8 +2536,8 @@ int launch_t(const GemmArgs& a, hipStream_t st) {
     }
     if (gemm_tile(a.tune) == 13 && v) return launch_tile<T, Tile64x128, true>(d, a, v, st);
     if (gemm_tile(a.tune) == 14 && v) return launch_tile<T, Tile128x64, true>(d, a, v, st);
-    if (gemm_tile(a.tune) == 7 && v) return launch_tile<T, TileXS, true>(d, a, v, st);
-    if (gemm_tile(a.tune) == 8 && v) return launch_tile<T, Tile64, true>(d, a, v, st);
+    if (gemm_tile(a.tune) == 7 && v) { if (a.kernel_id) *a.kernel_id = 7000 + (a.act + 1) * 10; return launch_tile<T, TileXS, true>(d, a, v, st); }
+    if (gemm_tile(a.tune) == 8 && v) { if (a.kernel_id) *a.kernel_id = 6000 + (a.act + 1) * 10; return launch_tile<T, Tile64, true>(d, a, v, st); }
   }
   if (a.kernel_id) *a.kernel_id = (a.x3 ? 21000 : 5000) + (a.act + 1) * 10;
   if (gemm_variant(a.tune) == 1 || a.w8) return launch_tile<T, TileS, true>(d, a, v, st);

@@ -2766,6 +2766,42 @@ int vima_op_linear(VimaHandle* h, const float* A, const float* W, const float* b
   return R.gemm(a);
 }
 
+// One launch_gemm call described field for field by the caller: no casts, no widening, no gemm_*_ok question of its own -- what
+// launch_gemm refuses comes back as the error. The only workspace is the split-K scratch, sized the way Run::gemm sizes it.
+int vima_op_gemm(VimaHandle* h, const VimaGemmDesc* g, int* kernel_id, vima_stream_t stream) {
+  if (!h) return fail("null handle");
+  if (!g) return fail("vima_op_gemm: null descriptor");
+  HIPCK(hipSetDevice(h->device));
+  if (h->arena.reset()) return fail("workspace reset failed");
+  Run R{h, (hipStream_t)stream};
+  GemmArgs a;
+  a.A = g->A; a.W = g->W; a.M = g->M; a.N = g->N; a.K = g->K; a.lda = g->lda; a.ldw = g->ldw; a.batch = g->batch;
+  a.grp_col = g->grp_col;
+  a.A2 = g->A2; a.W2 = g->W2; a.lda2 = g->lda2; a.ldw2 = g->ldw2;
+  a.bsA = g->bsA; a.bsW = g->bsW; a.bsBias = g->bsBias; a.bsMul = g->bsMul; a.bsRes = g->bsRes; a.bs32 = g->bs32; a.bsT = g->bsT;
+  a.bias = g->bias; a.act = g->act; a.mul = g->mul; a.ldmul = g->ldmul; a.res = g->res; a.ldres = g->ldres;
+  a.resT = g->resT; a.ldresT = g->ldresT; a.out32 = g->out32; a.ld32 = g->ld32; a.outT = g->outT; a.ldT = g->ldT;
+  a.hm_D = g->hm_D; a.hm_L = g->hm_L; a.pair32 = g->pair32;
+  a.rb = g->rb; a.s_hi = g->s_hi; a.s_lo = g->s_lo; a.ro = g->ro;
+  a.outT_lo = g->outT_lo; a.ldT_lo = g->ldT_lo; a.split_n = g->split_n;
+  a.ssq_out = g->ssq_out; a.rs_ssq = g->rs_ssq; a.rs_parts = g->rs_parts; a.rs_invk = g->rs_invk; a.rs_eps = g->rs_eps;
+  a.sum_out = g->sum_out; a.rs_sum = g->rs_sum; a.rs_c = g->rs_c;
+  a.x3 = g->x3;
+  a.tune = &h->tune;
+  if (const size_t wsb = gemm_splitk_bytes(a, h->bf16)) {
+    a.splitk_ws = R.ws<float>(wsb / sizeof(float));
+    a.splitk_ws_bytes = wsb;
+    if (R.err) return R.err;
+  }
+  int kid = 0;
+  a.kernel_id = &kid;
+  const int e = launch_gemm(a, h->bf16, R.st);
+  if (kernel_id) *kernel_id = kid;
+  if (e) return fail(std::string("vima_op_gemm: launch_gemm refused or failed: ") + hipGetErrorString((hipError_t)e) + " (M=" + std::to_string(a.M) +
+                     " N=" + std::to_string(a.N) + " K=" + std::to_string(a.K) + ")", e);
+  return 0;
+}
+
 int vima_op_layernorm(VimaHandle* h, const float* x, const float* gamma, const float* beta, float eps, int rms, int rows, int E,
                       float* out, vima_stream_t stream) {
   if (!h) return fail("null handle");
