@@ -2,7 +2,7 @@
 finished sample is restarted with a new prompt (`restart_samples`) while the others keep their histories, and the episode caches'
 shared row space is a ring (`set_option("decode_ring", 1)`), so no step count forces the whole batch back to step 0.
 
-    python examples/rollout_loop.py [--model 200M] [--batch 32] [--steps 500] [--prompts 3]
+    python examples/rollout_loop.py [--model 200M] [--batch 32] [--steps 500] [--prompts 3] [--stochastic]
 
 Per env step: forward_obs_token -> forward_step -> act (action head, mode, action embedding in one native call). Synthetic inputs
 stand in for the simulator, as in examples/episode_loop.py. Episode lengths are staggered (6 .. 28 steps); every eighth sample's
@@ -21,12 +21,27 @@ from vima_testing import synthetic as syn                      # noqa: E402
 from vima_amd.policy import VIMAPolicy                    # noqa: E402
 
 
+def pick_candidate(cand, best):
+    """`cand`: the ActionSelection of act(..., n_samples=S), every field with a sample axis after the leading dims; `best` int64
+    [...]: the candidate to keep per state -> the ActionSelection of that candidate alone, every field without the sample axis."""
+    def pick(v, has_feature_axis):
+        index = best[..., None, None].expand(*best.shape, 1, v.shape[-1]) if has_feature_axis else best[..., None]
+        return torch.gather(v, best.dim(), index).squeeze(best.dim())
+    return cand._replace(actions={k: pick(v, True) for k, v in cand.actions.items()},
+                         continuous={k: pick(v, True) for k, v in cand.continuous.items()},
+                         log_prob={k: pick(v, False) for k, v in cand.log_prob.items()},
+                         entropy={k: pick(v, False) for k, v in cand.entropy.items()},
+                         action_token=pick(cand.action_token, True))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="200M")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--prompts", type=int, default=3, help="encoded prompt batches the new episodes draw from")
+    ap.add_argument("--stochastic", action="store_true", help="sample 4 candidate actions per state on the device (temperature 0.7, top-k 10, "
+                    "top-p 0.9) and take the likeliest, instead of the mode")
     args = ap.parse_args()
     dev = "cuda:0"
     B = args.batch
@@ -59,7 +74,11 @@ def main():
                 policy.restart_samples(flags, prompt_tokens, prompt_masks)             # all flagged samples in one call
         obs_token, obs_mask = policy.forward_obs_token(observations[t % len(observations)])
         predicted = policy.forward_step(obs_token, obs_mask, prev, prompt_tokens, prompt_masks, step=t)   # step just counts up
-        sel = policy.act(predicted.unsqueeze(0))
+        if args.stochastic:   # 4 candidates per state from one pass of the action head; keep the one with the largest log-probability
+            cand = policy.act(predicted.unsqueeze(0), sample=True, temperature=0.7, top_k=10, top_p=0.9, n_samples=4)
+            sel = pick_candidate(cand, sum(cand.log_prob.values()).argmax(dim=-1))
+        else:
+            sel = policy.act(predicted.unsqueeze(0))
         prev = sel.action_token                                                       # ignored for the samples restarted before the next step
         age = [a + 1 for a in age]
     torch.cuda.synchronize()

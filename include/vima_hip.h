@@ -224,6 +224,45 @@ int vima_action_select(const float* logits, int R, const float* u, const float* 
 int vima_act(VimaHandle* h, const float* tokens, int R, const float* u, const float* bounds, float* logits_out, int64_t* const idx[4],
              float* cont, float* log_prob, float* entropy, float* token, vima_stream_t stream);
 
+/* Sampling controls and action scoring for the two calls above (additive, ABI version unchanged). opts NULL = all defaults. Per row r
+ * of logits, per sample s < n_samples and per segment of n bins:
+ *   temperature  DEVICE f32 [R], one per row of LOGITS, or NULL = 1. z = x / T, one correctly rounded fp32 division per element; T is
+ *                clamped to [1e-4, 1e4] and a NaN is 1, so z is finite for finite logits. Read from device memory during the launch.
+ *   top_k        rank(i) = #{j : z_j > z_i} + #{j < i : z_j == z_i} (exact comparisons, ties to the lower index); bin i survives iff
+ *                rank(i) < top_k. <= 0 or >= n keeps every bin; one value for all segments, so 50 truncates only the 100-bin heads.
+ *   top_p        after top_k: q = softmax(z) over the survivors; the bin of rank r survives iff the mass of the surviving bins of
+ *                rank < r is < top_p (rank 0 always survives). >= 1: off; must be > 0.
+ *   n_samples    S >= 1 candidates per row of logits: OUTPUT row r * S + s is sample s of logits row r. Every output and u have R * S rows.
+ *   given        idx are INPUTS (i64, clamped to [0, n), left as they are): nothing is selected, u is ignored, and cont, log_prob,
+ *                entropy (and the token of vima_act_ex) are computed for those bins. Requires n_samples == 1.
+ * The kept set K defines pi = softmax(z) over K and 0 elsewhere; log pi = z - (max_K z + log sum_K exp(z - max_K z)) on K, -inf
+ * outside (only a given bin can be outside). u NULL selects the first index of the segment's maximum, whatever the filters; otherwise
+ * the inverse CDF of vima_action_select runs over pi in bin order, and a result outside K (possible through rounding at the upper end
+ * only) becomes the last bin of K at or below it. log_prob and entropy describe pi, per key as above. */
+typedef struct VimaSampleOpts {
+  const float* temperature; /* DEVICE f32 [R] or NULL */
+  int top_k;                /* <= 0: off */
+  float top_p;              /* >= 1: off; must be > 0 */
+  int n_samples;            /* S >= 1 */
+  int given;                /* idx are inputs */
+} VimaSampleOpts;
+
+/* vima_action_select with VimaSampleOpts: ONE launch of act_sample_kernel (vima_amd/csrc/action_sample.hip), one workgroup per output
+ * row; logits f32 [R,700], u f32 [R*S,12] or NULL, idx / cont / log_prob / entropy with R*S rows. With opts NULL (or temperature NULL,
+ * top_k <= 0, top_p >= 1, n_samples 1, given 0) every output equals vima_action_select's, bit for bit. Refused before any launch:
+ * top_p <= 0 or NaN, n_samples < 1, given with n_samples != 1, null idx. */
+int vima_action_select_ex(const float* logits, int R, const float* u, const VimaSampleOpts* opts, const float* bounds,
+                          int64_t* const idx[4], float* cont, float* log_prob, float* entropy, vima_stream_t stream);
+
+/* vima_act with VimaSampleOpts: the launches of vima_action_head on R rows (tokens f32 [R,E]; logits_out f32 [R,700] or NULL), then
+ * act_sample_kernel on R*S rows, then the rest of vima_action_embed on R*S rows -> token f32 [R*S,E] (NULL skips it), bit-identical to
+ * vima_action_embed on the chosen (or given) bins. Every policy_kind and precision; the refusals of vima_action_select_ex. With option
+ * "graphs" it is captured like vima_act: the key holds every pointer, R, S, top_k, the bits of top_p, given and the VALUES of the
+ * bounds; u and temperature are read from device memory at replay, so new values written in place take effect. */
+int vima_act_ex(VimaHandle* h, const float* tokens, int R, const float* u, const VimaSampleOpts* opts, const float* bounds,
+                float* logits_out, int64_t* const idx[4], float* cont, float* log_prob, float* entropy, float* token,
+                vima_stream_t stream);
+
 /* ---- baseline policies (policy_kind != VIMA_POLICY_VIMA) ---------------------------------------- */
 /* Tokens one frame pair contributes: Q = 1 (GPT), 16 (GATO: 8 patches x 2 views), 4 (FLAMINGO: Perceiver latents); feature
  * width of obj_encoder's output Eo = 2E (GPT: views concatenated on the feature axis, obj_encoder.py:232-245) or E. */

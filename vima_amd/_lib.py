@@ -32,6 +32,11 @@ class VimaGemmDesc(ctypes.Structure):
                 [(n, c_f32) for n in ("rs_invk", "rs_eps")])
 
 
+class VimaSampleOpts(ctypes.Structure):
+    """VimaSampleOpts of include/vima_hip.h (vima_action_select_ex / vima_act_ex), same names, same order as the header."""
+    _fields_ = [("temperature", vp), ("top_k", ctypes.c_int), ("top_p", c_f32), ("n_samples", ctypes.c_int), ("given", ctypes.c_int)]
+
+
 def _header_abi_version() -> int:
     """VIMA_ABI_VERSION the package was built against. The number lives in include/vima_hip.h; `vima_amd/csrc/build.sh` copies it into
     vima_amd/_abi.py next to the library, so that a deployment which ships only the package directory (+ the .so, or a VIMA_HIP_LIB
@@ -90,6 +95,9 @@ PROTOTYPES = {
     "vima_action_embed": (ctypes.c_int, [vp, vp * 4, ctypes.c_int, vp, vp]),
     "vima_action_select": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.POINTER(c_f32), vp * 4, vp, vp, vp, vp]),
     "vima_act": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, ctypes.POINTER(c_f32), vp, vp * 4, vp, vp, vp, vp, vp]),
+    "vima_action_select_ex": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.POINTER(VimaSampleOpts), ctypes.POINTER(c_f32), vp * 4, vp, vp, vp, vp]),
+    "vima_act_ex": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, ctypes.POINTER(VimaSampleOpts), ctypes.POINTER(c_f32), vp, vp * 4, vp, vp, vp, vp,
+                                   vp]),
     "vima_op_linear": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       vp, vp]),
     "vima_op_gemm": (ctypes.c_int, [vp, ctypes.POINTER(VimaGemmDesc), ctypes.POINTER(ctypes.c_int), vp]),

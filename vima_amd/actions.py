@@ -6,6 +6,13 @@ environment takes, log-probability and entropy -- `vima_action_select` of includ
     sel = select_actions(logits, uniforms=torch.rand(R, 12, device=dev), action_bounds=meta["action_bounds"])
 
 `VIMAPolicy.act` is the same selection fused behind the action head, followed by the action embedding (`vima_act`).
+
+Sampling controls (`vima_action_select_ex` / `vima_act_ex`, `act_sample_kernel` of vima_amd/csrc/action_sample.hip): a temperature,
+top-k / top-p truncation, several candidates per state, and `score_actions` / `VIMAPolicy.evaluate_actions` for the
+log-probability of actions the caller already has.
+
+    sel = select_actions(logits, uniforms=torch.rand(R, 8, 12, device=dev), temperature=0.7, top_k=10, top_p=0.9, n_samples=8)
+    lp = score_actions(logits, sel_single.actions, temperature=0.7).log_prob
 """
 from __future__ import annotations
 
@@ -80,20 +87,80 @@ def package(lead, idx, cont, logp, ent, action_token=None, logits=None) -> Actio
     return ActionSelection(actions, continuous, log_prob, entropy, action_token, logits)
 
 
-def select_actions(logits: torch.Tensor, uniforms: torch.Tensor | None = None, action_bounds=None) -> ActionSelection:
-    """logits float32 [..., 700] on the GPU -> ActionSelection. `uniforms` [..., 12] in [0, 1) selects inverse-CDF sampling
-    (None: the mode, torch.argmax of every segment); `action_bounds` rescales the continuous action like the reference loop."""
+def sample_opts(temperature, top_k, top_p, n_samples, lead, device, given=False):
+    """The sampling controls of `select_actions` / `VIMAPolicy.act` as (VimaSampleOpts, temperature tensor to keep alive), or
+    (None, None) when every one is at its default. `temperature`: a Python float or a tensor broadcastable to the leading dims
+    `lead` of the logits, materialised as a device float32 [R]."""
+    if temperature is None and top_k <= 0 and top_p >= 1.0 and n_samples == 1 and not given:
+        return None, None
+    temp = None
+    if temperature is not None:
+        temp = torch.as_tensor(temperature, dtype=torch.float32, device=device)
+        temp = torch.broadcast_to(temp, tuple(lead)).reshape(-1).contiguous()
+    opts = _lib.VimaSampleOpts(temp.data_ptr() if temp is not None else None, int(top_k), float(top_p), int(n_samples), int(bool(given)))
+    return opts, temp
+
+
+def _logits_arg(logits, who):
     if not logits.is_cuda:
-        raise RuntimeError("select_actions needs logits on the GPU: the HIP library has no CPU fallback")
+        raise RuntimeError(f"{who} needs logits on the GPU: the HIP library has no CPU fallback")
     if logits.shape[-1] != N_LOGITS:
         raise AssertionError(f"expected [..., {N_LOGITS}] logits, got {tuple(logits.shape)}")
+    return logits.shape[:-1], logits.to(dtype=torch.float32).reshape(-1, N_LOGITS).contiguous()
+
+
+def given_bins(actions, device):
+    """{key: integer bins [..., 2|4]} -> (leading dims, four contiguous int64 [R, 2|4] tensors on `device`)"""
+    if set(actions.keys()) != set(ACTION_KEYS):
+        raise AssertionError(f"expected action keys {ACTION_KEYS}, got {sorted(actions.keys())}")
+    lead = actions[ACTION_KEYS[0]].shape[:-1]
+    idx = [actions[k].to(device=device, dtype=torch.int64).reshape(-1, w).contiguous() for k, w in zip(ACTION_KEYS, KEY_DIMS)]
+    if any(t.shape[0] != idx[0].shape[0] for t in idx):
+        raise ValueError("the four action keys must share their leading dims")
+    return lead, idx
+
+
+def select_actions(logits: torch.Tensor, uniforms: torch.Tensor | None = None, action_bounds=None, *, temperature=None,
+                   top_k: int = 0, top_p: float = 1.0, n_samples: int = 1) -> ActionSelection:
+    """logits float32 [..., 700] on the GPU -> ActionSelection. `uniforms` [..., 12] in [0, 1) selects inverse-CDF sampling
+    (None: the mode, torch.argmax of every segment); `action_bounds` rescales the continuous action like the reference loop.
+    Sampling controls (`vima_action_select_ex`, one launch of `act_sample_kernel`; all defaults: `vima_action_select` as before):
+    `temperature` (float or tensor broadcastable to the leading dims) divides the logits, `top_k` / `top_p` truncate every
+    segment (top-p after top-k) and log_prob / entropy describe the truncated distribution; `n_samples` = S > 1 draws S candidates
+    per row: every output gains a sample axis after the leading dims and `uniforms` is [..., S, 12]."""
+    lead, x = _logits_arg(logits, "select_actions")
     lib = _lib.load()
-    lead = logits.shape[:-1]
-    x = logits.to(dtype=torch.float32).reshape(-1, N_LOGITS).contiguous()
     R = x.shape[0]
-    u = uniforms_arg(uniforms, R, x.device)
-    idx, cont, logp, ent = alloc_outputs(R, x.device)
+    opts, temp = sample_opts(temperature, top_k, top_p, n_samples, lead, x.device)
+    S = int(n_samples) if opts is not None else 1
+    u = uniforms_arg(uniforms, R * max(S, 1), x.device)
+    idx, cont, logp, ent = alloc_outputs(R * max(S, 1), x.device)
     arr = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in idx])
     stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    _lib.check(lib.vima_action_select(_ptr(x), R, _ptr(u), bounds_array(action_bounds), arr, _ptr(cont), _ptr(logp), _ptr(ent), stream))
+    if opts is None:
+        _lib.check(lib.vima_action_select(_ptr(x), R, _ptr(u), bounds_array(action_bounds), arr, _ptr(cont), _ptr(logp), _ptr(ent), stream))
+        return package(lead, idx, cont, logp, ent)
+    _lib.check(lib.vima_action_select_ex(_ptr(x), R, _ptr(u), ctypes.byref(opts), bounds_array(action_bounds), arr, _ptr(cont), _ptr(logp),
+                                         _ptr(ent), stream))
+    return package((*lead, S) if S > 1 else lead, idx, cont, logp, ent)
+
+
+def score_actions(logits: torch.Tensor, actions, *, temperature=None, top_k: int = 0, top_p: float = 1.0,
+                  action_bounds=None) -> ActionSelection:
+    """Log-probability of bins the caller already has: logits float32 [..., 700] on the GPU, `actions` {key: integer bins [..., 2|4]}
+    (clamped to [0, n)) -> ActionSelection whose `actions` are the given ones, with `log_prob` (-inf for a bin the filters removed),
+    `entropy` and `continuous` of the distribution `select_actions` samples from under the same controls. With the defaults this is
+    MultiCategorical.log_prob(actions) / .entropy() of the raw head."""
+    lead, x = _logits_arg(logits, "score_actions")
+    lib = _lib.load()
+    R = x.shape[0]
+    alead, idx = given_bins(actions, x.device)
+    if idx[0].shape[0] != R:
+        raise ValueError(f"actions must hold one row per row of logits ({R} rows), got leading dims {tuple(alead)}")
+    opts, temp = sample_opts(temperature, top_k, top_p, 1, lead, x.device, given=True)
+    _, cont, logp, ent = alloc_outputs(R, x.device)
+    arr = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in idx])
+    stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    _lib.check(lib.vima_action_select_ex(_ptr(x), R, None, ctypes.byref(opts), bounds_array(action_bounds), arr, _ptr(cont), _ptr(logp),
+                                         _ptr(ent), stream))
     return package(lead, idx, cont, logp, ent)

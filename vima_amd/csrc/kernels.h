@@ -200,6 +200,20 @@ struct ActSelectArgs {
   const float* b0[4] = {nullptr, nullptr, nullptr, nullptr};
 };
 int launch_act_select(const ActSelectArgs& a, bool is_bf16, hipStream_t st);
+// action selection with sampling controls (action_sample.hip, act_sample_kernel): sel as above with sel.R = R * S OUTPUT rows, output
+// row r * S + s reading logits row r and u[r * S + s]; temp f32 [R] (device, or null = 1; clamped to [1e-4, 1e4], NaN = 1) divides the
+// logits, top_k (<= 0 or >= n: off) and top_p (>= 1: off; > 0) truncate every segment (ranks by exact comparison, ties to the lower
+// index; top-p after top-k), log-probability and entropy are those of the truncated distribution. given: sel.idx are INPUTS (clamped
+// to [0, n), not written), nothing is selected and sel.u is ignored. With every control off: the outputs of launch_act_select, bit for bit
+struct ActSampleArgs {
+  ActSelectArgs sel;
+  const float* temp = nullptr;
+  int top_k = 0;
+  float top_p = 1.0f;
+  int S = 1;
+  int given = 0;
+};
+int launch_act_sample(const ActSampleArgs& p, bool is_bf16, hipStream_t st);
 // out[r, :] += table[sel[r / group]][:]   (obs_fusion end-effector term)
 int launch_add_row_table(float* out, int rows, int E, const float* table, const long long* sel, int group,
                          hipStream_t st);

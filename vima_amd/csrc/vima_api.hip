@@ -2723,6 +2723,86 @@ int vima_act(VimaHandle* h, const float* tokens, int Rn, const float* u, const f
   });
 }
 
+// VimaSampleOpts (NULL = defaults) into the kernel's argument block; the refusals of include/vima_hip.h, before any launch
+static int set_sample_opts(ActSampleArgs& p, const VimaSampleOpts* o, const char* who) {
+  if (!o) return 0;
+  if (!(o->top_p > 0.f)) return fail(std::string(who) + ": top_p must be > 0");
+  if (o->n_samples < 1) return fail(std::string(who) + ": n_samples must be >= 1");
+  if (o->given && o->n_samples != 1) return fail(std::string(who) + ": given actions take n_samples == 1");
+  p.temp = o->temperature; p.top_k = o->top_k; p.top_p = o->top_p; p.S = o->n_samples; p.given = o->given ? 1 : 0;
+  return 0;
+}
+
+int vima_action_select_ex(const float* logits, int Rn, const float* u, const VimaSampleOpts* opts, const float* bounds,
+                          int64_t* const idx[4], float* cont, float* log_prob, float* entropy, vima_stream_t stream) {
+  ActSampleArgs p;
+  if (!idx || !idx[0] || !idx[1] || !idx[2] || !idx[3]) return fail("vima_action_select_ex: null idx");
+  if (int e = set_sample_opts(p, opts, "vima_action_select_ex")) return e;
+  if (Rn <= 0) return 0;
+  if (!logits) return fail("vima_action_select_ex: null argument");
+  if ((long long)Rn * p.S > 0x7fffffffLL) return fail("vima_action_select_ex: R * n_samples exceeds 2^31 - 1");
+  // the launch goes to the device that owns the logits, as in vima_action_select
+  int cur_dev = 0, out_dev = 0;
+  hipPointerAttribute_t pa;
+  HIPCK(hipGetDevice(&cur_dev));
+  out_dev = cur_dev;
+  if (hipPointerGetAttributes(&pa, logits) == hipSuccess) out_dev = pa.device;
+  else (void)hipGetLastError();
+  struct DeviceGuard {
+    int back; bool active;
+    ~DeviceGuard() { if (active) (void)hipSetDevice(back); }
+  } guard{cur_dev, false};
+  if (out_dev != cur_dev) {
+    HIPCK(hipSetDevice(out_dev));
+    guard.active = true;
+  }
+  ActSelectArgs& s = p.sel;
+  s.logits = logits; s.u = u; s.R = Rn * p.S; set_bounds(s, bounds);
+  for (int k = 0; k < 4; ++k) s.idx[k] = (long long*)idx[k];
+  s.cont = cont; s.logp = log_prob; s.ent = entropy;
+  const int e = launch_act_sample(p, false, (hipStream_t)stream);
+  if (e) return fail(std::string("act_sample launch failed: ") + hipGetErrorString((hipError_t)e), e);
+  return 0;
+}
+
+int vima_act_ex(VimaHandle* h, const float* tokens, int Rn, const float* u, const VimaSampleOpts* opts, const float* bounds,
+                float* logits_out, int64_t* const idx[4], float* cont, float* log_prob, float* entropy, float* token,
+                vima_stream_t stream) {
+  if (!h) return fail("null handle");
+  if (!idx || !idx[0] || !idx[1] || !idx[2] || !idx[3]) return fail("vima_act_ex: null idx");
+  ActSampleArgs p;
+  if (int e = set_sample_opts(p, opts, "vima_act_ex")) return e;
+  if (!tokens) return fail("vima_act_ex: null argument");
+  if ((long long)Rn * p.S > 0x7fffffffLL) return fail("vima_act_ex: R * n_samples exceeds 2^31 - 1");
+  uint32_t bb[4] = {0, 0, 0, 0}, pb = 0;   // the VALUES of the bounds and of top_p are kernel arguments: part of the graph key
+  if (bounds) memcpy(bb, bounds, sizeof bb);
+  memcpy(&pb, &p.top_p, sizeof pb);
+  const std::string key = gkey("act_ex", {(long long)(uintptr_t)tokens, Rn, (long long)(uintptr_t)u, (long long)(uintptr_t)p.temp, p.S, p.top_k,
+                                          (long long)pb, p.given, bounds ? 1 : 0, (long long)bb[0], (long long)bb[1], (long long)bb[2],
+                                          (long long)bb[3], (long long)(uintptr_t)logits_out, (long long)(uintptr_t)idx[0],
+                                          (long long)(uintptr_t)idx[1], (long long)(uintptr_t)idx[2], (long long)(uintptr_t)idx[3],
+                                          (long long)(uintptr_t)cont, (long long)(uintptr_t)log_prob, (long long)(uintptr_t)entropy,
+                                          (long long)(uintptr_t)token});
+  return run_graphed(h, key, (hipStream_t)stream, [&](hipStream_t st) -> int {
+  if (int e = check_ready(h)) return e;
+  if (Rn <= 0) return 0;
+  const int Ro = Rn * p.S;
+  Run R{h, st};
+  float* logits = logits_out ? logits_out : R.ws<float>((size_t)Rn * kLogits);
+  void* t1 = token ? R.wsT((size_t)Ro * 1024) : nullptr;
+  if (R.err) return R.err;
+  if (action_head_run(R, tokens, Rn, logits)) return R.err;
+  ActSampleArgs q = p;
+  ActSelectArgs& s = q.sel;
+  s.logits = logits; s.u = u; s.R = Ro; set_bounds(s, bounds);
+  for (int k = 0; k < 4; ++k) { s.idx[k] = (long long*)idx[k]; s.w0[k] = h->act0[k].w0; s.b0[k] = h->act0[k].b0; }
+  s.cont = cont; s.logp = log_prob; s.ent = entropy; s.t1 = t1;
+  OTHER(R, launch_act_sample(q, h->bf16, R.st), "act_sample");
+  if (!token || R.err) return R.err;
+  return action_embed_tail(R, t1, Ro, token);
+  });
+}
+
 // ---------------------------------------------------------------------------------------------- operator-level
 __global__ void widen_kernel(const bf16_t* in, float* out, long long n) {
   long long i = (long long)blockIdx.x * 256 + threadIdx.x;

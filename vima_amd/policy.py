@@ -8,7 +8,8 @@ Mirrors the method surface, argument meaning, return shapes and error behaviour 
     forward_obs_token             vima_policy.py:242-259   -> vima_obs_encode
     forward_action_token          vima_policy.py:261-262   -> vima_action_embed
     forward_action_decoder        vima_policy.py:264-265   -> vima_action_head (+ MultiCategorical wrapper)
-    act                           (no reference counterpart: head + mode / sample + de-discretise + embed) -> vima_act
+    act                           (no reference counterpart: head + mode / sample + de-discretise + embed) -> vima_act / vima_act_ex
+    evaluate_actions              (no reference counterpart: head + log-probability of given bins + embed) -> vima_act_ex
     discretize_action             vima_policy.py:267-299
     _de_discretize_actions        vima_policy.py:301-322
     load_state_dict(strict=True)  vima/__init__.py:11-14   -> vima_set_param / vima_finalize_params
@@ -489,7 +490,8 @@ class VIMAPolicy(nn.Module):
         return out.view(*lead, self.embed_dim)
 
     def act(self, predicted_action_tokens: torch.Tensor, *, sample: bool = False, generator=None, uniforms=None,
-            action_bounds=None, return_logits: bool = False):
+            action_bounds=None, return_logits: bool = False, temperature=None, top_k: int = 0, top_p: float = 1.0,
+            n_samples: int = 1):
         """Predicted action tokens [..., E] -> `actions.ActionSelection` in ONE native call (vima_act), no host synchronisation:
         the action head, then per action dimension the mode (default; torch.argmax of the logits) or an inverse-CDF sample
         (`sample=True`: `uniforms` [..., 12] in [0, 1), drawn with torch.rand(R, 12, generator=generator) on the device when not
@@ -500,24 +502,61 @@ class VIMAPolicy(nn.Module):
                                                      rescaled and clamped like the reference loop (scripts/example.py:213-234)
             action_token  float32 [..., E]           forward_action_token(actions), bit for bit
             log_prob / entropy  {key: float32 [...]} dists[key].log_prob(actions[key]) / dists[key].entropy()
-            logits        float32 [..., 700] with return_logits=True (== action_logits(...)), else None."""
+            logits        float32 [..., 700] with return_logits=True (== action_logits(...)), else None.
+
+        Sampling controls (vima_act_ex; with all of them at their defaults the call is vima_act as before): `temperature` (a float
+        or a tensor broadcastable to the leading dims) divides the logits; `top_k` / `top_p` truncate every segment (top-p after
+        top-k; one value for all segments), and log_prob / entropy describe the truncated distribution; `n_samples` = S > 1 draws S
+        candidates per state from ONE pass of the action head: actions / continuous [..., S, 2|4], log_prob / entropy [..., S],
+        action_token [..., S, E], `uniforms` [..., S, 12]; logits stay [..., 700]."""
         from . import actions as _actions
         self._ready()
         dev = self._device
         lead = predicted_action_tokens.shape[:-1]
         t = predicted_action_tokens.to(device=dev, dtype=torch.float32).reshape(-1, self.embed_dim).contiguous()
         R = t.shape[0]
+        opts, temp = _actions.sample_opts(temperature, top_k, top_p, n_samples, lead, dev)
+        S = int(n_samples) if opts is not None else 1
+        Ro = R * max(S, 1)
         if uniforms is None and sample:
-            uniforms = torch.rand(R, _actions.N_DIMS, generator=generator, device=dev, dtype=torch.float32)
-        u = _actions.uniforms_arg(uniforms, R, dev)
-        idx, cont, logp, ent = _actions.alloc_outputs(R, dev)
-        token = torch.empty(R, self.embed_dim, dtype=torch.float32, device=dev)
+            uniforms = torch.rand(Ro, _actions.N_DIMS, generator=generator, device=dev, dtype=torch.float32)
+        u = _actions.uniforms_arg(uniforms, Ro, dev)
+        idx, cont, logp, ent = _actions.alloc_outputs(Ro, dev)
+        token = torch.empty(Ro, self.embed_dim, dtype=torch.float32, device=dev)
         logits = torch.empty(R, N_LOGITS, dtype=torch.float32, device=dev) if return_logits else None
         arr = (ctypes.c_void_p * 4)(*[x.data_ptr() for x in idx])
-        _lib.check(self._lib.vima_act(self._handle, _ptr(t), R, _ptr(u), _actions.bounds_array(action_bounds), _ptr(logits), arr,
-                                      _ptr(cont), _ptr(logp), _ptr(ent), _ptr(token), self._stream()))
-        return _actions.package(lead, idx, cont, logp, ent, token.view(*lead, self.embed_dim),
+        if opts is None:
+            _lib.check(self._lib.vima_act(self._handle, _ptr(t), R, _ptr(u), _actions.bounds_array(action_bounds), _ptr(logits), arr,
+                                          _ptr(cont), _ptr(logp), _ptr(ent), _ptr(token), self._stream()))
+        else:
+            _lib.check(self._lib.vima_act_ex(self._handle, _ptr(t), R, _ptr(u), ctypes.byref(opts), _actions.bounds_array(action_bounds),
+                                             _ptr(logits), arr, _ptr(cont), _ptr(logp), _ptr(ent), _ptr(token), self._stream()))
+        out_lead = (*lead, S) if S > 1 else lead
+        return _actions.package(out_lead, idx, cont, logp, ent, token.view(*out_lead, self.embed_dim),
                                 logits.view(*lead, N_LOGITS) if logits is not None else None)
+
+    def evaluate_actions(self, predicted_action_tokens: torch.Tensor, actions, *, temperature=None, top_k: int = 0, top_p: float = 1.0,
+                         action_bounds=None):
+        """Predicted action tokens [..., E] and the `actions` {key: integer bins [..., 2|4]} the caller already has (demonstrations,
+        stored rollouts, candidates) -> `actions.ActionSelection` in ONE native call (vima_act_ex with given bins): `log_prob` of
+        those bins (-inf for a bin the filters removed) and `entropy` of the distribution `act` samples from under the same
+        controls, `continuous`, and `action_token` == forward_action_token(actions); `actions` are the given ones (int64)."""
+        from . import actions as _actions
+        self._ready()
+        dev = self._device
+        lead = predicted_action_tokens.shape[:-1]
+        t = predicted_action_tokens.to(device=dev, dtype=torch.float32).reshape(-1, self.embed_dim).contiguous()
+        R = t.shape[0]
+        alead, idx = _actions.given_bins(actions, dev)
+        if idx[0].shape[0] != R:
+            raise ValueError(f"actions must hold one row per predicted token ({R} rows), got leading dims {tuple(alead)}")
+        opts, temp = _actions.sample_opts(temperature, top_k, top_p, 1, lead, dev, given=True)
+        _, cont, logp, ent = _actions.alloc_outputs(R, dev)
+        token = torch.empty(R, self.embed_dim, dtype=torch.float32, device=dev)
+        arr = (ctypes.c_void_p * 4)(*[x.data_ptr() for x in idx])
+        _lib.check(self._lib.vima_act_ex(self._handle, _ptr(t), R, None, ctypes.byref(opts), _actions.bounds_array(action_bounds), None,
+                                         arr, _ptr(cont), _ptr(logp), _ptr(ent), _ptr(token), self._stream()))
+        return _actions.package(lead, idx, cont, logp, ent, token.view(*lead, self.embed_dim))
 
     def discretize_action(self, action):
         """vima_policy.py:267-299 (training-side helper; mutates `action` like the reference)."""
