@@ -383,6 +383,30 @@ int vima_op_attention(VimaHandle* h, const float* q, const float* k, const float
  * q_off = 0, Lq = Lk is vima_op_attention mode 2, bit for bit. impl as above. */
 int vima_op_attention_window(VimaHandle* h, const float* q, const float* k, const float* v, const uint8_t* kmask, int B, int H, int Lq,
                              int Lk, int D, float scale, int impl, int q_off, float* out, vima_stream_t stream);
+/* The ViT front end's non-GEMM kernels, ONE launcher call each (additive, ABI version unchanged; tests/test_vit_front_gpu.py holds every output
+ * element against fp64). Conventions of vima_op_attention: fp32 device buffers in and out, q | k | v cast to the handle's operand type
+ * internally, the operand-type result widened back to fp32; the fp32 side inputs (cls, pos, g, b, the bbox weights) are read as they are.
+ * Whatever a launcher refuses, and every non-positive size or NULL buffer, comes back as an error with nothing written to `out`.
+ * ViT self-attention (nn.MultiheadAttention, head dim 32, scale 1/sqrt(32)) of M crops with S <= 16 tokens: qkv [M*S, 3W] (q | k | v of a
+ * token, head h at columns h*32) -> out [M*S, W]. impl 0 = the launcher's own choice (on a bf16 handle at S = 5, W = 768, heads = 24 the
+ * LDS-staged kernel unless VIMA_VIT_ATTN_LDS=0), 1 = the register kernel with the instantiation S asks for (8 scores for S <= 8, else 16),
+ * 2 = the register kernel's 16-score instantiation whatever S. The three are bit-identical where more than one applies. */
+int vima_op_vit_attention(VimaHandle* h, const float* qkv, int M, int S, int W, int heads, int impl, float* out, vima_stream_t stream);
+/* the last ViT block's form: only the cls query. q [M, W], kv [M*S, 2W] (k | v of every token), S <= 8 -> out [M, W]; the bits of row 0 of
+ * every crop of vima_op_vit_attention on the same values. */
+int vima_op_vit_attention_cls(VimaHandle* h, const float* q, const float* kv, int M, int S, int W, int heads, float* out, vima_stream_t stream);
+/* /255, (x - mean) / std and the im2col of the PxP stride-P conv: img u8 [M, 3, H, W] -> out [M*(H/P)*(W/P), 3*P*P], row = image, gy, gx,
+ * column = c, py, px. P a multiple of 16 that divides H and W. impl 0: (H, W, P) = (32, 32, 16) runs the object-crop kernel, anything else
+ * the rectangular one; impl 1: the rectangular kernel at every shape (bit-identical at the crop shape). */
+int vima_op_patchify(VimaHandle* h, const uint8_t* img, int M, int H, int W, int P, int impl, float* out, vima_stream_t stream);
+/* ln_pre((t == 0 && cls ? cls : patch row) + pos[t]) over width 768, eps 1e-5, written in the operand type (the path that rounds): pre
+ * [M*n_patch, 768], cls [768] or NULL (then token t is patch t), pos [S, 768], g, b [768] -> out [M*S, 768]; S - (cls ? 1 : 0) <= n_patch.
+ * impl 0: cls != NULL, S = 5, n_patch = 4 runs the object-crop kernel, anything else the rectangular one; impl 1: the rectangular kernel
+ * at every shape (bit-identical at the crop shape). */
+int vima_op_vit_embed(VimaHandle* h, const float* pre, const float* cls, const float* pos, const float* g, const float* b, int M, int S,
+                      int n_patch, int impl, float* out, vima_stream_t stream);
+/* first layer of the bbox MLP: relu(W [N, 4] . (bbox / [256, 128, 128, 256]) + b [N]); bbox i64 [R, 4] -> out [R, N]. */
+int vima_op_bbox_l1(VimaHandle* h, const int64_t* bbox, const float* W, const float* b, int R, int N, float* out, vima_stream_t stream);
 /* precision FP8: the calibrated activation scales (dequantisation scale = headroom x max |x| / 448, see VIMA_PRECISION_FP8) of group 0 the T5 stack [12 layers][4 sites:
  * stream before qkv, attention context, stream before wi, ReLU hidden], 1 the ViT [4 blocks][4 sites: ln_1 output, attention output,
  * ln_2 output, QuickGELU hidden], 2 the decoder's prompt K/V projection [1]; returns their number (0 before that group's calibrating

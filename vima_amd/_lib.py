@@ -106,6 +106,11 @@ PROTOTYPES = {
                                          ctypes.c_int, ctypes.c_int, c_f32, ctypes.c_int, ctypes.c_int, vp, vp]),
     "vima_op_attention_window": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                 c_f32, ctypes.c_int, ctypes.c_int, vp, vp]),
+    "vima_op_vit_attention": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),
+    "vima_op_vit_attention_cls": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),
+    "vima_op_patchify": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),
+    "vima_op_vit_embed": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),
+    "vima_op_bbox_l1": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]),
     "vima_t5_bucket": (ctypes.c_int, [ctypes.c_int]),
     "vima_fp8_e4m3_encode": (None, [vp, vp, c_i64]),
     "vima_set_option": (ctypes.c_int, [vp, ctypes.c_char_p, c_i64]),

@@ -1304,18 +1304,18 @@ inline AttnDev to_dev(const AttnArgs& a) {
 
 }  // namespace
 
-int launch_vit_attn(const void* qkv, void* out, int M, int S, int W, int heads, bool is_bf16, hipStream_t st, void* out8, float inv8) {
+int launch_vit_attn(const void* qkv, void* out, int M, int S, int W, int heads, bool is_bf16, hipStream_t st, void* out8, float inv8, int force) {
   if (M <= 0) return 0;
-  if (S > 16 || W / heads != 32 || W % heads || (out8 && !is_bf16)) return (int)hipErrorInvalidValue;
+  if (S <= 0 || S > 16 || heads <= 0 || W / heads != 32 || W % heads || (out8 && !is_bf16) || force < 0 || force > 2) return (int)hipErrorInvalidValue;
   static const bool lds_path = [] { const char* e = getenv("VIMA_VIT_ATTN_LDS"); return !(e && e[0] == '0'); }();
-  if (is_bf16 && S == VA_S && W == VA_W && heads == VA_H && lds_path) {   // by shape only, never by the number of crops
+  if (is_bf16 && S == VA_S && W == VA_W && heads == VA_H && lds_path && !force) {   // by shape only, never by the number of crops
     hipLaunchKernelGGL(vit_attn_lds_kernel, dim3((unsigned)((M + 1) / 2)), dim3(256), 2 * VA_S * VA_ROWB, st, (const bf16_t*)qkv, (bf16_t*)out, M,
                        (uint8_t*)out8, inv8);
     return (int)hipGetLastError();
   }
   const long long total = (long long)M * S * heads;
   const unsigned g = (unsigned)((total + 255) / 256);
-  if (S > 8) {   // 9 .. 16 tokens (the baseline policies' frames: cls + 8 patches): the same body with 16 score registers
+  if (S > 8 || force == 2) {   // 9 .. 16 tokens (the baseline policies' frames: cls + 8 patches): the same body with 16 score registers
     if (is_bf16) hipLaunchKernelGGL((vit_attn_kernel<bf16_t, 16>), dim3(g), dim3(256), 0, st, (const bf16_t*)qkv, (bf16_t*)out, total, S, W, heads, (uint8_t*)out8, inv8);
     else hipLaunchKernelGGL((vit_attn_kernel<float, 16>), dim3(g), dim3(256), 0, st, (const float*)qkv, (float*)out, total, S, W, heads);
     return (int)hipGetLastError();
@@ -1328,7 +1328,7 @@ int launch_vit_attn(const void* qkv, void* out, int M, int S, int W, int heads, 
 int launch_vit_attn_cls(const void* q, const void* kv, void* out, int M, int S, int W, int heads, bool is_bf16, hipStream_t st, void* out8,
                         float inv8) {
   if (M <= 0) return 0;
-  if (S > 8 || W / heads != 32 || W % heads || (out8 && !is_bf16)) return (int)hipErrorInvalidValue;
+  if (S <= 0 || S > 8 || heads <= 0 || W / heads != 32 || W % heads || (out8 && !is_bf16)) return (int)hipErrorInvalidValue;
   const long long total = (long long)M * heads;
   const unsigned g = (unsigned)((total + 255) / 256);
   if (is_bf16) hipLaunchKernelGGL(vit_attn_cls_kernel<bf16_t>, dim3(g), dim3(256), 0, st, (const bf16_t*)q, (const bf16_t*)kv, (bf16_t*)out, total, S, W, heads, (uint8_t*)out8, inv8);

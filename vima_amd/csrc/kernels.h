@@ -283,7 +283,10 @@ int launch_fill_u8(uint8_t* p, long long n, uint8_t v, hipStream_t st);
 // ---------------------------------------------------------------- attention
 // ViT: 5-token (S <= 8) multi-head attention on packed qkv T [M*S, 3*W] -> T [M*S, W]; head dim 32
 // out8 (bf16 mode): write the result as fp8 e4m3(value * inv8) [M*S, W] bytes INSTEAD of the operand-type output
-int launch_vit_attn(const void* qkv, void* out, int M, int S, int W, int heads, bool is_bf16, hipStream_t st, void* out8 = nullptr, float inv8 = 1.0f);
+// force (vima_op_vit_attention's A/B): 0 the launcher's own choice, 1 the register kernel with the instantiation S asks for (never the
+// LDS-staged one), 2 the register kernel's 16-score instantiation whatever S
+int launch_vit_attn(const void* qkv, void* out, int M, int S, int W, int heads, bool is_bf16, hipStream_t st, void* out8 = nullptr, float inv8 = 1.0f,
+                    int force = 0);
 // last ViT block: cls-token query only. q T [M, W], kv T [M*S, 2W] -> out T [M, W]
 int launch_vit_attn_cls(const void* q, const void* kv, void* out, int M, int S, int W, int heads, bool is_bf16, hipStream_t st,
                         void* out8 = nullptr, float inv8 = 1.0f);

@@ -2934,4 +2934,95 @@ int vima_op_attention_window(VimaHandle* h, const float* q, const float* k, cons
   return op_attention(h, q, k, v, kmask, nullptr, B, H, Lq, Lk, D, scale, ATTN_CAUSAL, impl, q_off, q_off + Lq, out, stream);
 }
 
+// ---- the ViT front end's non-GEMM kernels, one launcher call each (tests/test_vit_front_gpu.py). Same conventions as above: fp32 device
+// buffers in and out, operands cast to the handle's operand type in the arena, the operand-type result widened back.
+static int op_widen(Run& R, const void* oT, float* out, long long n) {
+  if (R.err) return R.err;
+  if (R.h->bf16) {
+    hipLaunchKernelGGL(widen_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, R.st, (const bf16_t*)oT, out, n);
+    return R.other((int)hipGetLastError(), "widen");
+  }
+  if (hipMemcpyAsync(out, oT, n * 4, hipMemcpyDeviceToDevice, R.st) != hipSuccess) return fail("widen: hipMemcpyAsync failed");
+  return 0;
+}
+
+static int op_begin(VimaHandle* h, const char* fn) {
+  if (!h) return fail(std::string(fn) + ": null handle");
+  HIPCK(hipSetDevice(h->device));
+  if (h->arena.reset()) return fail("workspace reset failed");
+  return 0;
+}
+
+int vima_op_vit_attention(VimaHandle* h, const float* qkv, int M, int S, int W, int heads, int impl, float* out, vima_stream_t stream) {
+  if (int e = op_begin(h, "vima_op_vit_attention")) return e;
+  if (!qkv || !out) return fail("vima_op_vit_attention: null argument");
+  if (M <= 0 || S <= 0 || W <= 0 || heads <= 0) return fail("vima_op_vit_attention: M, S, W and heads must be positive");
+  if (impl < 0 || impl > 2) return fail("vima_op_vit_attention: impl must be 0 (the launcher's choice), 1 (register kernel) or 2 (its 16-score instantiation)");
+  if (W % heads || W / heads != 32) return fail("vima_op_vit_attention: the head dim W / heads must be 32");
+  Run R{h, (hipStream_t)stream};
+  const long long rows = (long long)M * S;
+  void* qT = R.wsT((size_t)rows * 3 * W); void* oT = R.wsT((size_t)rows * W);
+  if (R.err) return R.err;
+  OTHER(R, launch_cast(qkv, qT, rows * 3 * W, h->bf16, R.st), "cast");
+  OTHER(R, launch_vit_attn(qT, oT, M, S, W, heads, h->bf16, R.st, nullptr, 1.0f, impl), "vima_op_vit_attention: vit_attn");
+  return op_widen(R, oT, out, rows * W);
+}
+
+int vima_op_vit_attention_cls(VimaHandle* h, const float* q, const float* kv, int M, int S, int W, int heads, float* out, vima_stream_t stream) {
+  if (int e = op_begin(h, "vima_op_vit_attention_cls")) return e;
+  if (!q || !kv || !out) return fail("vima_op_vit_attention_cls: null argument");
+  if (M <= 0 || S <= 0 || W <= 0 || heads <= 0) return fail("vima_op_vit_attention_cls: M, S, W and heads must be positive");
+  if (W % heads || W / heads != 32) return fail("vima_op_vit_attention_cls: the head dim W / heads must be 32");
+  Run R{h, (hipStream_t)stream};
+  const long long rows = (long long)M * S;
+  void* qT = R.wsT((size_t)M * W); void* kvT = R.wsT((size_t)rows * 2 * W); void* oT = R.wsT((size_t)M * W);
+  if (R.err) return R.err;
+  OTHER(R, launch_cast(q, qT, (long long)M * W, h->bf16, R.st), "cast");
+  OTHER(R, launch_cast(kv, kvT, rows * 2 * W, h->bf16, R.st), "cast");
+  OTHER(R, launch_vit_attn_cls(qT, kvT, oT, M, S, W, heads, h->bf16, R.st), "vima_op_vit_attention_cls: vit_attn_cls");
+  return op_widen(R, oT, out, (long long)M * W);
+}
+
+int vima_op_patchify(VimaHandle* h, const uint8_t* img, int M, int H, int W, int P, int impl, float* out, vima_stream_t stream) {
+  if (int e = op_begin(h, "vima_op_patchify")) return e;
+  if (!img || !out) return fail("vima_op_patchify: null argument");
+  if (M <= 0 || H <= 0 || W <= 0 || P <= 0) return fail("vima_op_patchify: M, H, W and P must be positive");
+  if (impl < 0 || impl > 1) return fail("vima_op_patchify: impl must be 0 (by shape) or 1 (the rectangular kernel)");
+  Run R{h, (hipStream_t)stream};
+  const long long n = (long long)M * 3 * H * W;   // = rows x 3 P^2 when P divides H and W (anything else is refused below)
+  void* oT = R.wsT((size_t)n);
+  if (R.err) return R.err;
+  if (H == 32 && W == 32 && P == 16 && impl == 0) OTHER(R, launch_patchify(img, oT, M, h->bf16, R.st), "vima_op_patchify: patchify");
+  else OTHER(R, launch_patchify_rect(img, oT, M, H, W, P, h->bf16, R.st), "vima_op_patchify: patchify_rect");
+  return op_widen(R, oT, out, n);
+}
+
+int vima_op_vit_embed(VimaHandle* h, const float* pre, const float* cls, const float* pos, const float* g, const float* b, int M, int S,
+                      int n_patch, int impl, float* out, vima_stream_t stream) {
+  if (int e = op_begin(h, "vima_op_vit_embed")) return e;
+  if (!pre || !pos || !g || !b || !out) return fail("vima_op_vit_embed: null argument");
+  if (M <= 0 || S <= 0 || n_patch <= 0) return fail("vima_op_vit_embed: M, S and n_patch must be positive");
+  if (impl < 0 || impl > 1) return fail("vima_op_vit_embed: impl must be 0 (by shape) or 1 (the rectangular kernel)");
+  if (S - (cls ? 1 : 0) > n_patch) return fail("vima_op_vit_embed: S tokens need S - (cls ? 1 : 0) <= n_patch patch rows per image");
+  Run R{h, (hipStream_t)stream};
+  const long long n = (long long)M * S * 768;
+  void* xT = R.wsT((size_t)n);
+  if (R.err) return R.err;
+  if (cls && S == 5 && n_patch == 4 && impl == 0) OTHER(R, launch_vit_embed(pre, cls, pos, g, b, nullptr, xT, M, h->bf16, R.st), "vima_op_vit_embed: vit_embed");
+  else OTHER(R, launch_vit_embed_rect(pre, cls, pos, g, b, nullptr, xT, M, S, n_patch, h->bf16, R.st), "vima_op_vit_embed: vit_embed_rect");
+  return op_widen(R, xT, out, n);
+}
+
+int vima_op_bbox_l1(VimaHandle* h, const int64_t* bbox, const float* W, const float* b, int R_, int N, float* out, vima_stream_t stream) {
+  if (int e = op_begin(h, "vima_op_bbox_l1")) return e;
+  if (!bbox || !W || !b || !out) return fail("vima_op_bbox_l1: null argument");
+  if (R_ <= 0 || N <= 0) return fail("vima_op_bbox_l1: R and N must be positive");
+  Run R{h, (hipStream_t)stream};
+  const long long n = (long long)R_ * N;
+  void* oT = R.wsT((size_t)n);
+  if (R.err) return R.err;
+  OTHER(R, launch_bbox_l1((const long long*)bbox, W, b, oT, R_, N, h->bf16, R.st), "vima_op_bbox_l1: bbox_l1");
+  return op_widen(R, oT, out, n);
+}
+
 }  // extern "C"
