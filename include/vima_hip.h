@@ -407,6 +407,76 @@ int vima_op_vit_embed(VimaHandle* h, const float* pre, const float* cls, const f
                       int n_patch, int impl, float* out, vima_stream_t stream);
 /* first layer of the bbox MLP: relu(W [N, 4] . (bbox / [256, 128, 128, 256]) + b [N]); bbox i64 [R, 4] -> out [R, N]. */
 int vima_op_bbox_l1(VimaHandle* h, const int64_t* bbox, const float* W, const float* b, int R, int N, float* out, vima_stream_t stream);
+/* The norm and sequence-assembly kernels (elementwise.hip, baseline_kernels.hip), ONE launcher call each (additive, ABI version unchanged;
+ * tests/test_seq_norm_gpu.py holds every output element against fp64 or, for the exact ones, bit for bit). Conventions of the block above.
+ * Buffers named x32 / out32 are written by the kernel in fp32; buffers named xT / outT / out2T receive the operand-type output widened to
+ * fp32 (bf16 handles: bf16-exact values). Index arrays (tok_src, word_ids, list, sel) are DEVICE arrays and are not validated, as on the hot
+ * path. State buffers (hist_mask, poscnt, fresh, cache_mask, posbase) are the caller's and are updated in place. A NULL required argument,
+ * a non-positive size or anything the launcher refuses is an error with no caller buffer written.
+ * vima_op_norm: kind VIMA_NORM_LN launch_layernorm (fp32 rows), VIMA_NORM_LN_T launch_layernorm_T (x cast to the operand type first: x holds
+ * rows * ldin elements), VIMA_NORM_LN2 launch_layernorm2 (y = LN(x; gamma, beta, eps) -> out32 / outT, LN(y; gamma2, beta2, eps2) -> out2T),
+ * VIMA_NORM_RMS_STATS launch_rms_stats (outT = x, ssq[r] = sum x[r][:]^2; ldin == E). rms = 1: T5 RMSNorm (beta NULL). out32 / outT optional
+ * where the launcher makes them so; the fp8 output of the launchers is not reachable here. */
+enum { VIMA_NORM_LN = 0, VIMA_NORM_LN_T = 1, VIMA_NORM_LN2 = 2, VIMA_NORM_RMS_STATS = 3 };
+typedef struct VimaNormDesc {
+  const float* x; const float* gamma; const float* beta; const float* gamma2; const float* beta2;
+  float* out32; float* outT; float* out2T; float* ssq;
+  int64_t ldin;
+  int32_t kind, rms, rows, E;
+  float eps, eps2;
+} VimaNormDesc;
+int vima_op_norm(VimaHandle* h, const VimaNormDesc* desc, vima_stream_t stream);
+/* row r: tok_src[r] >= 0 word_table[word_ids[tok_src[r]]], -1 zeros (mask 0), <= -2 object row -(v + 2) of obj_tokens / obj_mask -> x [rows, E],
+ * mask [rows]. stats = 0 launch_prompt_assemble (x fp32); stats = 1 launch_prompt_assemble_stats (x = the operand-type rows widened, ssq [rows]). */
+int vima_op_prompt_assemble(VimaHandle* h, const int32_t* tok_src, const int64_t* word_ids, const float* word_table, const float* obj_tokens,
+                            const uint8_t* obj_mask, int rows, int E, int stats, float* x, float* ssq, uint8_t* mask, vima_stream_t stream);
+/* launch_dec_embed: obs_tok [T, B, Q, E], obs_mask [T, B, Q], act_tok [L_act, B, E], pos_table [n_pos, E] -> x32 / xT (optional) [B, T Q + L_act, E],
+ * mask [B, T Q + L_act]; L_act = T or T - 1. */
+int vima_op_dec_embed(VimaHandle* h, const float* obs_tok, const uint8_t* obs_mask, const float* act_tok, const float* pos_table, int n_pos,
+                      int T, int B, int Q, int L_act, int E, float* x32, float* xT, uint8_t* mask, vima_stream_t stream);
+/* launch_dec_embed_step: obs_tok [B, Q, E], obs_mask [B, Q], act_tok [B, E] (has_act) -> x32 / xT (optional) [B, Q + has_act, E]; hist_mask
+ * [B, Lmax] rows [L_hist, L_hist + Q + has_act), poscnt [B] and fresh [B] (optional) are updated. */
+int vima_op_dec_embed_step(VimaHandle* h, const float* obs_tok, const uint8_t* obs_mask, const float* act_tok, const float* pos_table, int n_pos,
+                           int L_hist, int Lmax, int B, int Q, int has_act, int E, float* x32, float* xT, uint8_t* hist_mask, int32_t* poscnt,
+                           uint8_t* fresh, vima_stream_t stream);
+/* launch_restart_samples: samples with flags[b] != 0 get hist_mask[b][:] = 0, poscnt[b] = 0, fresh[b] = 1. */
+int vima_op_restart_samples(VimaHandle* h, const uint8_t* flags, uint8_t* hist_mask, int32_t* poscnt, uint8_t* fresh, int B, int Lmax,
+                            vima_stream_t stream);
+/* launch_prompt_pos: out block r [Lp, E] = prompt rows (element strides sb, sl) + pos_table[cumsum(mask) - 1] of sample list[r] (list NULL: r);
+ * mask [samples, Lp]. */
+int vima_op_prompt_pos(VimaHandle* h, const float* prompt, int64_t sb, int64_t sl, const uint8_t* mask, const float* pos_table, int n_pos,
+                       const int32_t* list, int B, int Lp, int E, float* out, vima_stream_t stream);
+/* launch_gather_pred: out [T, B, E] = x [B, Lq, E] rows (Q - 1) + (Q + 1) t. */
+int vima_op_gather_pred(VimaHandle* h, const float* x, int T, int B, int Q, int Lq, int E, float* out, vima_stream_t stream);
+/* launch_action_l1: relu(W [256, K] . (idx / bins) + b) -> columns [col0, col0 + 256) of out [R, ldo]; K = 2 bins (50, 100), K = 4 bins 50.
+ * `out` is read first (values exact in the operand type): the columns the kernel does not write come back unchanged. */
+int vima_op_action_l1(VimaHandle* h, const int64_t* idx, int K, const float* W, const float* b, int R, int ldo, int col0, float* out,
+                      vima_stream_t stream);
+/* launch_add_row_table: out [rows, E] += table[clamp(sel[r / group], 0, 1)], in place. */
+int vima_op_add_row_table(VimaHandle* h, float* out, int rows, int E, const float* table, const int64_t* sel, int group, vima_stream_t stream);
+/* The operand-type copies: `in` is cast to the operand type, `out` is read first like vima_op_action_l1's (blocks and rows the kernel does
+ * not write come back unchanged). rows_to_headmajor: in [L, N] -> out [N / D, L, D]. kv_scatter: in [n, L, N] -> block list[r] of out
+ * [n_blocks, L N], row-major (hm = 0) or head-major. seq_kv_store: in [n L, ld_in] columns [0, N) -> rows [0, L) of block list[r] (NULL: r)
+ * of out [n_blocks, Lmax, N]. broadcast_rows (fp32): out [rows, E] = src [period, E] rows r % period. */
+int vima_op_rows_to_headmajor(VimaHandle* h, const float* in, int L, int N, int D, float* out, vima_stream_t stream);
+int vima_op_kv_scatter(VimaHandle* h, const float* in, const int32_t* list, int n, int L, int N, int D, int hm, int n_blocks, float* out,
+                       vima_stream_t stream);
+int vima_op_seq_kv_store(VimaHandle* h, const float* in, int64_t ld_in, const int32_t* list, int n, int L, int N, int Lmax, int n_blocks,
+                         float* out, vima_stream_t stream);
+int vima_op_broadcast_rows(VimaHandle* h, const float* src, int64_t rows, int E, int period, float* out, vima_stream_t stream);
+/* The decoder-only sequence (launch_seq_embed, _prefill, _step, launch_seq_restart): prompt (element strides sb, sl), pmask [samples, Lp],
+ * sep [E], obs_tok [T, B, Q, E] / act_tok [T, B, E] (step: [B, Q, E] / [B, E]) -> x32 and xT (optional) [B, L, E] / [n, Lp + 1, E] /
+ * [B, Q + has_act, E], mask; cache_mask [samples, n_pos], posbase [samples], fresh [samples] are the episode state. */
+int vima_op_seq_embed(VimaHandle* h, const float* prompt, int64_t sb, int64_t sl, const uint8_t* pmask, const float* sep, const float* obs_tok,
+                      const float* act_tok, const float* pos_table, int n_pos, int B, int L, int Lp, int Q, int E, float* x32, float* xT,
+                      uint8_t* mask, vima_stream_t stream);
+int vima_op_seq_embed_prefill(VimaHandle* h, const float* prompt, int64_t sb, int64_t sl, const uint8_t* pmask, const float* sep,
+                              const float* pos_table, int n_pos, const int32_t* list, int n, int Lp, int E, float* x32, float* xT, uint8_t* mask,
+                              uint8_t* cache_mask, int32_t* posbase, vima_stream_t stream);
+int vima_op_seq_embed_step(VimaHandle* h, const float* obs_tok, const float* act_tok, const float* pos_table, int n_pos, int row0, int B, int Q,
+                           int has_act, int E, float* x32, float* xT, uint8_t* cache_mask, int32_t* posbase, uint8_t* fresh, vima_stream_t stream);
+int vima_op_seq_restart(VimaHandle* h, const int32_t* list, int n, int lo, int hi, int n_pos, uint8_t* cache_mask, uint8_t* fresh,
+                        vima_stream_t stream);
 /* precision FP8: the calibrated activation scales (dequantisation scale = headroom x max |x| / 448, see VIMA_PRECISION_FP8) of group 0 the T5 stack [12 layers][4 sites:
  * stream before qkv, attention context, stream before wi, ReLU hidden], 1 the ViT [4 blocks][4 sites: ln_1 output, attention output,
  * ln_2 output, QuickGELU hidden], 2 the decoder's prompt K/V projection [1]; returns their number (0 before that group's calibrating

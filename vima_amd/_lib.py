@@ -32,6 +32,15 @@ class VimaGemmDesc(ctypes.Structure):
                 [(n, c_f32) for n in ("rs_invk", "rs_eps")])
 
 
+class VimaNormDesc(ctypes.Structure):
+    """VimaNormDesc of include/vima_hip.h (vima_op_norm), same names, same order as the header."""
+    _fields_ = ([(n, vp) for n in ("x", "gamma", "beta", "gamma2", "beta2", "out32", "outT", "out2T", "ssq")] + [("ldin", c_i64)] +
+                [(n, c_i32) for n in ("kind", "rms", "rows", "E")] + [(n, c_f32) for n in ("eps", "eps2")])
+
+
+NORM_KIND = {"ln": 0, "ln_T": 1, "ln2": 2, "rms_stats": 3}   # VIMA_NORM_* (include/vima_hip.h)
+
+
 class VimaSampleOpts(ctypes.Structure):
     """VimaSampleOpts of include/vima_hip.h (vima_action_select_ex / vima_act_ex), same names, same order as the header."""
     _fields_ = [("temperature", vp), ("top_k", ctypes.c_int), ("top_p", c_f32), ("n_samples", ctypes.c_int), ("given", ctypes.c_int)]
@@ -111,6 +120,23 @@ PROTOTYPES = {
     "vima_op_patchify": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),
     "vima_op_vit_embed": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),
     "vima_op_bbox_l1": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]),
+    "vima_op_norm": (ctypes.c_int, [vp, ctypes.POINTER(VimaNormDesc), vp]),
+    "vima_op_prompt_assemble": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]),
+    "vima_op_dec_embed": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]),
+    "vima_op_dec_embed_step": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp]),
+    "vima_op_restart_samples": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp]),
+    "vima_op_prompt_pos": (ctypes.c_int, [vp, vp, c_i64, c_i64, vp, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),
+    "vima_op_gather_pred": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),
+    "vima_op_action_l1": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),
+    "vima_op_add_row_table": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, vp]),
+    "vima_op_rows_to_headmajor": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),
+    "vima_op_kv_scatter": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),
+    "vima_op_seq_kv_store": (ctypes.c_int, [vp, vp, c_i64, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),
+    "vima_op_broadcast_rows": (ctypes.c_int, [vp, vp, c_i64, ctypes.c_int, ctypes.c_int, vp, vp]),
+    "vima_op_seq_embed": (ctypes.c_int, [vp, vp, c_i64, c_i64, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]),
+    "vima_op_seq_embed_prefill": (ctypes.c_int, [vp, vp, c_i64, c_i64, vp, vp, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp]),
+    "vima_op_seq_embed_step": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp]),
+    "vima_op_seq_restart": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp]),
     "vima_t5_bucket": (ctypes.c_int, [ctypes.c_int]),
     "vima_fp8_e4m3_encode": (None, [vp, vp, c_i64]),
     "vima_set_option": (ctypes.c_int, [vp, ctypes.c_char_p, c_i64]),

@@ -411,8 +411,14 @@ __global__ __launch_bounds__(256) void prompt_assemble_kernel(const int* __restr
   if (lane == 0) mask[row] = m;
 }
 
+// Sum of squares of one float4 for the two entries of the fused-RMSNorm chain (prompt_assemble_stats_kernel, rms_stats_kernel), with the
+// fused multiply-adds SPELLED OUT. Written as (x*x + y*y) + (z*z + w*w) the contraction was the compiler's choice per kernel: it fused
+// fma(w, w, z*z) in one and fma(z, z, w*w) in the other, and the two ssq differed in the last bit on 4 of 27 rows at E = 320
+// (tests/test_seq_norm_gpu.py). This is the form prompt_assemble_stats_kernel had been compiled to.
+__device__ __forceinline__ float ssq4(const float4& v) { return fmaf(v.y, v.y, v.x * v.x) + fmaf(v.w, v.w, v.z * v.z); }
+
 // The same gather writing what the T5 stack's fused-RMSNorm chain starts from -- the operand-type copy of the row and its sum of squares
-// (rms_stats_kernel's output, same lane -> element mapping and the same summation order: identical bits) -- instead of the fp32 row: with the
+// (rms_stats_kernel's output, same lane -> element mapping, the same summation order and the same ssq4: identical bits) -- instead of the fp32 row: with the
 // residual stream carried in the operand type the fp32 prompt is never read again, so its 403-MB write and read (batch 256) disappear.
 template <typename T>
 __global__ __launch_bounds__(256) void prompt_assemble_stats_kernel(const int* __restrict__ tok_src, const long long* __restrict__ word_ids,
@@ -438,7 +444,7 @@ __global__ __launch_bounds__(256) void prompt_assemble_stats_kernel(const int* _
   for (int c = lane; c < nv; c += 64) {
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (src) v = *reinterpret_cast<const float4*>(src + c * 4);
-    q += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+    q += ssq4(v);
     store4(xT + (long long)row * E + c * 4, v);
   }
   q = wave_sum(q);
@@ -614,7 +620,7 @@ __global__ __launch_bounds__(256) void rms_stats_kernel(const float* __restrict_
   float q = 0.f;
   for (int c = lane; c < nv; c += 64) {
     const float4 v = *reinterpret_cast<const float4*>(x + c * 4);
-    q += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+    q += ssq4(v);
     store4(outT + (long long)row * E + c * 4, v);
   }
   q = wave_sum(q);

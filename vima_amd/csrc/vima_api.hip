@@ -3025,4 +3025,287 @@ int vima_op_bbox_l1(VimaHandle* h, const int64_t* bbox, const float* W, const fl
   return op_widen(R, oT, out, n);
 }
 
+// ---- the norm and sequence-assembly kernels of elementwise.hip / baseline_kernels.hip, one launcher call each (tests/test_seq_norm_gpu.py).
+// Same conventions: fp32 / integer device buffers in and out, operands cast to the operand type in the arena, ONE call of the launcher under
+// test, operand-type results widened back. Every check and every launcher refusal comes before the first write to a caller's buffer.
+// Index arrays (tok_src, word_ids, list, sel) live on the device and are NOT validated here, as on the hot path: the caller sizes the buffers.
+#define OP_REQ(cond, msg) do { if (!(cond)) return fail(std::string(fn) + ": " + (msg)); } while (0)
+
+// an operand-type buffer whose untouched elements must come back as the caller left them: the caller's fp32 `out` (values exact in the operand
+// type) is cast in before the launch and the whole buffer widened back after it
+static void* op_stage_out(Run& R, const float* out, long long n) {
+  void* oT = R.wsT((size_t)n);
+  if (R.err) return nullptr;
+  OTHER(R, launch_cast(out, oT, n, R.h->bf16, R.st), "cast");
+  return R.err ? nullptr : oT;
+}
+
+int vima_op_norm(VimaHandle* h, const VimaNormDesc* d, vima_stream_t stream) {
+  const char* fn = "vima_op_norm";
+  if (int e = op_begin(h, fn)) return e;
+  OP_REQ(d, "null descriptor");
+  OP_REQ(d->x && d->rows > 0 && d->E > 0, "x, rows and E are required");
+  OP_REQ(d->kind >= VIMA_NORM_LN && d->kind <= VIMA_NORM_RMS_STATS, "kind must be 0 (launch_layernorm), 1 (launch_layernorm_T), 2 (launch_layernorm2) or 3 (launch_rms_stats)");
+  Run R{h, (hipStream_t)stream};
+  const long long n = (long long)d->rows * d->E;
+  if (d->kind == VIMA_NORM_RMS_STATS) {
+    OP_REQ(d->outT && d->ssq, "rms_stats writes outT and ssq");
+    OP_REQ(d->ldin == d->E, "rms_stats reads dense rows (ldin == E)");
+    void* oT = R.wsT((size_t)n);
+    if (R.err) return R.err;
+    OTHER(R, launch_rms_stats(d->x, d->rows, d->E, oT, d->ssq, h->bf16, R.st), "vima_op_norm: rms_stats");
+    return op_widen(R, oT, d->outT, n);
+  }
+  OP_REQ(d->gamma, "gamma is required");
+  OP_REQ(d->ldin >= d->E, "ldin must be at least E");
+  const bool two = d->kind == VIMA_NORM_LN2;
+  OP_REQ(two || d->out32 || d->outT, "no output requested");
+  OP_REQ(!two || (d->gamma2 && d->out2T && !d->rms), "layernorm2 needs gamma2 and out2T and has no rms form");
+  void* oT = d->outT ? R.wsT((size_t)n) : nullptr;
+  void* o2T = two ? R.wsT((size_t)n) : nullptr;
+  if (R.err) return R.err;
+  if (d->kind == VIMA_NORM_LN_T) {
+    const long long nin = (long long)d->rows * d->ldin;   // the caller's buffer holds rows * ldin elements
+    void* xT = R.wsT((size_t)nin);
+    if (R.err) return R.err;
+    OTHER(R, launch_cast(d->x, xT, nin, h->bf16, R.st), "cast");
+    OTHER(R, launch_layernorm_T(xT, d->ldin, d->gamma, d->beta, d->eps, d->rms, d->rows, d->E, d->out32, oT, h->bf16, R.st), "vima_op_norm: layernorm_T");
+  } else if (two) {
+    OTHER(R, launch_layernorm2(d->x, d->ldin, d->gamma, d->beta, d->eps, d->gamma2, d->beta2, d->eps2, d->rows, d->E, d->out32, oT, o2T, h->bf16, R.st),
+          "vima_op_norm: layernorm2");
+  } else {
+    OTHER(R, launch_layernorm(d->x, d->ldin, d->gamma, d->beta, d->eps, d->rms, d->rows, d->E, d->out32, oT, h->bf16, R.st), "vima_op_norm: layernorm");
+  }
+  if (R.err) return R.err;
+  if (oT && op_widen(R, oT, d->outT, n)) return R.err ? R.err : 1;
+  return two ? op_widen(R, o2T, d->out2T, n) : 0;
+}
+
+int vima_op_prompt_assemble(VimaHandle* h, const int32_t* tok_src, const int64_t* word_ids, const float* word_table, const float* obj_tokens,
+                            const uint8_t* obj_mask, int rows, int E, int stats, float* x, float* ssq, uint8_t* mask, vima_stream_t stream) {
+  const char* fn = "vima_op_prompt_assemble";
+  if (int e = op_begin(h, fn)) return e;
+  OP_REQ(tok_src && word_ids && word_table && obj_tokens && obj_mask && x && mask && (ssq || !stats), "null argument");
+  OP_REQ(rows > 0 && E > 0, "rows and E must be positive");
+  Run R{h, (hipStream_t)stream};
+  if (!stats) {
+    OTHER(R, launch_prompt_assemble(tok_src, (const long long*)word_ids, word_table, obj_tokens, obj_mask, x, mask, rows, E, R.st), "vima_op_prompt_assemble: prompt_assemble");
+    return R.err;
+  }
+  void* xT = R.wsT((size_t)rows * E);
+  if (R.err) return R.err;
+  OTHER(R, launch_prompt_assemble_stats(tok_src, (const long long*)word_ids, word_table, obj_tokens, obj_mask, xT, ssq, mask, rows, E, h->bf16, R.st),
+        "vima_op_prompt_assemble: prompt_assemble_stats");
+  return op_widen(R, xT, x, (long long)rows * E);
+}
+
+int vima_op_dec_embed(VimaHandle* h, const float* obs_tok, const uint8_t* obs_mask, const float* act_tok, const float* pos_table, int n_pos,
+                      int T, int B, int Q, int L_act, int E, float* x32, float* xT, uint8_t* mask, vima_stream_t stream) {
+  const char* fn = "vima_op_dec_embed";
+  if (int e = op_begin(h, fn)) return e;
+  OP_REQ(obs_tok && obs_mask && pos_table && x32 && mask && (act_tok || L_act == 0), "null argument");
+  OP_REQ(T > 0 && B > 0 && Q > 0 && E > 0 && n_pos > 0, "T, B, Q, E and n_pos must be positive");
+  OP_REQ(L_act == T || L_act == T - 1, "L_act must be T or T - 1");
+  Run R{h, (hipStream_t)stream};
+  const long long n = (long long)B * (T * Q + L_act) * E;
+  void* oT = xT ? R.wsT((size_t)n) : nullptr;
+  if (R.err) return R.err;
+  OTHER(R, launch_dec_embed(obs_tok, obs_mask, act_tok, pos_table, n_pos, x32, oT, mask, T, B, Q, L_act, E, h->bf16, R.st), "vima_op_dec_embed: dec_embed");
+  return oT ? op_widen(R, oT, xT, n) : R.err;
+}
+
+int vima_op_dec_embed_step(VimaHandle* h, const float* obs_tok, const uint8_t* obs_mask, const float* act_tok, const float* pos_table, int n_pos,
+                           int L_hist, int Lmax, int B, int Q, int has_act, int E, float* x32, float* xT, uint8_t* hist_mask, int32_t* poscnt,
+                           uint8_t* fresh, vima_stream_t stream) {
+  const char* fn = "vima_op_dec_embed_step";
+  if (int e = op_begin(h, fn)) return e;
+  OP_REQ(obs_tok && obs_mask && pos_table && x32 && hist_mask && poscnt && (act_tok || !has_act), "null argument");
+  OP_REQ(B > 0 && Q > 0 && E > 0 && n_pos > 0 && L_hist >= 0 && (has_act == 0 || has_act == 1), "B, Q, E, n_pos must be positive, L_hist >= 0, has_act 0 or 1");
+  Run R{h, (hipStream_t)stream};
+  const long long n = (long long)B * (Q + has_act) * E;
+  void* oT = xT ? R.wsT((size_t)n) : nullptr;
+  if (R.err) return R.err;
+  OTHER(R, launch_dec_embed_step(obs_tok, obs_mask, act_tok, pos_table, n_pos, x32, oT, hist_mask, poscnt, L_hist, Lmax, B, Q, has_act, E, h->bf16, R.st, fresh),
+        "vima_op_dec_embed_step: dec_embed_step");
+  return oT ? op_widen(R, oT, xT, n) : R.err;
+}
+
+int vima_op_restart_samples(VimaHandle* h, const uint8_t* flags, uint8_t* hist_mask, int32_t* poscnt, uint8_t* fresh, int B, int Lmax, vima_stream_t stream) {
+  const char* fn = "vima_op_restart_samples";
+  if (int e = op_begin(h, fn)) return e;
+  OP_REQ(flags && hist_mask && poscnt && fresh, "null argument");
+  OP_REQ(B > 0 && Lmax > 0, "B and Lmax must be positive");
+  Run R{h, (hipStream_t)stream};
+  OTHER(R, launch_restart_samples(flags, hist_mask, poscnt, fresh, B, Lmax, R.st), "vima_op_restart_samples: restart_samples");
+  return R.err;
+}
+
+int vima_op_prompt_pos(VimaHandle* h, const float* prompt, int64_t sb, int64_t sl, const uint8_t* mask, const float* pos_table, int n_pos,
+                       const int32_t* list, int B, int Lp, int E, float* out, vima_stream_t stream) {
+  const char* fn = "vima_op_prompt_pos";
+  if (int e = op_begin(h, fn)) return e;
+  OP_REQ(prompt && mask && pos_table && out, "null argument");
+  OP_REQ(B > 0 && Lp > 0 && E > 0 && n_pos > 0, "B, Lp, E and n_pos must be positive");
+  Run R{h, (hipStream_t)stream};
+  const long long n = (long long)B * Lp * E;
+  void* oT = R.wsT((size_t)n);
+  if (R.err) return R.err;
+  OTHER(R, launch_prompt_pos(prompt, sb, sl, mask, pos_table, n_pos, oT, B, Lp, E, h->bf16, R.st, list), "vima_op_prompt_pos: prompt_pos");
+  return op_widen(R, oT, out, n);
+}
+
+int vima_op_gather_pred(VimaHandle* h, const float* x, int T, int B, int Q, int Lq, int E, float* out, vima_stream_t stream) {
+  const char* fn = "vima_op_gather_pred";
+  if (int e = op_begin(h, fn)) return e;
+  OP_REQ(x && out, "null argument");
+  OP_REQ(T > 0 && B > 0 && Q > 0 && E > 0 && E % 4 == 0, "T, B, Q must be positive, E a positive multiple of 4");
+  OP_REQ((Q - 1) + (long long)(Q + 1) * (T - 1) < Lq, "row Q - 1 of the last step lies beyond Lq");
+  Run R{h, (hipStream_t)stream};
+  OTHER(R, launch_gather_pred(x, out, T, B, Q, Lq, E, R.st), "vima_op_gather_pred: gather_pred");
+  return R.err;
+}
+
+int vima_op_action_l1(VimaHandle* h, const int64_t* idx, int K, const float* W, const float* b, int R_, int ldo, int col0, float* out,
+                      vima_stream_t stream) {
+  const char* fn = "vima_op_action_l1";
+  if (int e = op_begin(h, fn)) return e;
+  OP_REQ(idx && W && b && out, "null argument");
+  OP_REQ(K == 2 || K == 4, "K must be 2 (position) or 4 (rotation)");
+  OP_REQ(R_ > 0 && col0 >= 0 && col0 + 256 <= ldo && ldo % 4 == 0, "R must be positive and the 256 columns from col0 on lie inside ldo (a multiple of 4)");
+  Run R{h, (hipStream_t)stream};
+  const long long n = (long long)R_ * ldo;
+  void* oT = op_stage_out(R, out, n);
+  if (!oT) return R.err;
+  OTHER(R, launch_action_l1((const long long*)idx, K, W, b, oT, R_, ldo, col0, h->bf16, R.st), "vima_op_action_l1: action_l1");
+  return op_widen(R, oT, out, n);
+}
+
+int vima_op_add_row_table(VimaHandle* h, float* out, int rows, int E, const float* table, const int64_t* sel, int group, vima_stream_t stream) {
+  const char* fn = "vima_op_add_row_table";
+  if (int e = op_begin(h, fn)) return e;
+  OP_REQ(out && table && sel, "null argument");
+  OP_REQ(rows > 0 && E > 0 && group > 0, "rows, E and group must be positive");
+  Run R{h, (hipStream_t)stream};
+  OTHER(R, launch_add_row_table(out, rows, E, table, (const long long*)sel, group, R.st), "vima_op_add_row_table: add_row_table");
+  return R.err;
+}
+
+int vima_op_rows_to_headmajor(VimaHandle* h, const float* in, int L, int N, int D, float* out, vima_stream_t stream) {
+  const char* fn = "vima_op_rows_to_headmajor";
+  if (int e = op_begin(h, fn)) return e;
+  OP_REQ(in && out, "null argument");
+  OP_REQ(L > 0 && N > 0 && D > 0 && N % 4 == 0, "L, N and D must be positive, N a multiple of 4");
+  Run R{h, (hipStream_t)stream};
+  const long long n = (long long)L * N;
+  void* iT = R.wsT((size_t)n); void* oT = R.wsT((size_t)n);
+  if (R.err) return R.err;
+  OTHER(R, launch_cast(in, iT, n, h->bf16, R.st), "cast");
+  OTHER(R, launch_rows_to_headmajor(iT, oT, L, N, D, h->bf16, R.st), "vima_op_rows_to_headmajor: rows_to_headmajor");
+  return op_widen(R, oT, out, n);
+}
+
+int vima_op_kv_scatter(VimaHandle* h, const float* in, const int32_t* list, int n, int L, int N, int D, int hm, int n_blocks, float* out,
+                       vima_stream_t stream) {
+  const char* fn = "vima_op_kv_scatter";
+  if (int e = op_begin(h, fn)) return e;
+  OP_REQ(in && list && out, "null argument");
+  OP_REQ(n > 0 && L > 0 && N > 0 && D > 0 && n_blocks > 0 && N % 4 == 0, "n, L, N, D and n_blocks must be positive, N a multiple of 4");
+  Run R{h, (hipStream_t)stream};
+  const long long ni = (long long)n * L * N, no = (long long)n_blocks * L * N;
+  void* iT = R.wsT((size_t)ni);
+  if (R.err) return R.err;
+  OTHER(R, launch_cast(in, iT, ni, h->bf16, R.st), "cast");
+  void* oT = op_stage_out(R, out, no);
+  if (!oT) return R.err;
+  OTHER(R, launch_kv_scatter(iT, oT, list, n, L, N, D, hm, h->bf16, R.st), "vima_op_kv_scatter: kv_scatter");
+  return op_widen(R, oT, out, no);
+}
+
+int vima_op_seq_kv_store(VimaHandle* h, const float* in, int64_t ld_in, const int32_t* list, int n, int L, int N, int Lmax, int n_blocks,
+                         float* out, vima_stream_t stream) {
+  const char* fn = "vima_op_seq_kv_store";
+  if (int e = op_begin(h, fn)) return e;
+  OP_REQ(in && out, "null argument");
+  OP_REQ(n > 0 && L > 0 && N > 0 && Lmax > 0 && n_blocks > 0 && ld_in >= N && ld_in % 4 == 0 && N % 4 == 0,
+         "n, L, N, Lmax and n_blocks must be positive, ld_in >= N, ld_in and N multiples of 4");
+  Run R{h, (hipStream_t)stream};
+  const long long ni = (long long)n * L * ld_in, no = (long long)n_blocks * Lmax * N;
+  void* iT = R.wsT((size_t)ni);
+  if (R.err) return R.err;
+  OTHER(R, launch_cast(in, iT, ni, h->bf16, R.st), "cast");
+  void* oT = op_stage_out(R, out, no);
+  if (!oT) return R.err;
+  OTHER(R, launch_seq_kv_store(iT, ld_in, oT, list, n, L, N, Lmax, h->bf16, R.st), "vima_op_seq_kv_store: seq_kv_store");
+  return op_widen(R, oT, out, no);
+}
+
+int vima_op_broadcast_rows(VimaHandle* h, const float* src, int64_t rows, int E, int period, float* out, vima_stream_t stream) {
+  const char* fn = "vima_op_broadcast_rows";
+  if (int e = op_begin(h, fn)) return e;
+  OP_REQ(src && out, "null argument");
+  OP_REQ(rows > 0 && E > 0, "rows and E must be positive");
+  Run R{h, (hipStream_t)stream};
+  OTHER(R, launch_broadcast_rows(src, out, rows, E, period, R.st), "vima_op_broadcast_rows: broadcast_rows");
+  return R.err;
+}
+
+int vima_op_seq_embed(VimaHandle* h, const float* prompt, int64_t sb, int64_t sl, const uint8_t* pmask, const float* sep, const float* obs_tok,
+                      const float* act_tok, const float* pos_table, int n_pos, int B, int L, int Lp, int Q, int E, float* x32, float* xT,
+                      uint8_t* mask, vima_stream_t stream) {
+  const char* fn = "vima_op_seq_embed";
+  if (int e = op_begin(h, fn)) return e;
+  OP_REQ(prompt && pmask && sep && pos_table && x32 && mask, "null argument");
+  OP_REQ(B > 0 && Lp > 0 && Q > 0 && E > 0 && n_pos > 0 && L >= Lp + 1, "B, Lp, Q, E and n_pos must be positive and L >= Lp + 1");
+  OP_REQ(L == Lp + 1 || obs_tok, "rows past the separator need obs_tok");
+  OP_REQ(L - Lp - 1 <= Q || act_tok, "rows past the first step's observations need act_tok");
+  Run R{h, (hipStream_t)stream};
+  const long long n = (long long)B * L * E;
+  void* oT = R.wsT((size_t)n);
+  if (R.err) return R.err;
+  OTHER(R, launch_seq_embed(prompt, sb, sl, pmask, sep, obs_tok, act_tok, pos_table, n_pos, x32, oT, mask, B, L, Lp, Q, E, h->bf16, R.st), "vima_op_seq_embed: seq_embed");
+  return xT ? op_widen(R, oT, xT, n) : R.err;
+}
+
+int vima_op_seq_embed_prefill(VimaHandle* h, const float* prompt, int64_t sb, int64_t sl, const uint8_t* pmask, const float* sep,
+                              const float* pos_table, int n_pos, const int32_t* list, int n, int Lp, int E, float* x32, float* xT, uint8_t* mask,
+                              uint8_t* cache_mask, int32_t* posbase, vima_stream_t stream) {
+  const char* fn = "vima_op_seq_embed_prefill";
+  if (int e = op_begin(h, fn)) return e;
+  OP_REQ(prompt && pmask && sep && pos_table && x32 && mask && cache_mask && posbase, "null argument");
+  OP_REQ(n > 0 && Lp > 0 && E > 0 && n_pos > 0, "n, Lp, E and n_pos must be positive");
+  Run R{h, (hipStream_t)stream};
+  const long long ne = (long long)n * (Lp + 1) * E;
+  void* oT = R.wsT((size_t)ne);
+  if (R.err) return R.err;
+  OTHER(R, launch_seq_embed_prefill(prompt, sb, sl, pmask, sep, pos_table, n_pos, x32, oT, mask, cache_mask, posbase, list, n, Lp, E, h->bf16, R.st),
+        "vima_op_seq_embed_prefill: seq_embed_prefill");
+  return xT ? op_widen(R, oT, xT, ne) : R.err;
+}
+
+int vima_op_seq_embed_step(VimaHandle* h, const float* obs_tok, const float* act_tok, const float* pos_table, int n_pos, int row0, int B, int Q,
+                           int has_act, int E, float* x32, float* xT, uint8_t* cache_mask, int32_t* posbase, uint8_t* fresh, vima_stream_t stream) {
+  const char* fn = "vima_op_seq_embed_step";
+  if (int e = op_begin(h, fn)) return e;
+  OP_REQ(obs_tok && pos_table && x32 && cache_mask && posbase && fresh, "null argument");
+  OP_REQ(B > 0 && E > 0 && n_pos > 0 && (has_act == 0 || has_act == 1), "B, E and n_pos must be positive, has_act 0 or 1");
+  Run R{h, (hipStream_t)stream};
+  const long long n = (long long)B * (Q + has_act) * E;
+  void* oT = R.wsT((size_t)(n > 0 ? n : 1));
+  if (R.err) return R.err;
+  OTHER(R, launch_seq_embed_step(obs_tok, act_tok, pos_table, n_pos, x32, oT, cache_mask, posbase, fresh, row0, B, Q, has_act, E, h->bf16, R.st),
+        "vima_op_seq_embed_step: seq_embed_step");
+  return xT ? op_widen(R, oT, xT, n) : R.err;
+}
+
+int vima_op_seq_restart(VimaHandle* h, const int32_t* list, int n, int lo, int hi, int n_pos, uint8_t* cache_mask, uint8_t* fresh, vima_stream_t stream) {
+  const char* fn = "vima_op_seq_restart";
+  if (int e = op_begin(h, fn)) return e;
+  OP_REQ(list && cache_mask && fresh, "null argument");
+  OP_REQ(n > 0 && n_pos > 0, "n and n_pos must be positive");
+  Run R{h, (hipStream_t)stream};
+  OTHER(R, launch_seq_restart(list, n, cache_mask, fresh, lo, hi, n_pos, R.st), "vima_op_seq_restart: seq_restart");
+  return R.err;
+}
+#undef OP_REQ
+
 }  // extern "C"
