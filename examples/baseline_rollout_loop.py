@@ -2,12 +2,15 @@
 The prompt is a sequence PREFIX: `seq_prefill` runs it through the decoder once, every env step then feeds only its own tokens
 (`seq_step`) against the K/V cache in the native handle, instead of re-feeding [prompt | sep | o, a, o, a, ...] to `forward`.
 
-    python examples/baseline_rollout_loop.py [--policy gato] [--batch 32] [--steps 60]
+    python examples/baseline_rollout_loop.py [--policy gato] [--batch 32] [--steps 60] [--ring 1]
 
 Per env step: forward_obs_token -> seq_step -> act (action head, mode, action embedding in one native call). Episodes end at different
 steps; a finished sample is restarted with a new prompt (`seq_restart`: all flagged samples in one batched prefill) while the others
-keep their histories. The batch shares ONE row space of n_positions rows and a restart gives no rows back: when `steps_left()`
-reaches 0 the whole batch starts over with `seq_prefill`. Synthetic inputs stand in for the simulator.
+keep their histories. The batch shares ONE row space of n_positions rows. With `--ring 1` (the default; option "seq_ring") the rows behind
+the prompt are a ring and a restart gives the sample's rows back: the loop never calls `seq_prefill` again, and a sample whose
+`steps_left()` entry reaches 0 (its own episode would outgrow the ring) is restarted like a finished one. With `--ring 0` a restart
+gives no rows back: when `steps_left()` reaches 0 the whole batch starts over with `seq_prefill` and every in-flight episode is cut
+(Gato at this shape: every 18 env steps). Synthetic inputs stand in for the simulator.
 """
 import argparse
 import os
@@ -27,12 +30,14 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--prompts", type=int, default=3, help="encoded prompt batches the new episodes draw from")
+    ap.add_argument("--ring", type=int, default=1, choices=[0, 1], help="option seq_ring: the cache rows behind the prompt are a ring (1, default) or linear (0)")
     args = ap.parse_args()
     dev = "cuda:0"
     B = args.batch
     cfg = syn.BaselineConfig(args.policy, 768, 11, 12)
     policy = build_baseline(cfg, precision="bf16", device=dev)
     policy.load_state_dict(syn.make_baseline_state_dict(cfg, 0), strict=True)
+    policy.set_option("seq_ring", args.ring)
     # a real loop encodes the prompt of every new episode; here they come from a small pool (same layout -> same Lp)
     pool = []
     for k in range(args.prompts):
@@ -50,12 +55,15 @@ def main():
     for t in range(args.steps):
         if t > 0:
             flags = [age[b] >= length[b] for b in range(B)]
+            left = policy.steps_left().tolist()                                       # host bookkeeping only: no synchronisation
+            if args.ring:                                                             # a sample out of ring rows ends like a finished one
+                flags = [f or n == 0 for f, n in zip(flags, left)]
             for b in range(B):
                 if flags[b]:
                     episodes += 1
                     age[b], which[b] = 0, (which[b] + 1) % len(pool)
                     prompt_tokens[:, b], prompt_masks[b] = pool[which[b]][0][:, b], pool[which[b]][1][b]
-            if policy.steps_left()[0] == 0:                                           # host bookkeeping only: no synchronisation
+            if not args.ring and left[0] == 0:
                 # the shared row space is used up: every sample starts over. A simulator would finish the running episodes first (or re-feed
                 # their histories); the synthetic ones are simply cut here
                 policy.seq_prefill(prompt_tokens, prompt_masks)
@@ -70,7 +78,7 @@ def main():
         age = [a + 1 for a in age]
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) / args.steps * 1e3
-    print(f"{args.policy} batch {B}: {args.steps} env steps, {ms:.2f} ms per step including restarts; {episodes} episodes restarted, "
+    print(f"{args.policy} batch {B}, seq_ring {args.ring}: {args.steps} env steps, {ms:.2f} ms per step including restarts; {episodes} episodes restarted, "
           f"{resets} batch-wide prefills after steps_left() == 0; last action pose0_position = {sel.continuous['pose0_position'][0, 0].tolist()}")
 
 

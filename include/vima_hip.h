@@ -182,7 +182,8 @@ int vima_decode_restart(VimaHandle* h, const uint8_t* restart, int B, const floa
  * succeed if sample b ALONE were never restarted again (the row bookkeeping of vima_decode_step run forward; no device work, no state change).
  * Without option "decode_ring" the number is the same for every sample: the steps left before the whole batch must start over.
  * On a GPT / GATO handle the call reports the episode of vima_seq_prefill / vima_seq_decode_step: every entry is
- * floor((n_positions - rows used) / (Q + 1)) (before step 0, which feeds Q rows only: floor((n_positions - rows used + 1) / (Q + 1))). */
+ * floor((n_positions - rows used) / (Q + 1)) (before step 0, which feeds Q rows only: floor((n_positions - rows used + 1) / (Q + 1))).
+ * With option "seq_ring" the ring bookkeeping of vima_seq_decode_step is run forward per sample, as with "decode_ring" above. */
 int vima_decode_steps_left(VimaHandle* h, int B, int32_t* out_host);
 
 /* VIMAPolicy.forward_action_decoder (vima_policy.py:264-265 -> action_decoder.py:51-52,165-166): tokens f32 [R,E]
@@ -287,7 +288,7 @@ int vima_seq_decode(VimaHandle* h, const float* obs_tok, const float* act_tok, i
                     int64_t stride_b, int64_t stride_l, const uint8_t* prompt_mask, int Lp, float* out, vima_stream_t stream);
 
 /* ---- incremental decoding of the decoder-only policies (additive, ABI version unchanged; VIMA_POLICY_GPT / VIMA_POLICY_GATO handles only,
- * every other kind fails; not available with option "decode_ring") -------------------------------------------------------------------
+ * every other kind fails; option "decode_ring" is refused here: the ring of these policies is option "seq_ring", below) -----------------
  * The rollout form of vima_seq_decode: the prompt is a sequence PREFIX that is consumed once, every env step then feeds only its own rows
  * against a per-layer K | V cache [B][n_positions][2E] in the handle. HFGPT blocks are post-LN and act per row and the attention is causal,
  * so the cached prefix is exact: step t returns row t of vima_seq_decode on the whole history (L_act = T - 1) up to summation order.
@@ -311,7 +312,29 @@ int vima_seq_decode_step(VimaHandle* h, const float* obs_tok, const float* act_t
  * action slot becomes a masked row (zeros are embedded: that row of act_tok is never read) and rows [0, Lp] of every layer's cache are
  * rebuilt. All flagged samples are rebuilt together: one prefill of n_flagged x (Lp + 1) rows and one scatter per layer by sample list,
  * the same number of launches whatever n_flagged is. Lp must equal the episode's; rows of `prompt` of unflagged samples are not read. The
- * batch keeps ONE row index space: a restart does not give rows back (vima_decode_steps_left). */
+ * batch keeps ONE row index space: a restart does not give rows back (vima_decode_steps_left) -- unless that space is a ring:
+ *
+ * Option "seq_ring" = 1 (default 0: every call behaves bit for bit as described above; changing it ends a running episode) makes the rows
+ * behind the prefix a ring, for batches that never stop. Rows [0, P0), P0 = Lp + 1, of every sample's cache block stay the fixed prefix
+ * (prompt + separator; a restart rewrites them in place); rows [P0, n_positions) are the ring, R = n_positions - P0 rows, still ONE row index
+ * space for the whole batch. The host keeps wp (next row), hw (one past the highest row written since the prefill) and age[b] (ring rows
+ * advanced since sample b's episode began); vima_seq_prefill sets wp = hw = P0 and every age to 0. A step of Lq rows (Q at step 0 of the
+ * batch, Q + 1 afterwards) goes to row = wp and advances Lq rows, or, when wp + Lq > n_positions, to row = P0 and advances
+ * n_positions - wp + Lq rows (the tail is skipped: a step's rows are never split). The step is legal iff age[b] + advance <= R for every
+ * sample; otherwise it fails with code 34, names the first such sample, changes nothing, and succeeds once that sample has been restarted
+ * (vima_decode_steps_left tells in advance). On success age[b] += advance, wp = row + Lq, hw = max(hw, wp). `step` keeps its meaning
+ * (previous + 1) and is unbounded. The step's k | v go to rows [row, row + Lq) and its queries read the written image [0, hw) under the
+ * WINDOWED causal rule of vima_decode_step's ring (key j is "future" for the step's query i iff i + row < j < row + Lq; the rows from
+ * row + Lq on hold older history) and the cache's key mask; rows at and beyond hw were never written and are never read. In the first lap
+ * hw = row + Lq: the launches are those of the linear cache, bit for bit. vima_seq_decode_restart clears a flagged sample's key mask over the
+ * whole ring image [P0, hw), rebuilds its prefix and position base as above, takes no ring rows and sets age[b] = 0: the predictions of a
+ * sample depend on its own episode only and equal those of the linear cache up to the order of the softmax sums. Position ids stay the
+ * per-sample device counters and never reach the clamp of the position table: a sample's counter is at most Lp + 1 (prefix) plus one per
+ * ring row of its episode, and those rows are at most age[b] <= R, so posbase <= Lp + 1 + age <= n_positions and every id used is below
+ * n_positions. A sample's own episode is thus bounded by n_positions tokens, as in vima_seq_decode. With option "graphs" the key also
+ * carries hw; one eager step with an action slot warms the whole family and every (row, hw) is captured when first seen. From the second
+ * lap on every step has Q + 1 rows starting at P0, so the rows repeat exactly and the set of graphs stops growing one lap after hw has
+ * stopped moving. */
 int vima_seq_decode_restart(VimaHandle* h, const uint8_t* restart, int B, const float* prompt, int64_t stride_b, int64_t stride_l,
                             const uint8_t* prompt_mask, int Lp, vima_stream_t stream);
 
@@ -539,6 +562,9 @@ int vima_t5_bucket(int relative_position);
  *                                               the operand is then bf16(a) instead of bf16(LN(a)): same precision class, different rounding point
  *   rollouts:                "decode_ring"  [0] the episode caches' shared row index space is a ring (vima_decode_step): a batch steps without bound as long as
  *                                               every sample is restarted before ITS episode exceeds n_positions rows; setting it ends a running episode
+ *                            "seq_ring"     [0] the same for the decoder-only policies (vima_seq_prefill / vima_seq_decode_step / vima_seq_decode_restart on GPT /
+ *                                               GATO handles, where "decode_ring" is refused): the rows behind the prompt prefix are a ring and a restart gives a
+ *                                               sample's rows back; setting it ends a running episode
  *                            "restart_batched" [1] vima_decode_restart rebuilds the prompt K / V of all flagged samples together (prompts of more than 32
  *                                               tokens); 0 = one sample at a time: same bits, launches proportional to the number of flagged samples
  *   scheduling:              "dual_stream"  [1] independent halves of the work on an auxiliary HIP stream

@@ -180,7 +180,9 @@ class _BaselinePolicy(VIMAPolicy):
     def seq_prefill(self, prompt_token, prompt_token_mask):
         """Start an episode batch of incremental decoding (no reference counterpart: its loop re-feeds the whole sequence to `forward`
         every env step): prompt_token [Lp, B, E] + the separator run through the stack ONCE and every layer's K/V stay in the native
-        handle. Then call `seq_step` once per env step. A sample without any valid prompt token is refused like in `forward`."""
+        handle. Then call `seq_step` once per env step. A sample without any valid prompt token is refused like in `forward`.
+        With `set_option("seq_ring", 1)` the cache rows behind the prompt + separator are a ring (see `seq_restart`); the prefill is then
+        needed once per batch, not once per n_positions rows."""
         self._seq_only("seq_prefill")
         prompt_token, prompt_token_mask = self._seq_prompt(prompt_token, prompt_token_mask)
         if not bool(prompt_token_mask.any(dim=1).all()):
@@ -193,7 +195,10 @@ class _BaselinePolicy(VIMAPolicy):
     def seq_step(self, obs_token, prev_action_token=None):
         """One env step of the episode batch started by `seq_prefill`: obs_token [B, Q, E] ([B, E] or [B, 1, E] for GPT) and, from the
         second step on, the embedded action of the previous step [B, E]. The step number is kept here. Returns the predicted action
-        token [B, E] == forward(<full history>)[step]. IndexError when the sequence would exceed n_positions, like `forward`."""
+        token [B, E] == forward(<full history>)[step]. IndexError when the sequence would exceed n_positions, like `forward`.
+        With option `seq_ring` the step number is unbounded; IndexError then names the first sample whose OWN episode would exceed the
+        ring (n_positions - Lp - 1 rows, skipped tail rows included), nothing changes, and the step succeeds once that sample has been
+        restarted. `steps_left()` tells in advance."""
         self._seq_only("seq_step")
         Q, E = self._obj_xf_num_queries, self.embed_dim
         if obs_token.dim() == 2:
@@ -225,7 +230,9 @@ class _BaselinePolicy(VIMAPolicy):
         prompt from `prompt_token[:, b]` / `prompt_token_mask[b]` (same [Lp, B, E] / [B, Lp] layout and the same Lp as `seq_prefill`;
         other samples' rows are not read) and its next `seq_step` ignores its row of `prev_action_token`. All flagged samples are
         rebuilt in one batched prefill. The batch keeps stepping with `seq_step`; a restart does not give cache rows back
-        (`steps_left`): when they run out, start over with `seq_prefill`."""
+        (`steps_left`): when they run out, start over with `seq_prefill` -- unless option `seq_ring` is set: the restarted samples' rows
+        then return to the ring, a restart takes no rows itself, and a batch whose samples are each restarted before their
+        `steps_left()` entry reaches 0 never calls `seq_prefill` again (`decode_ring` is VIMAPolicy's ring and is refused here)."""
         self._seq_only("seq_restart")
         prompt_token, prompt_token_mask = self._seq_prompt(prompt_token, prompt_token_mask)
         flags = torch.as_tensor(restart).to(dtype=torch.uint8, device="cpu").contiguous()
@@ -238,7 +245,8 @@ class _BaselinePolicy(VIMAPolicy):
                                                      prompt_token.stride(1), prompt_token.stride(0), _ptr(prompt_token_mask), Lp, self._stream()))
 
     # steps_left() is VIMAPolicy's: on a gpt / gato handle vima_decode_steps_left reports the episode of seq_prefill / seq_step (all entries
-    # equal: how many further seq_step calls fit into n_positions)
+    # equal: how many further seq_step calls fit into n_positions; with option seq_ring per sample: how many more would succeed if that sample
+    # alone were never restarted)
 
 
 class VIMAGPTPolicy(_BaselinePolicy):

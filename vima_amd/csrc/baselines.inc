@@ -195,7 +195,9 @@ int hfgpt_stack(Run& R, float* x32, void* xT, const uint8_t* mask, int B, int L,
 // rows [row, row + Lq) of every sample. c_attn appends their k | v to the layer's cache through the GEMM's row-remap epilogue (row b Lq + i ->
 // b Lmax + row + i; one launch with the q columns dense where decode_launch has that form, two otherwise) and the new queries attend to
 // [0, row + Lq) with the causal offset `row` and the cache's key mask. Everything after the attention acts per row, as in hfgpt_stack.
-int hfgpt_step_stack(Run& R, float* x32, void* xT, int B, int Lq, int row, int Lmax) {
+// Lk / win_end: the keys read and the end of the causal window -- row + Lq / 0 (the plain rule) for the linear cache; with option seq_ring the
+// written image [0, hw) and row + Lq: the rows from win_end on hold OLDER history of the ring, which stays visible (AttnArgs::win_end).
+int hfgpt_step_stack(Run& R, float* x32, void* xT, int B, int Lq, int row, int Lmax, int Lk, int win_end) {
   VimaHandle* h = R.h;
   const int E = h->cfg.embed_dim, Hs = h->cfg.sattn_n_heads, rq = B * Lq;
   void* q = R.wsT((size_t)rq * E);
@@ -228,7 +230,7 @@ int hfgpt_step_stack(Run& R, float* x32, void* xT, int B, int Lq, int row, int L
     }
     AttnArgs s;
     s.q = q; s.ldq = E; s.k = cache; s.ldk = 2 * E; s.v = R.offT(cache, E); s.ldv = 2 * E;
-    s.out = ctx; s.ldo = E; s.B = B; s.H = Hs; s.Lq = Lq; s.Lk = row + Lq; s.Lk_rows = Lmax; s.q_off = row; s.D = E / Hs;
+    s.out = ctx; s.ldo = E; s.B = B; s.H = Hs; s.Lq = Lq; s.Lk = Lk; s.Lk_rows = Lmax; s.q_off = row; s.win_end = win_end; s.D = E / Hs;
     s.kmask = h->ep_mask; s.scale = 1.0f / sqrtf((float)(E / Hs)); s.mode = ATTN_CAUSAL;
     R.attn(s, h->attn_impl);
     R.linear(ctx, E, D.c_proj, rq, ACT_NONE, nullptr, 0, x32, E, a32, E, nullptr, 0);   // x + a

@@ -232,6 +232,11 @@ struct VimaHandle {
   // ep_fresh and ep_B / ep_Q / ep_Lp / ep_Lmax are theirs): seq_next = the step number the next call must carry, seq_row = cache rows in use
   // (Lp + 1 + the rows of the steps so far) = the row the next step writes at
   bool seq_live = false; int seq_next = 0, seq_row = 0;
+  // option "seq_ring": rows [P0, Lmax), P0 = ep_Lp + 1, of that row space are a ring behind the fixed prefix [0, P0) (prompt + separator, which a restart
+  // rewrites in place). seq_row is then the ring's write pointer, seq_hw = one past the highest row written since the prefill (rows beyond it hold
+  // hipMalloc garbage and are never read), seq_age[b] = ring rows advanced (skipped tail rows included) since sample b's episode began
+  int seq_ring = 0, seq_hw = 0;
+  std::vector<int> seq_age;
   // option "decode_ring": the ONE row index space of the episode caches is a ring. Host bookkeeping (decode_prepare plans, decode_commit stores):
   // ring_wp = next row to write, ring_hw = one past the highest row written since step 0 (rows beyond it hold hipMalloc garbage and are never
   // read), ring_age[b] = ring rows advanced (skipped tail rows included) since sample b's episode began
@@ -1802,6 +1807,7 @@ int vima_set_option(VimaHandle* h, const char* key, int64_t value) {
   else if (k == "ln_fuse") h->ln_fuse = (int)value;
   else if (k == "kv_headmajor") { h->kv_headmajor = (int)value; h->kv_valid = false; h->ep_step = -1; }   // the next decode rebuilds the cache in the chosen layout; a running episode (vima_decode_step) ends: start a new one with step 0
   else if (k == "decode_ring") { h->decode_ring = value != 0; h->ep_step = -1; h->seq_live = false; }   // a running episode (vima_decode_step) ends: start a new one with step 0
+  else if (k == "seq_ring") { h->seq_ring = value != 0; h->seq_live = false; }   // a running episode (vima_seq_decode_step) ends: start a new one with vima_seq_prefill
   else if (k == "restart_batched") h->restart_batched = (int)value;
   else if (k == "t5_fuse_rms") h->t5_fuse_rms = (int)value;
   else if (k == "stream_T") h->stream_T = (int)value;
@@ -2006,6 +2012,8 @@ struct DecodePlan { bool inc; int has_act, row, Lq, Lmax, kv_mode, Lk, win_end; 
 // fit, the tail [wp, Lmax) is skipped (and counts as advanced) and the rows go to [0, Lq).
 struct RingStep { int row, advance; };
 static RingStep ring_next(int wp, int Lq, int Lmax) { return wp + Lq > Lmax ? RingStep{0, Lmax - wp + Lq} : RingStep{wp, Lq}; }
+// The same for the ring [P0, Lmax) behind a fixed prefix (option seq_ring of the decoder-only policies): the rows go to [P0, P0 + Lq) after a skipped tail.
+static RingStep seq_ring_next(int wp, int Lq, int P0, int Lmax) { return wp + Lq > Lmax ? RingStep{P0, Lmax - wp + Lq} : RingStep{wp, Lq}; }
 
 // The episode caches for B samples of Lmax rows: per-layer self-attention K | V [layer][B][Lmax][2E], key mask [B][Lmax], position counter and
 // restart flag [B]. Grown (never shrunk) on demand; a reallocation invalidates the captured graphs.
@@ -2418,6 +2426,19 @@ int vima_decode_steps_left(VimaHandle* h, int B, int32_t* out_host) {
   if (h->cfg.policy_kind == VIMA_POLICY_GPT || h->cfg.policy_kind == VIMA_POLICY_GATO) {   // the episode of vima_seq_prefill / vima_seq_decode_step
     if (!(h->seq_live && h->ep_B == B))
       return fail("vima_decode_steps_left: no running episode batch of this size (start one with vima_seq_prefill)");
+    if (h->seq_ring) {   // the bookkeeping of vima_seq_decode_step run forward, per sample
+      const int P0 = h->ep_Lp + 1, Lmax = h->ep_Lmax;
+      for (int b = 0; b < B; ++b) {
+        int n = 0, wp = h->seq_row, age = h->seq_age[b], Lq = h->ep_Q + (h->seq_next == 0 ? 0 : 1);
+        for (;;) {
+          const RingStep rs = seq_ring_next(wp, Lq, P0, Lmax);
+          if (age + rs.advance > Lmax - P0) break;
+          age += rs.advance; wp = rs.row + Lq; Lq = h->ep_Q + 1; ++n;
+        }
+        out_host[b] = n;
+      }
+      return 0;
+    }
     // every step takes Q + 1 rows (after a restart the action slot is a masked row), except step 0 of the batch: Q
     const int left = h->ep_Lmax - h->seq_row + (h->seq_next == 0 ? 1 : 0);
     for (int b = 0; b < B; ++b) out_host[b] = left / (h->ep_Q + 1);
@@ -2570,12 +2591,13 @@ int vima_seq_prefill(VimaHandle* h, const float* prompt, int64_t stride_b, int64
                                     h->ep_poscnt, nullptr, B, Lp, E, h->bf16, R.st), "seq_embed_prefill");
   if (hfgpt_stack(R, x32, xT, mask, B, L, h->ep_kv, nullptr, B, Lmax)) return R.err;
   h->seq_live = true; h->seq_next = 0; h->seq_row = L;
+  h->seq_hw = L; h->seq_age.assign((size_t)B, 0);   // option seq_ring: write pointer (seq_row) = high-water mark = P0, every age 0
   h->ep_B = B; h->ep_Q = rgb_tokens_per_image(h->cfg.policy_kind); h->ep_Lp = Lp; h->ep_Lmax = Lmax;
   return 0;
 }
 
-static int seq_step_launch(VimaHandle* h, const float* obs_tok, const float* act_tok, int B, int Q, int has_act, int row, float* out,
-                           hipStream_t stream) {
+static int seq_step_launch(VimaHandle* h, const float* obs_tok, const float* act_tok, int B, int Q, int has_act, int row, int Lk, int win_end,
+                           float* out, hipStream_t stream) {
   if (int e = check_ready(h)) return e;
   const int E = h->cfg.embed_dim, Lmax = h->ep_Lmax, Lq = Q + has_act;
   Run R{h, stream};
@@ -2584,7 +2606,7 @@ static int seq_step_launch(VimaHandle* h, const float* obs_tok, const float* act
   if (R.err) return R.err;
   OTHER(R, launch_seq_embed_step(obs_tok, act_tok, h->pos_emb, Lmax, x32, xT, h->ep_mask, h->ep_poscnt, h->ep_fresh, row, B, Q, has_act, E,
                                  h->bf16, R.st), "seq_embed_step");
-  if (hfgpt_step_stack(R, x32, xT, B, Lq, row, Lmax)) return R.err;
+  if (hfgpt_step_stack(R, x32, xT, B, Lq, row, Lmax, Lk, win_end)) return R.err;
   OTHER(R, launch_gather_pred(x32, out, 1, B, Lq, Lq, E, R.st), "gather_pred");   // the last new row of every sample
   return R.err;
 }
@@ -2597,16 +2619,42 @@ int vima_seq_decode_step(VimaHandle* h, const float* obs_tok, const float* act_t
     return fail("vima_seq_decode_step: step " + std::to_string(step) + " of " + std::to_string(B) + " samples does not continue the episode state (" +
                 (h->seq_live ? "next step " + std::to_string(h->seq_next) + " of " + std::to_string(h->ep_B) + " samples" : std::string("no episode")) +
                 "); start an episode with vima_seq_prefill");
-  const int has_act = step > 0 ? 1 : 0, Q = h->ep_Q, Lq = Q + has_act, row = h->seq_row;
+  const int has_act = step > 0 ? 1 : 0, Q = h->ep_Q, Lq = Q + has_act, Lmax = h->ep_Lmax;
+  const bool ring = h->seq_ring != 0;
   if (has_act && !act_tok) return fail("vima_seq_decode_step: the previous action token is required for step > 0");
-  if (row + Lq > h->ep_Lmax)
-    return fail("vima_seq_decode_step: sequence of " + std::to_string(row + Lq) + " tokens exceeds n_positions " + std::to_string(h->ep_Lmax), 34);
+  // row: first cache row this call writes; Lk / win_end: keys the self-attention reads and the end of its causal window (0: the plain rule)
+  int row = h->seq_row, Lk = row + Lq, win_end = 0, advance = Lq;
+  if (!ring) {
+    if (row + Lq > Lmax)
+      return fail("vima_seq_decode_step: sequence of " + std::to_string(row + Lq) + " tokens exceeds n_positions " + std::to_string(Lmax), 34);
+  } else {   // legal iff every ring row about to be overwritten or skipped is dead for every sample
+    const int P0 = h->ep_Lp + 1;
+    const RingStep rs = seq_ring_next(h->seq_row, Lq, P0, Lmax);
+    for (int b = 0; b < B; ++b)
+      if (h->seq_age[b] + rs.advance > Lmax - P0)
+        return fail("vima_seq_decode_step: the episode of sample " + std::to_string(b) + " is longer than the ring behind its prompt (" +
+                    std::to_string(h->seq_age[b]) + " + " + std::to_string(rs.advance) + " ring rows > n_positions " + std::to_string(Lmax) + " - " +
+                    std::to_string(P0) + "): restart it with vima_seq_decode_restart", 34);
+    row = rs.row; advance = rs.advance; win_end = row + Lq;
+    Lk = h->seq_hw > win_end ? h->seq_hw : win_end;
+  }
+  // ring mode: the launch sequence depends on (write pointer, keys read, action slot), not on the step number -- from the second lap on every step
+  // has Q + 1 rows and the write pointers repeat, so the set of captured graphs stays bounded however long the rollout runs ...
   const std::string key = gkey("seq_step", {(long long)(uintptr_t)obs_tok, (long long)(uintptr_t)act_tok, (long long)(uintptr_t)out, B, row, has_act,
-                                            (long long)(uintptr_t)h->ep_kv});
+                                            (long long)(uintptr_t)h->ep_kv, Lk, win_end});
+  // ... and one eager step with an action slot warms all of them (same shapes, same workspace, same kernels: the attention launcher picks by Lk < 64 / >= 64):
+  // each (write pointer, keys read) is captured when first seen
+  const std::string warm = ring && has_act ? gkey("seq_step_ring", {B, Lk >= 64 ? 1 : 0}) : std::string();
   const int rc = run_graphed(h, key, (hipStream_t)stream, [&](hipStream_t st) {
-    return seq_step_launch(h, obs_tok, has_act ? act_tok : nullptr, B, Q, has_act, row, out, st);
-  });
-  if (!rc) { h->seq_next = step + 1; h->seq_row = row + Lq; }
+    return seq_step_launch(h, obs_tok, has_act ? act_tok : nullptr, B, Q, has_act, row, Lk, win_end, out, st);
+  }, warm);
+  if (!rc) {
+    h->seq_next = step + 1; h->seq_row = row + Lq;
+    if (ring) {
+      for (int& a : h->seq_age) a += advance;
+      h->seq_hw = Lk;
+    }
+  }
   return rc;
 }
 
@@ -2631,10 +2679,13 @@ int vima_seq_decode_restart(VimaHandle* h, const uint8_t* restart, int B, const 
   uint8_t* mask = R.ws<uint8_t>((size_t)n_r * L);
   if (R.err) return R.err;
   HIPCK(hipMemcpyAsync(list, h->restart_list.data(), (size_t)n_r * sizeof(int), hipMemcpyHostToDevice, R.st));
-  OTHER(R, launch_seq_restart(list, n_r, h->ep_mask, h->ep_fresh, L, h->seq_row, Lmax, R.st), "seq_restart");
+  // ring mode: the sample's history may lie anywhere in the written part [P0, hw) of the ring
+  OTHER(R, launch_seq_restart(list, n_r, h->ep_mask, h->ep_fresh, L, h->seq_ring ? h->seq_hw : h->seq_row, Lmax, R.st), "seq_restart");
   OTHER(R, launch_seq_embed_prefill(prompt, stride_b, stride_l, prompt_mask, h->sep_token, h->pos_emb, Lmax, x32, xT, mask, h->ep_mask,
                                     h->ep_poscnt, list, n_r, Lp, E, h->bf16, R.st), "seq_embed_prefill");
   hfgpt_stack(R, x32, xT, mask, n_r, L, h->ep_kv, list, B, Lmax);
+  if (!R.err && h->seq_ring)
+    for (int b : h->restart_list) h->seq_age[b] = 0;   // the sample's ring rows are dead: later steps may overwrite them (a restart itself takes none)
   return R.err;
 }
 
