@@ -165,6 +165,27 @@ int vima_decode(VimaHandle* h, const float* obs_tok, const uint8_t* obs_mask, co
 int vima_decode_step(VimaHandle* h, const float* obs_tok, const uint8_t* obs_mask, const float* act_tok, int step, int B,
                      int Q, const float* prompt, int64_t stride_b, int64_t stride_l, const uint8_t* prompt_mask,
                      int Lp, float* out, vima_stream_t stream);
+/* Multi-step prefill of the episode caches (additive, ABI version unchanged): the T calls vima_decode_step(step), ..., (step + T - 1) made as
+ * ONE pass -- resuming an interrupted rollout, switching from vima_decode to vima_decode_step mid-episode, teacher-forced scoring of a recorded
+ * prefix that leaves the caches filled. obs_tok f32 [T,B,Q,E], obs_mask u8 [T,B,Q], out f32 [T,B,E]; act_tok f32 [T,B,E] when step > 0 (row 0
+ * = the embedded action of step-1, row j = that of step+j-1) and f32 [T-1,B,E] when step == 0 (row j = the action of step j; NULL for T = 1).
+ * out[j] equals row step+j of vima_decode on the full history up to floating-point reassociation. Afterwards the episode state is that of the
+ * T single calls: the next call carries step + T, key mask / position counters / restart flags are the same (a sample restarted right before
+ * the chunk has the chunk's FIRST action slot masked, as in a single step).
+ * Rows: the chunk's T (Q + 1) rows (T (Q + 1) - 1 at step 0; at most 512) are contiguous; step u's slot is [action row, Q obs rows] at
+ * row0 + u (Q + 1) (no action row in the first slot of batch step 0). Without "decode_ring" they are the rows the T single steps would have
+ * written; a chunk that does not fit in front of n_positions fails with code 34, tells how many steps still fit, and changes nothing. With
+ * "decode_ring" the chunk is ONE unit of the ring: never split, the tail is skipped when it does not fit, legal iff
+ * age[b] + rows advanced <= n_positions for every b -- otherwise code 34, the first such sample is named, nothing changes (so a chunk can be
+ * refused where single steps would still pass: the skipped tail is longer). The chunk's own rows are causal among themselves, everything else
+ * written is history (the windowed rule above with the window = the chunk's rows).
+ * T == 1 IS vima_decode_step (same code, same bits, same graph keys). With option "graphs" a chunk of T > 1 runs eager; the graphs of
+ * vima_decode_step stay valid and keep being replayed afterwards. Launches: those of ONE step whatever T (give or take a GEMM form
+ * that runs as two launches at the larger row count: 135 -> 157 at 11 layers, batch 256, T >= 8).
+ * Precision: no precision-specific code; in fp8 / fp8w the call runs the GEMM forms vima_decode_step runs at T (Q + 1) B rows. */
+int vima_decode_chunk(VimaHandle* h, const float* obs_tok, const uint8_t* obs_mask, const float* act_tok, int step, int T, int B,
+                      int Q, const float* prompt, int64_t stride_b, int64_t stride_l, const uint8_t* prompt_mask, int Lp,
+                      float* out, vima_stream_t stream);
 /* Per-sample episode restart inside a running batch of incremental decoding (no reference counterpart: scripts/example.py:97-110 runs
  * one episode at a time; batched environments end their episodes at different steps). For every sample with restart[b] != 0 (HOST
  * array of B bytes): its cached history is masked out, its position counter restarts at 0, its next step has no previous action, and
@@ -177,6 +198,32 @@ int vima_decode_step(VimaHandle* h, const float* obs_tok, const uint8_t* obs_mas
  * cache receives the bits of the per-sample loop (option 0). */
 int vima_decode_restart(VimaHandle* h, const uint8_t* restart, int B, const float* prompt, int64_t stride_b, int64_t stride_l,
                         const uint8_t* prompt_mask, int Lp, vima_stream_t stream);
+
+/* Restart with a history (additive, ABI version unchanged): everything vima_decode_restart does for the flagged samples, then T env steps of
+ * history are installed for each of them, so that an in-flight episode can JOIN a running batch (re-balancing vectorised environments over
+ * handles, merging half-empty batches, resuming single episodes). hist_obs f32 [T,n_r,Q,E], hist_mask u8 [T,n_r,Q], hist_act f32 [T-1,n_r,E]
+ * (NULL for T = 1): the observation tokens of the sample's steps 0 .. T-1 and the embedded actions of steps 0 .. T-2; n_r = the number of flagged
+ * samples, in increasing sample order; all samples flagged in one call share T (ragged histories: one call per length). T == 0 IS
+ * vima_decode_restart, bit for bit. out (may be NULL): f32 [T,n_r,E], the predicted action tokens of the installed steps (the teacher-forced
+ * pass; it costs nothing extra). Afterwards the sample is mid-episode: its next vima_decode_step consumes its row of act_tok (= the action of
+ * history step T-1), its outputs equal vima_decode on (history + later steps) at the matching rows up to reassociation, its position ids continue
+ * from the history's number of valid tokens. The state of every other sample is untouched (their later outputs keep their bits).
+ * Placement: history step s takes the cache rows that BATCH step t-T+s wrote (t = the next batch step): its Q obs rows that slot's obs rows,
+ * a_{s-1} its action row (s > 0; the first slot's action row stays masked). With "decode_ring" the sample's age becomes exactly that of a sample
+ * restarted right before batch step t-T, and so does its vima_decode_steps_left entry. T may be at most vima_decode_history_room (below);
+ * beyond it the call fails with code 34, the message names the room, and NOTHING changes (no restart either).
+ * The history runs as one full-history pass over the n_r samples (plain causal attention under the history's own mask, against the prompt K/V
+ * this call has just rebuilt); per layer its K | V rows are scattered to the mapped rows. On top of the restart's launches: those of ONE vima_decode
+ * pass plus 2 + 2 x layers (the prompt-mask gather, per layer the prompt K/V gather and the K | V scatter, the install), whatever n_r
+ * (the restart's own count depends on n_r for prompts of at most 32 tokens, see above). T (Q + 1) - 1 <= min(512, n_positions). Runs eager also with option "graphs"; the step graphs stay valid.
+ * Precision: no precision-specific code; in fp8 / fp8w the pass runs the GEMM forms vima_decode runs at n_r (T (Q + 1) - 1) rows. */
+int vima_decode_restart_history(VimaHandle* h, const uint8_t* restart, int B, const float* prompt, int64_t stride_b, int64_t stride_l,
+                                const uint8_t* prompt_mask, int Lp, const float* hist_obs, const uint8_t* hist_mask,
+                                const float* hist_act, int T, float* out, vima_stream_t stream);
+/* Host-only: *steps_host = the largest T vima_decode_restart_history accepts now = the number of most recent batch steps whose cache rows are all
+ * still there. Without "decode_ring": the batch steps taken since step 0. With it: the largest R such that the ring rows advanced by the last R
+ * batch steps (skipped tails included; a chunk's tail counts with its first step) sum to at most n_positions. */
+int vima_decode_history_room(VimaHandle* h, int32_t* steps_host);
 
 /* Host-only (additive, ABI version unchanged): out_host[b], b < B = how many further vima_decode_step calls of the running episode batch would
  * succeed if sample b ALONE were never restarted again (the row bookkeeping of vima_decode_step run forward; no device work, no state change).

@@ -89,7 +89,11 @@ PROTOTYPES = {
                                    vp, c_i64, c_i64, vp, ctypes.c_int, ctypes.c_int, vp, vp]),
     "vima_decode_step": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, c_i64, c_i64, vp,
                                         ctypes.c_int, vp, vp]),
+    "vima_decode_chunk": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, c_i64, c_i64, vp,
+                                         ctypes.c_int, vp, vp]),
     "vima_decode_restart": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, c_i64, c_i64, vp, ctypes.c_int, vp]),
+    "vima_decode_restart_history": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, c_i64, c_i64, vp, ctypes.c_int, vp, vp, vp, ctypes.c_int, vp, vp]),
+    "vima_decode_history_room": (ctypes.c_int, [vp, ctypes.POINTER(c_i32)]),
     "vima_decode_steps_left": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(c_i32)]),
     "vima_rgb_tokens_per_image": (ctypes.c_int, [ctypes.POINTER(VimaConfig)]),
     "vima_rgb_encode": (ctypes.c_int, [vp, vp * 2, ctypes.c_int, vp, vp]),

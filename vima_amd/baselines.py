@@ -161,6 +161,32 @@ class _BaselinePolicy(VIMAPolicy):
         ones = torch.ones(obs_token.shape[:2], dtype=torch.bool, device=self._device)
         return VIMAPolicy.forward_step(self, obs_token, ones, prev_action_token, prompt_token, prompt_token_mask, step)
 
+    def forward_steps(self, obs_token, action_token, prompt_token, prompt_token_mask, step: int):
+        """T env steps as one pass (see VIMAPolicy.forward_steps): obs_token [T,B,Q,E], every token valid. VIMAFlamingoPolicy only; the
+        decoder-only policies fill their cache with `seq_prefill` and step with `seq_step`."""
+        if self.KIND != "flamingo":
+            raise NotImplementedError("forward_steps needs the XAttnGPT episode caches (VIMAPolicy / VIMAFlamingoPolicy); the decoder-only "
+                                      "policies decode incrementally with seq_prefill / seq_step")
+        ones = torch.ones(obs_token.shape[:3], dtype=torch.bool, device=self._device)
+        return VIMAPolicy.forward_steps(self, obs_token, ones, action_token, prompt_token, prompt_token_mask, step)
+
+    def restart_samples(self, restart, prompt_token, prompt_token_mask, history=None):
+        """VIMAPolicy.restart_samples; `history` = (obs_token [T,n_r,Q,E], action_token [T-1,n_r,E] | None) -- every token valid -- or the
+        three-tuple of VIMAPolicy with its mask. VIMAFlamingoPolicy only; the decoder-only policies restart with `seq_restart`."""
+        if history is None:
+            return VIMAPolicy.restart_samples(self, restart, prompt_token, prompt_token_mask)
+        if self.KIND != "flamingo":
+            raise NotImplementedError("restart_samples(history=) needs the XAttnGPT episode caches (VIMAPolicy / VIMAFlamingoPolicy); the "
+                                      "decoder-only policies restart with seq_restart and refill with seq_step")
+        if len(history) == 2:
+            history = (history[0], torch.ones(history[0].shape[:3], dtype=torch.bool, device=self._device), history[1])
+        return VIMAPolicy.restart_samples(self, restart, prompt_token, prompt_token_mask, history)
+
+    def history_room(self) -> int:
+        if self.KIND != "flamingo":
+            raise NotImplementedError("history_room: VIMAPolicy / VIMAFlamingoPolicy only (the decoder-only policies have seq_* and steps_left)")
+        return VIMAPolicy.history_room(self)
+
     # ------------------------------------------------------------------ incremental decoding (gpt / gato)
     def _seq_only(self, what):
         if self.KIND == "flamingo":

@@ -535,6 +535,73 @@ __global__ __launch_bounds__(256) void dec_embed_step_kernel(const float* __rest
   }
 }
 
+// Multi-step form of dec_embed_step_kernel (vima_decode_chunk): Tn env steps of every sample in one pass. The chunk's rows are the slots
+// [a_{t-1}, o_t^1 .. o_t^Q] of steps t = step .. step + Tn - 1 back to back; at batch step 0 (has_act = 0) the first slot has no action row, so
+// Ln = Tn (Q + 1) - (1 - has_act) <= 512 rows. obs_tok [Tn,B,Q,E], obs_mask [Tn,B,Q]; act_tok [Tn,B,E] (has_act) or [Tn-1,B,E]: the action row of
+// slot u is act_tok[u - (1 - has_act)]. Position ids continue poscnt[b] over the chunk: each thread owns a contiguous run of rows, block-wide
+// scan of the run totals in LDS as in prompt_pos_kernel (no thread walks the rows alone). fresh[b] masks the action row of the FIRST slot only.
+// One workgroup per sample: it alone reads and then writes poscnt[b] / fresh[b].
+template <typename T>
+__global__ __launch_bounds__(256) void dec_embed_chunk_kernel(const float* __restrict__ obs_tok, const uint8_t* __restrict__ obs_mask,
+                                                               const float* __restrict__ act_tok, const float* __restrict__ pos_table, int n_pos,
+                                                               float* x32, T* xT, uint8_t* hist_mask, int* poscnt, int row0, int Lmax, int Tn, int B,
+                                                               int Q, int has_act, int E, uint8_t* fresh) {
+  __shared__ int pos_s[512];
+  __shared__ int part[256];
+  const int b = blockIdx.x;
+  const int shift = 1 - has_act;              // chunk row l is row l + shift of a chunk whose every slot has an action row
+  const int Ln = Tn * (Q + 1) - shift;
+  const int fr = fresh[b];
+  const int base = poscnt[b];
+  const int per = (Ln + 255) / 256;
+  const int l0 = threadIdx.x * per;
+  auto valid = [&](int l) -> int {
+    const int u = (l + shift) / (Q + 1), s = (l + shift) % (Q + 1);
+    if (s == 0) return (l == 0 && fr) ? 0 : 1;   // l == 0 is an action row only when has_act
+    return obs_mask[((long long)u * B + b) * Q + (s - 1)] ? 1 : 0;
+  };
+  int cnt = 0;
+  for (int j = 0; j < per; ++j)
+    if (l0 + j < Ln) cnt += valid(l0 + j);
+  part[threadIdx.x] = cnt;
+  __syncthreads();   // every thread has read fresh[b] / poscnt[b] by now
+  for (int off = 1; off < 256; off <<= 1) {
+    const int v = threadIdx.x >= off ? part[threadIdx.x - off] : 0;
+    __syncthreads();
+    part[threadIdx.x] += v;
+    __syncthreads();
+  }
+  int run = base + part[threadIdx.x] - cnt;
+  for (int j = 0; j < per; ++j) {
+    const int l = l0 + j;
+    if (l < Ln) {
+      const int mk = valid(l);
+      run += mk;
+      int p = run - 1;
+      p = p < 0 ? 0 : (p >= n_pos ? n_pos - 1 : p);
+      pos_s[l] = p;
+      hist_mask[(long long)b * Lmax + row0 + l] = (uint8_t)mk;
+    }
+  }
+  if (threadIdx.x == 255) {
+    poscnt[b] = base + part[255];
+    if (fr) fresh[b] = 0;
+  }
+  __syncthreads();
+  const int e4 = E >> 2;
+  for (int i = threadIdx.x; i < Ln * e4; i += 256) {
+    const int l = i / e4, c = (i % e4) * 4;
+    const int u = (l + shift) / (Q + 1), s = (l + shift) % (Q + 1);
+    const float* src = s == 0 ? act_tok + ((long long)(u - shift) * B + b) * E : obs_tok + (((long long)u * B + b) * Q + (s - 1)) * E;
+    const float4 a = *reinterpret_cast<const float4*>(src + c);
+    const float4 pp = *reinterpret_cast<const float4*>(pos_table + (long long)pos_s[l] * E + c);
+    const float4 o = make_float4(a.x + pp.x, a.y + pp.y, a.z + pp.z, a.w + pp.w);
+    const long long off = ((long long)b * Ln + l) * E + c;
+    store4(x32 + off, o);
+    if (xT) store4(xT + off, o);
+  }
+}
+
 // per-sample episode restart (vima_decode_restart): flagged samples forget their history (every cached key masked), their position
 // counter restarts at 0 and their next step's action slot is marked absent
 __global__ __launch_bounds__(256) void restart_samples_kernel(const uint8_t* __restrict__ flags, uint8_t* hist_mask, int* poscnt, uint8_t* fresh,
@@ -597,15 +664,16 @@ __global__ __launch_bounds__(256) void prompt_pos_kernel(const float* __restrict
 }
 
 // predicted_action_tokens = tokens_out[Q-1 :: Q+1]  (vima_policy.py:158) -> [T, B, E]
+// lead = 1 (a chunk of vima_decode_chunk behind batch step 0): every slot starts with an action row, the last obs row of slot t is lead + Q - 1 + (Q + 1) t
 __global__ __launch_bounds__(256) void gather_pred_kernel(const float* __restrict__ x, float* out, int Tn, int B, int Q,
-                                                           int Lq, int E) {
+                                                           int Lq, int E, int lead) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   const int e4 = E >> 2;
   if (i >= (long long)Tn * B * e4) return;
   const int c = (int)(i % e4) * 4;
   const long long tb = i / e4;
   const int b = (int)(tb % B), t = (int)(tb / B);
-  const int l = (Q - 1) + (Q + 1) * t;
+  const int l = lead + (Q - 1) + (Q + 1) * t;
   *reinterpret_cast<float4*>(out + tb * E + c) = *reinterpret_cast<const float4*>(x + ((long long)b * Lq + l) * E + c);
 }
 
@@ -859,6 +927,102 @@ __global__ __launch_bounds__(256) void kv_scatter_kernel(const T* __restrict__ i
   *reinterpret_cast<uint4*>(dst + (hm ? ((long long)(n / D) * L + l) * D + n % D : (long long)l * N + n)) = v;
 }
 
+// The inverse of kv_scatter_kernel: block list[r] of a cache of L * N elements per sample (either layout) -> rows [n * L][N]
+template <typename T>
+__global__ __launch_bounds__(256) void kv_gather_kernel(const T* __restrict__ in, T* __restrict__ out, const int* __restrict__ list, int L, int N,
+                                                         int D, int hm) {
+  constexpr int EPC = 16 / (int)sizeof(T);
+  const int r = blockIdx.y;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int cpr = N / EPC;
+  if (i >= (long long)L * cpr) return;
+  const int l = (int)(i / cpr), n = (int)(i % cpr) * EPC;
+  const T* src = in + (long long)list[r] * L * N;
+  const uint4 v = *reinterpret_cast<const uint4*>(src + (hm ? ((long long)(n / D) * L + l) * D + n % D : (long long)l * N + n));
+  *reinterpret_cast<uint4*>(out + ((long long)r * L + l) * N + n) = v;
+}
+
+// Row-map form of kv_scatter_kernel (vima_decode_restart_history): N columns of rows [n * L] (leading dimension ld) -> row rowmap[l] of sample
+// list[r] in a row-major cache of Lmax rows of N elements per sample; the row map is shared by the samples
+template <typename T>
+__global__ __launch_bounds__(256) void kv_scatter_rows_kernel(const T* __restrict__ in, int ld, T* __restrict__ out, const int* __restrict__ list,
+                                                               const int* __restrict__ rowmap, int L, int Lmax, int N) {
+  constexpr int EPC = 16 / (int)sizeof(T);
+  const int r = blockIdx.y;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int cpr = N / EPC;
+  if (i >= (long long)L * cpr) return;
+  const int l = (int)(i / cpr), n = (int)(i % cpr) * EPC;
+  const uint4 v = *reinterpret_cast<const uint4*>(in + ((long long)r * L + l) * ld + n);
+  *reinterpret_cast<uint4*>(out + ((long long)list[r] * Lmax + rowmap[l]) * N + n) = v;
+}
+
+// The episode state of an installed history (vima_decode_restart_history): key mask of the L compact rows -> cache row rowmap[l] of sample list[r],
+// position counter = the history's number of valid tokens, and the sample is mid-episode (its next step consumes its action token)
+__global__ __launch_bounds__(256) void history_install_kernel(const uint8_t* __restrict__ mask, const int* __restrict__ list,
+                                                               const int* __restrict__ rowmap, int L, int Lmax, uint8_t* hist_mask, int* poscnt,
+                                                               uint8_t* fresh) {
+  __shared__ int part[256];
+  const int r = blockIdx.x, b = list[r];
+  int cnt = 0;
+  for (int l = threadIdx.x; l < L; l += 256) {
+    const uint8_t mk = mask[(long long)r * L + l] ? 1 : 0;
+    hist_mask[(long long)b * Lmax + rowmap[l]] = mk;
+    cnt += mk;
+  }
+  part[threadIdx.x] = cnt;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { poscnt[b] = part[0]; fresh[b] = 0; }
+}
+
+// out[r][l] = in[list[r]][l]: the flagged samples' rows of a byte mask [B][L]
+__global__ __launch_bounds__(256) void mask_rows_gather_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, const int* __restrict__ list,
+                                                                int L) {
+  const int r = blockIdx.y;
+  const int l = blockIdx.x * 256 + threadIdx.x;
+  if (l < L) out[(long long)r * L + l] = in[(long long)list[r] * L + l];
+}
+
+int launch_mask_rows_gather(const uint8_t* in, uint8_t* out, const int* list, int n, int L, hipStream_t st) {
+  if (n <= 0 || L <= 0) return 0;
+  if (n > 65535 || !in || !out || !list) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(mask_rows_gather_kernel, dim3(nblk(L, 256), (unsigned)n), dim3(256), 0, st, in, out, list, L);
+  return (int)hipGetLastError();
+}
+
+int launch_kv_gather(const void* in, void* out, const int* list, int n, int L, int N, int D, int hm, bool is_bf16, hipStream_t st) {
+  const int epc = is_bf16 ? 8 : 4;
+  if (n <= 0 || L <= 0 || N <= 0) return 0;
+  if (N % epc || (hm && (D % epc || N % D)) || n > 65535) return (int)hipErrorInvalidValue;
+  const dim3 grid(nblk((long long)L * (N / epc), 256), (unsigned)n);
+  if (is_bf16) hipLaunchKernelGGL(kv_gather_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)in, (bf16_t*)out, list, L, N, D, hm);
+  else hipLaunchKernelGGL(kv_gather_kernel<float>, grid, dim3(256), 0, st, (const float*)in, (float*)out, list, L, N, D, hm);
+  return (int)hipGetLastError();
+}
+
+int launch_kv_scatter_rows(const void* in, int ld, void* out, const int* list, const int* rowmap, int n, int L, int Lmax, int N, bool is_bf16,
+                           hipStream_t st) {
+  const int epc = is_bf16 ? 8 : 4;
+  if (n <= 0 || L <= 0 || N <= 0) return 0;
+  if (N % epc || ld % epc || ld < N || L > Lmax || n > 65535 || !list || !rowmap) return (int)hipErrorInvalidValue;
+  const dim3 grid(nblk((long long)L * (N / epc), 256), (unsigned)n);
+  if (is_bf16) hipLaunchKernelGGL(kv_scatter_rows_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)in, ld, (bf16_t*)out, list, rowmap, L, Lmax, N);
+  else hipLaunchKernelGGL(kv_scatter_rows_kernel<float>, grid, dim3(256), 0, st, (const float*)in, ld, (float*)out, list, rowmap, L, Lmax, N);
+  return (int)hipGetLastError();
+}
+
+int launch_history_install(const uint8_t* mask, const int* list, const int* rowmap, int n, int L, int Lmax, uint8_t* hist_mask, int* poscnt,
+                           uint8_t* fresh, hipStream_t st) {
+  if (n <= 0) return 0;
+  if (L <= 0 || L > Lmax || !mask || !list || !rowmap || !hist_mask || !poscnt || !fresh) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(history_install_kernel, dim3(n), dim3(256), 0, st, mask, list, rowmap, L, Lmax, hist_mask, poscnt, fresh);
+  return (int)hipGetLastError();
+}
+
 int launch_kv_scatter(const void* in, void* out, const int* list, int n, int L, int N, int D, int hm, bool is_bf16, hipStream_t st) {
   const int epc = is_bf16 ? 8 : 4;
   if (n <= 0 || L <= 0 || N <= 0) return 0;
@@ -910,6 +1074,22 @@ int launch_dec_embed_step(const float* obs_tok, const uint8_t* obs_mask, const f
   return (int)hipGetLastError();
 }
 
+int launch_dec_embed_chunk(const float* obs_tok, const uint8_t* obs_mask, const float* act_tok, const float* pos_table, int n_pos,
+                           float* x32, void* xT, uint8_t* hist_mask, int* poscnt, int row0, int Lmax, int T, int B, int Q,
+                           int has_act, int E, bool is_bf16, hipStream_t st, uint8_t* fresh) {
+  if (B <= 0) return 0;
+  const long long Ln = (long long)T * (Q + 1) - (has_act ? 0 : 1);
+  if (T < 1 || Q < 1 || Ln < 1 || Ln > 512 || E % 4 || row0 < 0 || row0 + Ln > Lmax || !fresh || !poscnt || !hist_mask || (Ln > Q && !act_tok))
+    return (int)hipErrorInvalidValue;
+  if (is_bf16)
+    hipLaunchKernelGGL(dec_embed_chunk_kernel<bf16_t>, dim3(B), dim3(256), 0, st, obs_tok, obs_mask, act_tok, pos_table, n_pos,
+                       x32, (bf16_t*)xT, hist_mask, poscnt, row0, Lmax, T, B, Q, has_act ? 1 : 0, E, fresh);
+  else
+    hipLaunchKernelGGL(dec_embed_chunk_kernel<float>, dim3(B), dim3(256), 0, st, obs_tok, obs_mask, act_tok, pos_table, n_pos,
+                       x32, (float*)xT, hist_mask, poscnt, row0, Lmax, T, B, Q, has_act ? 1 : 0, E, fresh);
+  return (int)hipGetLastError();
+}
+
 int launch_restart_samples(const uint8_t* flags, uint8_t* hist_mask, int* poscnt, uint8_t* fresh, int B, int Lmax, hipStream_t st) {
   if (B <= 0) return 0;
   hipLaunchKernelGGL(restart_samples_kernel, dim3(B), dim3(256), 0, st, flags, hist_mask, poscnt, fresh, Lmax);
@@ -931,10 +1111,11 @@ int launch_prompt_pos(const float* prompt, long long sb, long long sl, const uin
   return (int)hipGetLastError();
 }
 
-int launch_gather_pred(const float* x, float* out, int T, int B, int Q, int Lq, int E, hipStream_t st) {
+int launch_gather_pred(const float* x, float* out, int T, int B, int Q, int Lq, int E, hipStream_t st, int lead) {
   const long long total = (long long)T * B * (E / 4);
   if (total <= 0) return 0;
-  hipLaunchKernelGGL(gather_pred_kernel, dim3(nblk(total, 256)), dim3(256), 0, st, x, out, T, B, Q, Lq, E);
+  if (lead < 0 || lead > 1 || lead + (Q - 1) + (long long)(Q + 1) * (T - 1) >= Lq) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(gather_pred_kernel, dim3(nblk(total, 256)), dim3(256), 0, st, x, out, T, B, Q, Lq, E, lead);
   return (int)hipGetLastError();
 }
 

@@ -236,6 +236,12 @@ int launch_dec_embed(const float* obs_tok, const uint8_t* obs_mask, const float*
 int launch_dec_embed_step(const float* obs_tok, const uint8_t* obs_mask, const float* act_tok, const float* pos_table, int n_pos,
                           float* x32, void* xT, uint8_t* hist_mask, int* poscnt, int L_hist, int Lmax, int B, int Q,
                           int has_act, int E, bool is_bf16, hipStream_t st, uint8_t* fresh = nullptr);
+// T env steps of incremental decoding in one pass (vima_decode_chunk): obs_tok [T,B,Q,E], obs_mask [T,B,Q], act_tok [T,B,E] (has_act) or
+// [T-1,B,E] (batch step 0: the first slot has no action row) -> x32 / xT [B, Ln, E], Ln = T (Q + 1) - (1 - has_act) <= 512 rows = the slots
+// [action, Q obs] back to back; position ids continue poscnt[b]; hist_mask[b][row0 + l], poscnt[b] and fresh[b] (first slot only) are updated
+int launch_dec_embed_chunk(const float* obs_tok, const uint8_t* obs_mask, const float* act_tok, const float* pos_table, int n_pos,
+                           float* x32, void* xT, uint8_t* hist_mask, int* poscnt, int row0, int Lmax, int T, int B, int Q,
+                           int has_act, int E, bool is_bf16, hipStream_t st, uint8_t* fresh);
 // per-sample episode restart: for flags[b] != 0 (device array) mask sample b's whole history, reset its position counter, mark its
 // next action slot absent (fresh[b] = 1, consumed by launch_dec_embed_step)
 int launch_restart_samples(const uint8_t* flags, uint8_t* hist_mask, int* poscnt, uint8_t* fresh, int B, int Lmax, hipStream_t st);
@@ -246,8 +252,19 @@ int launch_prompt_pos(const float* prompt, long long sb, long long sl, const uin
 // rows [n * L][N] of the operand type (sample r = rows r * L ..) -> block list[r] (DEVICE array [n]) of a cache of L * N elements per sample:
 // row-major [L][N] (hm = 0) or head-major [N / D][L][D] (the prompt K / V cache's two layouts)
 int launch_kv_scatter(const void* in, void* out, const int* list, int n, int L, int N, int D, int hm, bool is_bf16, hipStream_t st);
-// out[t,b,:] = x[b, (Q-1) + (Q+1) t, :]
-int launch_gather_pred(const float* x, float* out, int T, int B, int Q, int Lq, int E, hipStream_t st);
+// out[r][l] = in[list[r]][l], r < n: rows of a byte mask [B][L] by a sample list (DEVICE array)
+int launch_mask_rows_gather(const uint8_t* in, uint8_t* out, const int* list, int n, int L, hipStream_t st);
+// the inverse of launch_kv_scatter: block list[r] of the cache (either layout) -> rows [n * L][N]
+int launch_kv_gather(const void* in, void* out, const int* list, int n, int L, int N, int D, int hm, bool is_bf16, hipStream_t st);
+// row-map form: N columns of rows [n * L] (leading dimension ld) -> row rowmap[l] (DEVICE array [L], shared by the samples) of sample list[r] in a
+// row-major cache of Lmax rows of N elements per sample (the episode K | V cache)
+int launch_kv_scatter_rows(const void* in, int ld, void* out, const int* list, const int* rowmap, int n, int L, int Lmax, int N, bool is_bf16,
+                           hipStream_t st);
+// installed history: hist_mask[list[r]][rowmap[l]] = mask[r][l], poscnt[list[r]] = the number of valid rows, fresh[list[r]] = 0
+int launch_history_install(const uint8_t* mask, const int* list, const int* rowmap, int n, int L, int Lmax, uint8_t* hist_mask, int* poscnt,
+                           uint8_t* fresh, hipStream_t st);
+// out[t,b,:] = x[b, lead + (Q-1) + (Q+1) t, :]; lead = 1 when every slot of Q + 1 rows starts with an action row (a chunk behind batch step 0)
+int launch_gather_pred(const float* x, float* out, int T, int B, int Q, int Lq, int E, hipStream_t st, int lead = 0);
 
 // ---- baseline policies (baseline_kernels.hip): whole RGB frames, decoder-only sequences
 // uint8 frames [M,3,H,W] -> normalised patch matrix T [M*(H/P)*(W/P), 3*P*P], k = c*P*P + py*P + px

@@ -245,6 +245,12 @@ struct VimaHandle {
   std::vector<int> ring_age;
   int restart_batched = 1;                       // option "restart_batched": vima_decode_restart rebuilds the flagged samples' prompt K / V together (0: one sample at a time)
   std::vector<int> restart_list;                 // host copy of the flagged sample indices (source of the upload)
+  // vima_decode_restart_history: where the recent batch steps wrote (decode_commit appends, chunks included; step 0 clears). obs_row = the slot's first
+  // observation row (its action row, absent at batch step 0, is obs_row - 1); adv = the ring rows the step advanced (a chunk's skipped tail counts
+  // with its first step; without the ring: the slot's rows). Trimmed to n_positions entries: a step advances at least one row
+  struct EpSlot { int obs_row, adv; };
+  std::vector<EpSlot> ep_slots;
+  std::vector<int> hist_rowmap;                  // host copy of the history's compact row -> cache row map (source of the upload)
   // hipGraph replay of the per-env-step entry points (option "graphs"): at small batch a step is ~1300 launches of
   // microsecond kernels and the HOST launch rate is the bound. The launch sequence of a call is captured the second time
   // the same (entry point, shapes, pointers, options, workspace generation) is seen and replayed afterwards.
@@ -2048,23 +2054,34 @@ static int decode_prepare(VimaHandle* h, const float* act_tok, int T, int B, int
   if (!inc && (L_act < 0 || L_act > T || (L_act > 0 && !act_tok) || L_act < T - 1)) return fail("vima_decode: L_act must be T-1 or T");
   const int has_act = inc && step > 0 ? 1 : 0;
   const int L_hist = inc && step > 0 ? step * (Q + 1) - 1 : 0;     // tokens already in the episode cache
-  const int Lq = inc ? Q + has_act : T * Q + L_act;                // tokens processed by this call, per sample
+  // tokens processed by this call, per sample. Incremental: T env steps (vima_decode_step: 1; vima_decode_chunk: more), each a slot of
+  // [action, Q obs] rows; the first slot of batch step 0 has no action row
   const int Lmax = h->cfg.n_positions;
+  const bool chunk = inc && T > 1;
+  const char* fn = chunk ? "vima_decode_chunk" : "vima_decode_step";
+  if (chunk && (long long)T * (Q + 1) > 512)
+    return fail("vima_decode_chunk: a chunk holds at most 512 rows (T (Q + 1) = " + std::to_string((long long)T * (Q + 1)) + ")");
+  const int Lq = inc ? T * (Q + 1) - (has_act ? 0 : 1) : T * Q + L_act;
   const bool ring = inc && h->decode_ring != 0;
+  if (chunk && !ring && L_hist + Lq > Lmax)
+    return fail("vima_decode_chunk: " + std::to_string(T) + " steps from step " + std::to_string(step) + " need " + std::to_string(L_hist + Lq) +
+                " cache rows > n_positions " + std::to_string(Lmax) + " (room for " + std::to_string(std::max(0, (Lmax + 1) / (Q + 1) - step)) +
+                " more steps)", 34);
   if (ring ? Lq > Lmax : L_hist + Lq > h->cfg.n_positions) return fail("vima_decode: history longer than n_positions", 34);
   if (Lp > h->cfg.xattn_n_positions)   // xattn_gpt.py:110 assert
     return fail("AssertionError: prompt_tokens.size(1) <= xattn_n_positions (" + std::to_string(Lp) + " > " +
                 std::to_string(h->cfg.xattn_n_positions) + ")", 33);
   if (inc) {
     if (has_act && !act_tok) return fail("vima_decode_step: the previous action token is required for step > 0");
+    if (chunk && !act_tok) return fail("vima_decode_chunk: the action tokens between the chunk's steps are required");
     if (step > 0 && !(h->ep_step == step - 1 && h->ep_B == B && h->ep_Q == Q && h->ep_Lp == Lp && h->kv_valid))
-      return fail("vima_decode_step: step " + std::to_string(step) + " does not continue the episode state (last step " +
+      return fail(std::string(fn) + ": step " + std::to_string(step) + " does not continue the episode state (last step " +
                   std::to_string(h->ep_step) + "); start an episode with step 0");
-    if (ring && step > 0) {   // legal iff every row about to be overwritten or skipped is dead for every sample
+    if (ring && step > 0) {   // legal iff every row about to be overwritten or skipped is dead for every sample (a chunk is ONE unit of Lq rows)
       const RingStep rs = ring_next(h->ring_wp, Lq, Lmax);
       for (int b = 0; b < B; ++b)
         if (h->ring_age[b] + rs.advance > Lmax)
-          return fail("vima_decode_step: the episode of sample " + std::to_string(b) + " is longer than n_positions (" + std::to_string(h->ring_age[b]) + " + " +
+          return fail(std::string(fn) + ": the episode of sample " + std::to_string(b) + " is longer than n_positions (" + std::to_string(h->ring_age[b]) + " + " +
                       std::to_string(rs.advance) + " ring rows > " + std::to_string(Lmax) + "): restart it with vima_decode_restart", 34);
     }
     kv_cache_mode = step == 0 ? 1 : 2;
@@ -2099,9 +2116,19 @@ static int decode_prepare(VimaHandle* h, const float* act_tok, int T, int B, int
   return 0;
 }
 
-static void decode_commit(VimaHandle* h, const DecodePlan& P, int B, int Q, int Lp, int step) {
+// step: the first env step of the call; T: how many it took (vima_decode_chunk)
+static void decode_commit(VimaHandle* h, const DecodePlan& P, int B, int Q, int Lp, int step, int T = 1) {
   if (P.kv_mode == 1) { h->kv_valid = true; h->kv_B = B; h->kv_Lp = Lp; }
-  if (P.inc) { h->ep_step = step; h->ep_B = B; h->ep_Q = Q; h->ep_Lp = Lp; h->ep_Lmax = P.Lmax; }
+  if (P.inc) {
+    h->ep_step = step + T - 1; h->ep_B = B; h->ep_Q = Q; h->ep_Lp = Lp; h->ep_Lmax = P.Lmax;
+    if (step == 0) h->ep_slots.clear();
+    for (int u = 0; u < T; ++u) {   // slot u = [action row, Q obs rows] at P.row + u (Q + 1); the first slot of batch step 0 has no action row
+      const int obs_row = P.row + u * (Q + 1) + (P.has_act ? 1 : 0);
+      const int rows = (step == 0 && u == 0) ? Q : Q + 1;
+      h->ep_slots.push_back({obs_row, u == 0 ? (P.ring ? P.advance : P.Lq) - (T - 1) * (Q + 1) : rows});
+    }
+    if ((int)h->ep_slots.size() > P.Lmax) h->ep_slots.erase(h->ep_slots.begin(), h->ep_slots.end() - P.Lmax);
+  }
   if (P.ring) {
     if (step == 0) h->ring_age.assign((size_t)B, 0);
     for (int& a : h->ring_age) a += P.advance;
@@ -2111,7 +2138,10 @@ static void decode_commit(VimaHandle* h, const DecodePlan& P, int B, int Q, int 
 
 static int decode_launch(VimaHandle* h, const float* obs_tok, const uint8_t* obs_mask, const float* act_tok, int T, int B, int Q,
                          int L_act, const float* prompt, int64_t stride_b, int64_t stride_l, const uint8_t* prompt_mask, int Lp,
-                         const DecodePlan& P, float* out, hipStream_t stream) {
+                         const DecodePlan& P, float* out, hipStream_t stream, bool hist = false) {
+  // hist (vima_decode_restart_history): the full-history branch over the B = n_r flagged samples (h->restart_list) of a running episode batch. Their
+  // prompt K / V are gathered from the handle's cache, every layer's self-attention K | V rows are scattered into the episode cache at
+  // h->hist_rowmap, and the episode state is installed at the end; `prompt` / `prompt_mask` (the batch's) are indexed through the list
   if (int e = check_ready(h)) return e;
   const int E = h->cfg.embed_dim;
   const bool inc = P.inc;
@@ -2133,8 +2163,8 @@ static int decode_launch(VimaHandle* h, const float* obs_tok, const uint8_t* obs
   // they are all issued on the auxiliary stream up front (one buffer per layer) and overlap the serial decoder chain;
   // with kv_cache_mode 1/2 they live in a handle-owned cache that survives across calls (one episode = one prompt).
   const int NL = h->cfg.xf_n_layers;
-  const bool use_cache = kv_cache_mode != 0;
-  const bool build_kv = kv_cache_mode != 2;
+  const bool use_cache = kv_cache_mode != 0 && !hist;
+  const bool build_kv = kv_cache_mode != 2 && !hist;
   const size_t kv_layer_bytes = (size_t)rp * 2 * E * h->esz();
   const bool dual = h->dual_stream != 0 && build_kv;
   std::vector<void*> KVs(NL);
@@ -2162,8 +2192,21 @@ static int decode_launch(VimaHandle* h, const float* obs_tok, const uint8_t* obs
                         : 0;
   float* st_sum = ffold ? R.ws<float>((size_t)rq * (E / 32)) : nullptr;
   float* st_ssq = ffold ? R.ws<float>((size_t)rq * (E / 32)) : nullptr;
+  int* hlist = hist ? R.ws<int>((size_t)B) : nullptr;
+  int* hmap = hist ? R.ws<int>((size_t)Lq) : nullptr;
+  uint8_t* hpmask = hist ? R.ws<uint8_t>((size_t)rp) : nullptr;   // the flagged samples' rows of the prompt mask
   if (R.err) return R.err;
-  if (inc)
+  if (hist) {
+    if ((int)h->restart_list.size() != B || (int)h->hist_rowmap.size() != Lq) return fail("vima_decode_restart_history: internal row map mismatch");
+    HIPCK(hipMemcpyAsync(hlist, h->restart_list.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, R.st));
+    HIPCK(hipMemcpyAsync(hmap, h->hist_rowmap.data(), (size_t)Lq * sizeof(int), hipMemcpyHostToDevice, R.st));
+    OTHER(R, launch_mask_rows_gather(prompt_mask, hpmask, hlist, B, Lp, R.st), "mask_rows_gather");
+    prompt_mask = hpmask;
+  }
+  if (inc && T > 1)   // a chunk of T env steps (vima_decode_chunk): Lq = T (Q + 1) [- 1 at step 0] rows per sample at row L_hist
+    OTHER(R, launch_dec_embed_chunk(obs_tok, obs_mask, act_tok, h->pos_emb, h->cfg.n_positions, x32, xT, h->ep_mask, h->ep_poscnt,
+                                    L_hist, Lmax, T, B, Q, has_act, E, h->bf16, R.st, h->ep_fresh), "dec_embed_chunk");
+  else if (inc)
     OTHER(R, launch_dec_embed_step(obs_tok, obs_mask, act_tok, h->pos_emb, h->cfg.n_positions, x32, xT, h->ep_mask, h->ep_poscnt,
                                    L_hist, Lmax, B, Q, has_act, E, h->bf16, R.st, h->ep_fresh), "dec_embed_step");
   else
@@ -2207,7 +2250,7 @@ static int decode_launch(VimaHandle* h, const float* obs_tok, const uint8_t* obs
   if (build_kv)
     hm = h->kv_headmajor && h->bf16 && gemm_headmajor_ok(&h->tune, rp, 2 * E, E, E, E, Dx, Lp, p8 != nullptr ? 1 : 0) != 0;
   else
-    hm = h->kv_hm;
+    hm = hist ? false : h->kv_hm;   // hist: gathered below, row-major
   if (use_cache && build_kv) h->kv_hm = hm;
   auto kv_proj = [&](Run& Rr, int i, void* KV) {
     GemmArgs g;
@@ -2241,6 +2284,9 @@ static int decode_launch(VimaHandle* h, const float* obs_tok, const uint8_t* obs
     if (dual) HIPCK(hipStreamWaitEvent(R.st, h->ev_layer[i], 0));
     else if (build_kv)   // single stream: project right before use (without a cache all layers share one buffer)
       kv_proj(R, i, KV);
+    else if (hist)       // the flagged samples' blocks of the prompt K / V cache (either layout), which the restart in front of this pass has rebuilt
+      OTHER(R, launch_kv_gather(reinterpret_cast<char*>(h->kv_cache) + (size_t)h->ep_B * Lp * 2 * E * h->esz() * i, KV, hlist, B, Lp, 2 * E, Dx,
+                                h->kv_hm ? 1 : 0, h->bf16, R.st), "kv_gather");
     AttnArgs a;
     a.q = Qb; a.ldq = E; a.out = ctx; a.ldo = E;
     if (hm) {   // [B][2 Hx][Lp][Dx]: K heads 0 .. Hx-1, V heads Hx .. 2 Hx-1
@@ -2300,6 +2346,9 @@ static int decode_launch(VimaHandle* h, const float* obs_tok, const uint8_t* obs
       R.linear(xT, E, D.c_attn, rq, ACT_NONE, nullptr, 0, nullptr, 0, nullptr, 0, qkv, 3 * E);
       s.q = qkv; s.ldq = 3 * E; s.k = R.offT(qkv, E); s.ldk = 3 * E; s.v = R.offT(qkv, 2 * E); s.ldv = 3 * E;
       s.kmask = dmask; s.Lk = Lq;
+      if (hist)   // the history's K | V rows of this layer -> the episode cache, at the rows the batch steps behind them wrote
+        OTHER(R, launch_kv_scatter_rows(R.offT(qkv, E), 3 * E, reinterpret_cast<char*>(h->ep_kv) + (size_t)i * h->ep_B * Lmax * 2 * E * h->esz(), hlist,
+                                        hmap, B, Lq, Lmax, 2 * E, h->bf16, R.st), "kv_scatter_rows");
     }
     R.attn(s, h->attn_impl);
     R.linear(ctx, E, D.c_proj, rq, ACT_NONE, nullptr, 0, x32, E, a32, E, nullptr, 0);   // x + a
@@ -2314,8 +2363,10 @@ static int decode_launch(VimaHandle* h, const float* obs_tok, const uint8_t* obs
     }
     if (R.err) return R.err;
   }
-  if (inc) OTHER(R, launch_gather_pred(x32, out, 1, B, Lq, Lq, E, R.st), "gather_pred");   // the last new token of every sample
-  else OTHER(R, launch_gather_pred(x32, out, T, B, Q, Lq, E, R.st), "gather_pred");
+  if (inc && T > 1) OTHER(R, launch_gather_pred(x32, out, T, B, Q, Lq, E, R.st, has_act), "gather_pred");   // the last obs row of every slot of the chunk
+  else if (inc) OTHER(R, launch_gather_pred(x32, out, 1, B, Lq, Lq, E, R.st), "gather_pred");   // the last new token of every sample
+  else if (out) OTHER(R, launch_gather_pred(x32, out, T, B, Q, Lq, E, R.st), "gather_pred");
+  if (hist) OTHER(R, launch_history_install(dmask, hlist, hmap, B, Lq, Lmax, h->ep_mask, h->ep_poscnt, h->ep_fresh, R.st), "history_install");
   if (dual && join_aux(R)) return 1;
   return R.err;
 }
@@ -2354,6 +2405,23 @@ int vima_decode_step(VimaHandle* h, const float* obs_tok, const uint8_t* obs_mas
     return decode_launch(h, obs_tok, obs_mask, act_tok, 1, B, Q, 0, prompt, stride_b, stride_l, prompt_mask, Lp, P, out, st);
   }, warm);
   if (!rc) decode_commit(h, P, B, Q, Lp, step);
+  return rc;
+}
+
+// T env steps of the running episode batch as ONE pass of the incremental branch: Lq = T (Q + 1) rows per sample (one fewer at batch step 0) at
+// one row offset -- one unit of the ring -- instead of T passes of Q + 1 rows; 1 / T of the launches. T = 1 IS vima_decode_step (graph keys
+// included). A longer chunk runs eager also with option "graphs": it is a rare call (prefill, resume), and every distinct (T, row, keys read)
+// would be a graph of its own; the step graphs captured before stay valid (they read the episode state from the device and the plan from
+// their key) and are replayed again from the next vima_decode_step on.
+int vima_decode_chunk(VimaHandle* h, const float* obs_tok, const uint8_t* obs_mask, const float* act_tok, int step, int T, int B, int Q,
+                      const float* prompt, int64_t stride_b, int64_t stride_l, const uint8_t* prompt_mask, int Lp, float* out,
+                      vima_stream_t stream) {
+  if (T == 1) return vima_decode_step(h, obs_tok, obs_mask, act_tok, step, B, Q, prompt, stride_b, stride_l, prompt_mask, Lp, out, stream);
+  if (step < 0 || T < 1) return fail("vima_decode_chunk: step must be >= 0 and T >= 1");
+  DecodePlan P;
+  if (int e = decode_prepare(h, act_tok, T, B, Q, 0, Lp, 0, step, P)) return e;
+  const int rc = decode_launch(h, obs_tok, obs_mask, act_tok, T, B, Q, 0, prompt, stride_b, stride_l, prompt_mask, Lp, P, out, (hipStream_t)stream);
+  if (!rc) decode_commit(h, P, B, Q, Lp, step, T);
   return rc;
 }
 
@@ -2418,6 +2486,71 @@ int vima_decode_restart(VimaHandle* h, const uint8_t* restart, int B, const floa
   if (!R.err && h->decode_ring && (int)h->ring_age.size() == B)
     for (int b : h->restart_list) h->ring_age[b] = 0;   // the sample's rows are dead: the ring may overwrite them
   return R.err;
+}
+
+// The largest history vima_decode_restart_history can install: the batch steps whose rows are all still there. Without the ring: every step since
+// step 0; with it: the last R steps whose advances sum to at most n_positions (a sample restarted right before them would still be legal now).
+static int history_room(const VimaHandle* h) {
+  if (h->ep_step < 0) return 0;
+  if (!h->decode_ring) return (int)h->ep_slots.size();
+  int R = 0, sum = 0;
+  for (int j = (int)h->ep_slots.size() - 1; j >= 0 && sum + h->ep_slots[j].adv <= h->ep_Lmax; --j) { sum += h->ep_slots[j].adv; ++R; }
+  return R;
+}
+
+int vima_decode_history_room(VimaHandle* h, int32_t* steps_host) {
+  if (!h || !steps_host) return fail("vima_decode_history_room: null argument");
+  if (h->cfg.policy_kind != VIMA_POLICY_VIMA && h->cfg.policy_kind != VIMA_POLICY_FLAMINGO)
+    return fail("vima_decode_history_room: the handle's policy has no XAttnGPT episode caches");
+  if (h->ep_step < 0) return fail("vima_decode_history_room: no running episode batch (start one with vima_decode_step(step = 0))");
+  *steps_host = history_room(h);
+  return 0;
+}
+
+// vima_decode_restart with a history: the restart itself (same code, same bits), then the T env steps of history of the n_r flagged samples as ONE
+// full-history pass over [n_r, T (Q + 1) - 1] rows (decode_launch, hist): plain causal attention under the history's own mask against the prompt K / V
+// the restart has just rebuilt, every layer's K | V rows scattered to the cache rows that batch steps t - T .. t - 1 wrote, then the key mask, position
+// counter and restart flag. The launches of one vima_decode pass plus 2 + 2 x layers on top of the restart's, whatever n_r. Host: the samples' ring
+// age becomes that of a sample restarted right before batch step t - T.
+int vima_decode_restart_history(VimaHandle* h, const uint8_t* restart, int B, const float* prompt, int64_t stride_b, int64_t stride_l,
+                                const uint8_t* prompt_mask, int Lp, const float* hist_obs, const uint8_t* hist_mask, const float* hist_act, int T,
+                                float* out, vima_stream_t stream) {
+  if (T == 0) return vima_decode_restart(h, restart, B, prompt, stride_b, stride_l, prompt_mask, Lp, stream);
+  if (!h) return fail("null handle");
+  if (T < 0) return fail("vima_decode_restart_history: T must be >= 0");
+  if (!restart || !prompt || !prompt_mask || !hist_obs || !hist_mask || (T > 1 && !hist_act)) return fail("vima_decode_restart_history: null argument");
+  if (h->cfg.policy_kind != VIMA_POLICY_VIMA && h->cfg.policy_kind != VIMA_POLICY_FLAMINGO)
+    return fail("vima_decode_restart_history: the handle's policy has no XAttnGPT episode caches");
+  if (!(h->ep_step >= 0 && h->ep_B == B && h->ep_Lp == Lp && h->kv_valid && h->kv_B == B && h->kv_Lp == Lp))
+    return fail("vima_decode_restart_history: no running episode batch with this B / Lp (start one with vima_decode_step(step = 0))");
+  const int Q = h->ep_Q, Lmax = h->ep_Lmax;
+  const int room = history_room(h);
+  if (T > room)
+    return fail("vima_decode_restart_history: a history of " + std::to_string(T) + " steps does not fit: room for " + std::to_string(room) +
+                " (the batch steps whose cache rows are all still there)", 34);
+  const long long Lh = (long long)T * (Q + 1) - 1;
+  if (Lh > 512 || Lh > Lmax) return fail("vima_decode_restart_history: a history holds at most min(512, n_positions) rows");
+  if (int e = vima_decode_restart(h, restart, B, prompt, stride_b, stride_l, prompt_mask, Lp, stream)) return e;
+  const int n_r = (int)h->restart_list.size();
+  if (n_r == 0) return 0;
+  // history step s sits in the slot of batch step t - T + s: its Q obs rows in the slot's obs rows, a_{s-1} in its action row (s > 0; the first
+  // slot's action row stays masked). Compact rows (dec_embed_kernel): [o_0 (Q), a_0, o_1 (Q), a_1, ...]
+  const VimaHandle::EpSlot* S = h->ep_slots.data() + (h->ep_slots.size() - (size_t)T);
+  h->hist_rowmap.resize((size_t)Lh);
+  int age = 0;
+  for (int s = 0; s < T; ++s) {
+    age += S[s].adv;
+    for (int q = 0; q < Q; ++q) h->hist_rowmap[(size_t)s * (Q + 1) + q] = S[s].obs_row + q;
+    if (s + 1 < T) h->hist_rowmap[(size_t)s * (Q + 1) + Q] = S[s + 1].obs_row - 1;
+  }
+  for (int r : h->hist_rowmap)
+    if (r < 0 || r >= Lmax) return fail("vima_decode_restart_history: internal error: history row outside the cache");
+  const DecodePlan P{false, 0, 0, (int)Lh, Lmax, 0, (int)Lh, 0, false, 0, 0, 0};
+  const int rc = decode_launch(h, hist_obs, hist_mask, hist_act, T, n_r, Q, T - 1, prompt, stride_b, stride_l, prompt_mask, Lp, P, out,
+                               (hipStream_t)stream, true);
+  if (!rc && h->decode_ring && (int)h->ring_age.size() == B)
+    for (int b : h->restart_list) h->ring_age[b] = age;
+  return rc;
 }
 
 // Host-only: how many further vima_decode_step calls would succeed if sample b alone were never restarted (the bookkeeping of decode_prepare run forward).

@@ -421,6 +421,49 @@ class VIMAPolicy(nn.Module):
         self._ep_B = B
         return out
 
+    def forward_steps(self, obs_token: torch.Tensor, obs_mask: torch.Tensor, action_token: torch.Tensor | None,
+                      prompt_token: torch.Tensor, prompt_token_mask: torch.Tensor, step: int):
+        """Episode prefill: the T calls `forward_step(step), ..., forward_step(step + T - 1)` as ONE pass (vima_decode_chunk; the launches
+        of one step whatever T) -- resume an interrupted rollout from its recorded tokens, switch from `forward` to `forward_step`
+        mid-episode, or score a recorded prefix teacher-forced and keep stepping. obs_token [T,B,Q,E], obs_mask [T,B,Q]; action_token
+        [T,B,E] for step > 0 (row 0 = the embedded action of step-1, row j = that of step+j-1) and [T-1,B,E] for step 0 (None for T = 1).
+        Returns the predicted action tokens [T,B,E] == forward(<full history>)[step : step + T]; the next call carries step + T.
+        T = 1 is `forward_step` itself, bit for bit. IndexError (nothing changes) when the chunk does not fit: without `decode_ring` in
+        front of n_positions (the message tells how many steps still fit), with it when the chunk -- one unit of the ring, never split --
+        would overrun the episode of a sample (named in the message)."""
+        self._ready()
+        dev = self._device
+        if obs_token.dim() != 4 or obs_mask.dim() != 3 or tuple(obs_mask.shape) != tuple(obs_token.shape[:3]):
+            raise AssertionError(f"forward_steps: obs_token must be [T,B,Q,E] and obs_mask [T,B,Q], got {tuple(obs_token.shape)} / {tuple(obs_mask.shape)}")
+        T, B, Q, E = obs_token.shape
+        if T < 1:
+            raise AssertionError("forward_steps: T must be >= 1")
+        n_act = T if step > 0 else T - 1
+        if action_token is not None and action_token.dim() == 2 and n_act == 1:
+            action_token = action_token.unsqueeze(0)
+        if n_act > 0 and (action_token is None or tuple(action_token.shape) != (n_act, B, E)):
+            raise AssertionError(f"forward_steps: action_token must be [{n_act}, {B}, {E}] for T = {T} at step {step}, got "
+                                 f"{None if action_token is None else tuple(action_token.shape)}")
+        if T == 1:
+            return self.forward_step(obs_token[0], obs_mask[0], action_token[0] if n_act else None, prompt_token, prompt_token_mask, step).unsqueeze(0)
+        obs_token = obs_token.to(device=dev, dtype=torch.float32).contiguous()
+        obs_mask = obs_mask.to(device=dev, dtype=torch.bool).contiguous()
+        if step == 0:
+            assert torch.all(obs_mask[0, :, 0]), "first observation token of every sample must be valid (position id >= 0)"
+        action_token = action_token.to(device=dev, dtype=torch.float32).contiguous()
+        if prompt_token.stride(-1) != 1:
+            prompt_token = prompt_token.contiguous()
+        prompt_token = prompt_token.to(dev)
+        prompt_token_mask = prompt_token_mask.to(device=dev, dtype=torch.bool).contiguous()
+        Lp = prompt_token.shape[0]
+        out = torch.empty(T, B, E, dtype=torch.float32, device=dev)
+        self._kv_key = None   # the native prompt cache now belongs to this episode
+        _lib.check(self._lib.vima_decode_chunk(
+            self._handle, _ptr(obs_token), _ptr(obs_mask), _ptr(action_token), int(step), T, B, Q, _ptr(prompt_token),
+            prompt_token.stride(1), prompt_token.stride(0), _ptr(prompt_token_mask), Lp, _ptr(out), self._stream()))
+        self._ep_B = B
+        return out
+
     def steps_left(self) -> torch.Tensor:
         """torch.IntTensor[B] on the CPU: for every sample of the batch that is stepping with `forward_step`, how many further
         `forward_step` calls would succeed if that sample alone were never restarted (host bookkeeping only: no device work, no
@@ -432,12 +475,20 @@ class VIMAPolicy(nn.Module):
         _lib.check(self._lib.vima_decode_steps_left(self._handle, B, ctypes.cast(out.data_ptr(), ctypes.POINTER(ctypes.c_int32))))
         return out[:B]
 
-    def restart_samples(self, restart, prompt_token: torch.Tensor, prompt_token_mask: torch.Tensor):
+    def restart_samples(self, restart, prompt_token: torch.Tensor, prompt_token_mask: torch.Tensor, history=None):
         """Per-sample episode restart inside a batch that is stepping with `forward_step` (batched environments finish their
         episodes at different steps): for every sample with `restart[b]` true its cached history is forgotten, its position ids
         restart at 0, its next `forward_step` ignores the previous-action token, and its prompt K/V cache rows are rebuilt from
         `prompt_token[:, b]` / `prompt_token_mask[b]` (the new episode's prompt, same [Lp, B, E] / [B, Lp] layout as `forward_step`;
-        other samples' rows are not read). Keep calling `forward_step(..., step=previous + 1)` with the UPDATED prompt tensors."""
+        other samples' rows are not read). Keep calling `forward_step(..., step=previous + 1)` with the UPDATED prompt tensors.
+
+        history = (obs_token [T,n_r,Q,E], obs_mask [T,n_r,Q], action_token [T-1,n_r,E] | None): the flagged samples (n_r of them, in
+        increasing sample order; one T for all) do not start empty but JOIN the batch mid-episode with these T env steps behind them
+        (vima_decode_restart_history): their next `forward_step` consumes their row of the previous-action token (the action of history
+        step T-1) and continues the episode as if it had run here. Returns the predicted action tokens [T,n_r,E] of the installed steps
+        (the teacher-forced pass). The other samples are untouched. T may be at most `history_room()`: IndexError beyond, and nothing
+        changes. With `decode_ring` the samples' `steps_left()` is that of a sample restarted T batch steps ago. T = 0 (or None) is the
+        plain restart."""
         self._ready()
         dev = self._device
         flags = torch.as_tensor(restart).to(dtype=torch.uint8, device="cpu").contiguous()
@@ -447,9 +498,38 @@ class VIMAPolicy(nn.Module):
         prompt_token_mask = prompt_token_mask.to(device=dev, dtype=torch.bool).contiguous()
         Lp, B = prompt_token.shape[0], prompt_token.shape[1]
         assert flags.numel() == B
+        if history is None:
+            self._kv_key = None
+            _lib.check(self._lib.vima_decode_restart(self._handle, ctypes.c_void_p(flags.data_ptr()), B, _ptr(prompt_token),
+                                                     prompt_token.stride(1), prompt_token.stride(0), _ptr(prompt_token_mask), Lp, self._stream()))
+            return None
+        h_obs, h_mask, h_act = history
+        n_r, E = int(flags.count_nonzero()), self.embed_dim
+        if h_obs.dim() != 4 or h_obs.shape[1] != n_r or h_obs.shape[3] != E or tuple(h_mask.shape) != tuple(h_obs.shape[:3]):
+            raise AssertionError(f"restart_samples: history obs_token must be [T, {n_r}, Q, {E}] and obs_mask [T, {n_r}, Q], got "
+                                 f"{tuple(h_obs.shape)} / {tuple(h_mask.shape)}")
+        T = h_obs.shape[0]
+        if T > 1 and (h_act is None or tuple(h_act.shape) != (T - 1, n_r, E)):
+            raise AssertionError(f"restart_samples: history action_token must be [{T - 1}, {n_r}, {E}], got {None if h_act is None else tuple(h_act.shape)}")
+        h_obs = h_obs.to(device=dev, dtype=torch.float32).contiguous()
+        h_mask = h_mask.to(device=dev, dtype=torch.bool).contiguous()
+        if T > 0 and n_r > 0:
+            assert torch.all(h_mask[0, :, 0]), "first observation token of every history must be valid (position id >= 0)"
+        h_act = h_act.to(device=dev, dtype=torch.float32).contiguous() if T > 1 else None
+        out = torch.empty(T, n_r, E, dtype=torch.float32, device=dev)
         self._kv_key = None
-        _lib.check(self._lib.vima_decode_restart(self._handle, ctypes.c_void_p(flags.data_ptr()), B, _ptr(prompt_token),
-                                                 prompt_token.stride(1), prompt_token.stride(0), _ptr(prompt_token_mask), Lp, self._stream()))
+        _lib.check(self._lib.vima_decode_restart_history(
+            self._handle, ctypes.c_void_p(flags.data_ptr()), B, _ptr(prompt_token), prompt_token.stride(1), prompt_token.stride(0),
+            _ptr(prompt_token_mask), Lp, _ptr(h_obs), _ptr(h_mask), _ptr(h_act), T, _ptr(out) if T > 0 else None, self._stream()))
+        return out
+
+    def history_room(self) -> int:
+        """The largest T `restart_samples(..., history=)` accepts now: the number of most recent batch steps whose cache rows are all still
+        there (without `decode_ring`: the steps taken since step 0). Host bookkeeping only."""
+        self._ready()
+        room = ctypes.c_int32(0)
+        _lib.check(self._lib.vima_decode_history_room(self._handle, ctypes.byref(room)))
+        return int(room.value)
 
     # ------------------------------------------------------------------ actions
     def action_logits(self, predicted_action_tokens: torch.Tensor) -> torch.Tensor:
