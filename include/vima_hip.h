@@ -384,6 +384,45 @@ int vima_seq_decode_step(VimaHandle* h, const float* obs_tok, const float* act_t
  * stopped moving. */
 int vima_seq_decode_restart(VimaHandle* h, const uint8_t* restart, int B, const float* prompt, int64_t stride_b, int64_t stride_l,
                             const uint8_t* prompt_mask, int Lp, vima_stream_t stream);
+/* Episode prefill of the decoder-only policies (GPT / GATO handles only, option decode_ring refused, like the other vima_seq_* calls): the
+ * counterparts of vima_decode_chunk / vima_decode_restart_history / vima_decode_history_room.
+ *
+ * vima_seq_decode_chunk: the T calls vima_seq_decode_step(step) .. (step + T - 1) as ONE pass. obs_tok f32 [T,B,Q,E], out f32 [T,B,E]; act_tok
+ * f32 [T,B,E] when step > 0 (row 0 = the action of step - 1, row j that of step + j - 1), f32 [T-1,B,E] when step == 0 (NULL for T = 1). `step`
+ * must continue the episode state as for the single step. The chunk is Lq = T (Q + 1) - (step == 0) contiguous rows: slot u is [a, o^1 .. o^Q] at
+ * row + u (Q + 1) - (step == 0); the first slot of batch step 0 has no action row. Linear cache: legal iff rows so far + Lq <= n_positions, else
+ * code 34, the message says how many steps still fit ("room for N more steps") and nothing changes. Option "seq_ring": the chunk is ONE unit of
+ * the ring -- row = wp, or P0 after skipping the tail [wp, n_positions) when wp + Lq > n_positions; never split -- legal iff age[b] + advance <= R
+ * for every b, else code 34, the first such sample is named and nothing changes; because the skipped tail is longer a chunk can be refused where
+ * single steps still pass. The new queries attend with q_off = row, win_end = row + Lq (ring; the plain rule otherwise) to the keys
+ * [0, max(hw, row + Lq)): the chunk's rows are causal among themselves, everything else written is history. The episode state afterwards is that
+ * of the T single calls (step number, rows, ages, hw, one position id per valid row). A sample restarted right before the chunk has only the
+ * chunk's FIRST action slot masked (zeros embedded, no position id, its act_tok row not read). T == 1 is vima_seq_decode_step itself: same
+ * code, same bits, same graph keys. T > 1 runs eager also with option "graphs"; the captured step graphs stay valid and are replayed afterwards.
+ * There is no bound on Lq beyond the two legality rules: the chunk has its own embedding kernel (no 64-row limit of the single step's) and
+ * GEMM, attention, LayerNorm and gather take any row count.
+ * Every successful step / chunk appends one host record per env step (first obs row, ring rows advanced; a chunk's skipped tail counts with its
+ * first step); vima_seq_prefill clears the record.
+ *
+ * vima_seq_history_room (host only): the largest T vima_seq_decode_restart_history accepts now -- without seq_ring the batch steps taken since
+ * the prefill, with it the largest r such that the ring rows advanced by the last r batch steps sum to at most R.
+ *
+ * vima_seq_decode_restart_history: everything vima_seq_decode_restart does for the flagged samples, then T env steps of history installed for
+ * each of them, so that an episode recorded elsewhere continues inside this running batch. hist_obs f32 [T,n_r,Q,E], hist_act f32 [T-1,n_r,E]
+ * (NULL for T = 1), n_r = the flagged samples in increasing order, one T per call; out NULL or f32 [T,n_r,E] = the teacher-forced predictions.
+ * T == 0 is vima_seq_decode_restart, bit for bit. Code 34 before ANYTHING changes (the restart included) when T > room (the message names the
+ * room) or Lp + T (Q + 1) > n_positions. With t the next batch step, history step s takes the cache rows batch step t - T + s wrote: its Q obs
+ * rows in that slot's obs rows, a_{s-1} in its action row (s > 0); the first slot's action row stays masked. With seq_ring age[b] becomes the sum
+ * of those T slots' advances -- the age of a sample restarted right before batch step t - T (vima_decode_steps_left agrees). ONE pass of the
+ * vima_seq_decode form, [prompt | sep | o_0, a_0, .., o_{T-1}] = Lp + T (Q + 1) rows of the n_r samples, replaces the restart's prefix prefill; per
+ * layer one launch scatters K | V by (sample list, row map); one kernel masks the old episode's history rows and writes the key mask (prompt mask,
+ * 1 for the separator and every mapped row), posbase[b] = nv_b + T (Q + 1) and fresh[b] = 0: the next step consumes the sample's act_tok row, the
+ * action of history step T - 1. Other samples are not touched; the launch count does not depend on n_r; eager also with "graphs". */
+int vima_seq_decode_chunk(VimaHandle* h, const float* obs_tok, const float* act_tok, int step, int T, int B, float* out, vima_stream_t stream);
+int vima_seq_decode_restart_history(VimaHandle* h, const uint8_t* restart, int B, const float* prompt, int64_t stride_b, int64_t stride_l,
+                                    const uint8_t* prompt_mask, int Lp, const float* hist_obs, const float* hist_act, int T, float* out,
+                                    vima_stream_t stream);
+int vima_seq_history_room(VimaHandle* h, int32_t* steps_host);
 
 /* ---- image preprocessing in front of the policy ------------------------------------------- */
 /* The per-object work of prepare_obs / prepare_prompt (/root/reference/scripts/example.py:374-473 and :243-371; numpy +
@@ -547,6 +586,14 @@ int vima_op_seq_embed_step(VimaHandle* h, const float* obs_tok, const float* act
                            int has_act, int E, float* x32, float* xT, uint8_t* cache_mask, int32_t* posbase, uint8_t* fresh, vima_stream_t stream);
 int vima_op_seq_restart(VimaHandle* h, const int32_t* list, int n, int lo, int hi, int n_pos, uint8_t* cache_mask, uint8_t* fresh,
                         vima_stream_t stream);
+/* launch_seq_embed_chunk: obs_tok [T, B, Q, E], act_tok [T, B, E] (has_act) / [T - 1, B, E] -> x32 and xT (optional) [B, T (Q + 1) - (1 - has_act), E];
+ * writes cache_mask[b][row0 .. row0 + rows), advances posbase, consumes fresh. launch_seq_history_install: mask [n, L], list [n], rowmap [L]
+ * (DEVICE arrays; rowmap values must lie in [0, n_pos)): cache_mask[list[r]][lo .. hi) = 0, then [rowmap[l]] = mask[r][l]; posbase[list[r]] = the
+ * valid rows; fresh[list[r]] = 0. Rows and samples the kernels do not write come back unchanged. */
+int vima_op_seq_embed_chunk(VimaHandle* h, const float* obs_tok, const float* act_tok, const float* pos_table, int n_pos, int row0, int T, int B, int Q,
+                            int has_act, int E, float* x32, float* xT, uint8_t* cache_mask, int32_t* posbase, uint8_t* fresh, vima_stream_t stream);
+int vima_op_seq_history_install(VimaHandle* h, const uint8_t* mask, const int32_t* list, const int32_t* rowmap, int n, int L, int lo, int hi, int n_pos,
+                                uint8_t* cache_mask, int32_t* posbase, uint8_t* fresh, vima_stream_t stream);
 /* precision FP8: the calibrated activation scales (dequantisation scale = headroom x max |x| / 448, see VIMA_PRECISION_FP8) of group 0 the T5 stack [12 layers][4 sites:
  * stream before qkv, attention context, stream before wi, ReLU hidden], 1 the ViT [4 blocks][4 sites: ln_1 output, attention output,
  * ln_2 output, QuickGELU hidden], 2 the decoder's prompt K/V projection [1]; returns their number (0 before that group's calibrating

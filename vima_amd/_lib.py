@@ -104,6 +104,9 @@ PROTOTYPES = {
     "vima_seq_prefill": (ctypes.c_int, [vp, vp, c_i64, c_i64, vp, ctypes.c_int, ctypes.c_int, vp]),
     "vima_seq_decode_step": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]),
     "vima_seq_decode_restart": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, c_i64, c_i64, vp, ctypes.c_int, vp]),
+    "vima_seq_decode_chunk": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),
+    "vima_seq_decode_restart_history": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, c_i64, c_i64, vp, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp]),
+    "vima_seq_history_room": (ctypes.c_int, [vp, ctypes.POINTER(c_i32)]),
     "vima_action_head": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, vp]),
     "vima_action_embed": (ctypes.c_int, [vp, vp * 4, ctypes.c_int, vp, vp]),
     "vima_action_select": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.POINTER(c_f32), vp * 4, vp, vp, vp, vp]),
@@ -141,6 +144,9 @@ PROTOTYPES = {
     "vima_op_seq_embed_prefill": (ctypes.c_int, [vp, vp, c_i64, c_i64, vp, vp, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp]),
     "vima_op_seq_embed_step": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp]),
     "vima_op_seq_restart": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp]),
+    "vima_op_seq_embed_chunk": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               vp, vp, vp, vp, vp, vp]),
+    "vima_op_seq_history_install": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]),
     "vima_t5_bucket": (ctypes.c_int, [ctypes.c_int]),
     "vima_fp8_e4m3_encode": (None, [vp, vp, c_i64]),
     "vima_set_option": (ctypes.c_int, [vp, ctypes.c_char_p, c_i64]),

@@ -166,25 +166,25 @@ class _BaselinePolicy(VIMAPolicy):
         decoder-only policies fill their cache with `seq_prefill` and step with `seq_step`."""
         if self.KIND != "flamingo":
             raise NotImplementedError("forward_steps needs the XAttnGPT episode caches (VIMAPolicy / VIMAFlamingoPolicy); the decoder-only "
-                                      "policies decode incrementally with seq_prefill / seq_step")
+                                      "policies take T env steps in one pass with seq_steps (after seq_prefill)")
         ones = torch.ones(obs_token.shape[:3], dtype=torch.bool, device=self._device)
         return VIMAPolicy.forward_steps(self, obs_token, ones, action_token, prompt_token, prompt_token_mask, step)
 
     def restart_samples(self, restart, prompt_token, prompt_token_mask, history=None):
         """VIMAPolicy.restart_samples; `history` = (obs_token [T,n_r,Q,E], action_token [T-1,n_r,E] | None) -- every token valid -- or the
-        three-tuple of VIMAPolicy with its mask. VIMAFlamingoPolicy only; the decoder-only policies restart with `seq_restart`."""
+        three-tuple of VIMAPolicy with its mask. VIMAFlamingoPolicy only; the decoder-only policies restart with `seq_restart` (which takes `history=` too)."""
         if history is None:
             return VIMAPolicy.restart_samples(self, restart, prompt_token, prompt_token_mask)
         if self.KIND != "flamingo":
             raise NotImplementedError("restart_samples(history=) needs the XAttnGPT episode caches (VIMAPolicy / VIMAFlamingoPolicy); the "
-                                      "decoder-only policies restart with seq_restart and refill with seq_step")
+                                      "decoder-only policies install a history with seq_restart(history=)")
         if len(history) == 2:
             history = (history[0], torch.ones(history[0].shape[:3], dtype=torch.bool, device=self._device), history[1])
         return VIMAPolicy.restart_samples(self, restart, prompt_token, prompt_token_mask, history)
 
     def history_room(self) -> int:
         if self.KIND != "flamingo":
-            raise NotImplementedError("history_room: VIMAPolicy / VIMAFlamingoPolicy only (the decoder-only policies have seq_* and steps_left)")
+            raise NotImplementedError("history_room: VIMAPolicy / VIMAFlamingoPolicy only (the decoder-only policies have seq_history_room)")
         return VIMAPolicy.history_room(self)
 
     # ------------------------------------------------------------------ incremental decoding (gpt / gato)
@@ -251,14 +251,53 @@ class _BaselinePolicy(VIMAPolicy):
         self._seq_t = step + 1
         return out
 
-    def seq_restart(self, restart, prompt_token, prompt_token_mask):
+    def seq_steps(self, obs_token, action_token=None):
+        """T env steps of the episode batch as ONE pass (`vima_seq_decode_chunk`): obs_token [T, B, Q, E] ([T, B, E] for GPT); action_token
+        [T, B, E] once the batch has taken a step (row 0 = the action of the step before the chunk), [T-1, B, E] before its first step (None for
+        T = 1). Returns [T, B, E], row j == what `seq_step` returns for step j of the chunk (up to summation order; T = 1 IS `seq_step`, bit for
+        bit). Resumes a recorded rollout, or scores a recorded prefix teacher-forced before stepping on. IndexError, nothing changed, when the
+        chunk does not fit: linear cache "room for N more steps"; with `seq_ring` the chunk is one unit of the ring (never split, it skips the
+        tail whole), so it can be refused -- naming the sample -- where single steps still pass."""
+        self._seq_only("seq_steps")
+        Q, E = self._obj_xf_num_queries, self.embed_dim
+        if obs_token.dim() == 3 and Q == 1:
+            obs_token = obs_token.unsqueeze(2)
+        if obs_token.dim() != 4 or obs_token.shape[2] != Q or obs_token.shape[3] != E or obs_token.dtype != torch.float32:
+            raise AssertionError(f"obs_token must be float32 [T, B, {Q}, {E}], got {obs_token.dtype} {tuple(obs_token.shape)}")
+        T, B = obs_token.shape[0], obs_token.shape[1]
+        if T < 1:
+            raise AssertionError("seq_steps: at least one step")
+        step = getattr(self, "_seq_t", None)
+        if step is None:
+            raise _lib.VimaError("seq_steps: no running episode (call seq_prefill first)")
+        n_act = T if step > 0 else T - 1
+        if n_act > 0:
+            if action_token is None:
+                raise AssertionError(f"seq_steps: action_token [{n_act}, {B}, {E}] is required (the actions in front of / between the chunk's steps)")
+            if tuple(action_token.shape) != (n_act, B, E) or action_token.dtype != torch.float32:
+                raise AssertionError(f"action_token must be float32 [{n_act}, {B}, {E}], got {action_token.dtype} {tuple(action_token.shape)}")
+            action_token = action_token.to(device=self._device).contiguous()
+        else:
+            action_token = None
+        obs_token = obs_token.to(device=self._device).contiguous()
+        out = torch.empty(T, B, E, dtype=torch.float32, device=self._device)
+        _lib.check(self._lib.vima_seq_decode_chunk(self._handle, _ptr(obs_token), _ptr(action_token), step, T, B, _ptr(out), self._stream()))
+        self._seq_t = step + T
+        return out
+
+    def seq_restart(self, restart, prompt_token, prompt_token_mask, history=None):
         """Per-sample episode restart inside the stepping batch: every sample with `restart[b]` true forgets its history, takes its new
         prompt from `prompt_token[:, b]` / `prompt_token_mask[b]` (same [Lp, B, E] / [B, Lp] layout and the same Lp as `seq_prefill`;
         other samples' rows are not read) and its next `seq_step` ignores its row of `prev_action_token`. All flagged samples are
         rebuilt in one batched prefill. The batch keeps stepping with `seq_step`; a restart does not give cache rows back
         (`steps_left`): when they run out, start over with `seq_prefill` -- unless option `seq_ring` is set: the restarted samples' rows
         then return to the ring, a restart takes no rows itself, and a batch whose samples are each restarted before their
-        `steps_left()` entry reaches 0 never calls `seq_prefill` again (`decode_ring` is VIMAPolicy's ring and is refused here)."""
+        `steps_left()` entry reaches 0 never calls `seq_prefill` again (`decode_ring` is VIMAPolicy's ring and is refused here).
+        history = (obs_token [T, n_r, Q, E], action_token [T-1, n_r, E] | None), n_r = the flagged samples in increasing order: the flagged
+        samples join the batch MID-episode -- T recorded env steps are installed in the cache rows of the batch's last T steps (one pass over
+        [prompt | sep | history]), the teacher-forced predictions [T, n_r, E] are returned, and the next `seq_step` consumes each sample's row
+        of `prev_action_token` (the action of history step T - 1). IndexError, nothing changed, when T > `seq_history_room()` or the sequence
+        exceeds n_positions. Without `history`: returns None."""
         self._seq_only("seq_restart")
         prompt_token, prompt_token_mask = self._seq_prompt(prompt_token, prompt_token_mask)
         flags = torch.as_tensor(restart).to(dtype=torch.uint8, device="cpu").contiguous()
@@ -267,8 +306,38 @@ class _BaselinePolicy(VIMAPolicy):
             raise AssertionError(f"restart must have one flag per sample ({B}), got {flags.numel()}")
         if not bool(prompt_token_mask[flags.bool().to(self._device)].any(dim=1).all()):
             raise IndexError("index out of range in self (a restarted sample has no valid prompt token: position id -1, vima_gato_policy.py:164)")
-        _lib.check(self._lib.vima_seq_decode_restart(self._handle, ctypes.c_void_p(flags.data_ptr()), B, _ptr(prompt_token),
-                                                     prompt_token.stride(1), prompt_token.stride(0), _ptr(prompt_token_mask), Lp, self._stream()))
+        if history is None:
+            _lib.check(self._lib.vima_seq_decode_restart(self._handle, ctypes.c_void_p(flags.data_ptr()), B, _ptr(prompt_token),
+                                                         prompt_token.stride(1), prompt_token.stride(0), _ptr(prompt_token_mask), Lp, self._stream()))
+            return None
+        Q, E = self._obj_xf_num_queries, self.embed_dim
+        obs_token, action_token = history
+        if obs_token.dim() == 3 and Q == 1:
+            obs_token = obs_token.unsqueeze(2)
+        n_r = int(flags.bool().sum())
+        if obs_token.dim() != 4 or tuple(obs_token.shape[1:]) != (n_r, Q, E) or obs_token.dtype != torch.float32:
+            raise AssertionError(f"history obs_token must be float32 [T, {n_r}, {Q}, {E}] (one column per flagged sample), got {obs_token.dtype} {tuple(obs_token.shape)}")
+        T = obs_token.shape[0]
+        if T > 1:
+            if action_token is None or tuple(action_token.shape) != (T - 1, n_r, E) or action_token.dtype != torch.float32:
+                raise AssertionError(f"history action_token must be float32 [{T - 1}, {n_r}, {E}]")
+            action_token = action_token.to(device=self._device).contiguous()
+        else:
+            action_token = None
+        obs_token = obs_token.to(device=self._device).contiguous()
+        out = torch.empty(T, n_r, E, dtype=torch.float32, device=self._device)
+        _lib.check(self._lib.vima_seq_decode_restart_history(
+            self._handle, ctypes.c_void_p(flags.data_ptr()), B, _ptr(prompt_token), prompt_token.stride(1), prompt_token.stride(0),
+            _ptr(prompt_token_mask), Lp, _ptr(obs_token), _ptr(action_token), T, _ptr(out), self._stream()))
+        return out
+
+    def seq_history_room(self) -> int:
+        """The largest T `seq_restart(..., history=)` accepts now: the most recent batch steps whose cache rows are all still there (without
+        `seq_ring`: the steps taken since `seq_prefill`). Host bookkeeping only."""
+        self._seq_only("seq_history_room")
+        room = ctypes.c_int32(0)
+        _lib.check(self._lib.vima_seq_history_room(self._handle, ctypes.byref(room)))
+        return int(room.value)
 
     # steps_left() is VIMAPolicy's: on a gpt / gato handle vima_decode_steps_left reports the episode of seq_prefill / seq_step (all entries
     # equal: how many further seq_step calls fit into n_positions; with option seq_ring per sample: how many more would succeed if that sample

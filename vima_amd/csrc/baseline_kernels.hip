@@ -109,27 +109,29 @@ __global__ __launch_bounds__(256) void broadcast_rows_kernel(const float* __rest
 //   l == Lp : prompt_sep_token                                 key mask 1, position nv
 //   else j = l-Lp-1, t = j / (Q+1), s = j % (Q+1): s < Q -> obs token (t, b, s), else action token (t, b); position nv + 1 + j
 // with nv = number of valid prompt tokens of sample b. One wave per row; nv is recomputed per wave (Lp <= 512 bytes).
+// list (optional, DEVICE array [B]): sample b of the call reads row list[b] of prompt / pmask; obs_tok / act_tok stay indexed by b.
 // ---------------------------------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void seq_embed_kernel(const float* __restrict__ prompt, long long sb, long long sl,
                                                         const uint8_t* __restrict__ pmask, const float* __restrict__ sep,
                                                         const float* __restrict__ obs_tok, const float* __restrict__ act_tok,
                                                         const float* __restrict__ pos_table, int n_pos, float* x32, T* xT,
-                                                        uint8_t* mask, int B, int L, int Lp, int Q, int E) {
+                                                        uint8_t* mask, const int* __restrict__ list, int B, int L, int Lp, int Q, int E) {
   const int lane = threadIdx.x & 63;
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= (long long)B * L) return;
   const int b = (int)(row / L), l = (int)(row % L);
+  const int bp = list ? list[b] : b;   // the sample's row of prompt / pmask (vima_seq_decode_restart_history: a compact list of a batch's samples)
   float cnt = 0.f;
-  for (int j = lane; j < Lp; j += 64) cnt += pmask[(long long)b * Lp + j] ? 1.f : 0.f;
+  for (int j = lane; j < Lp; j += 64) cnt += pmask[(long long)bp * Lp + j] ? 1.f : 0.f;
   const int nv = (int)wave_sum(cnt);
   const float* src;
   int pos;
   uint8_t m = 1;
   if (l < Lp) {
-    src = prompt + (long long)b * sb + (long long)l * sl;
+    src = prompt + (long long)bp * sb + (long long)l * sl;
     pos = l < nv ? l : nv - 1;
-    m = pmask[(long long)b * Lp + l] ? 1 : 0;
+    m = pmask[(long long)bp * Lp + l] ? 1 : 0;
   } else if (l == Lp) {
     src = sep;
     pos = nv;
@@ -247,6 +249,49 @@ __global__ __launch_bounds__(256) void seq_embed_step_kernel(const float* __rest
   }
 }
 
+// The rows of T env steps as ONE chunk (vima_seq_decode_chunk), Ln = T (Q + 1) - (1 - has_act) per sample at cache rows [row0, row0 + Ln): slot u is
+// [a, o^1 .. o^Q] at u (Q + 1) - (1 - has_act); the first slot of batch step 0 (has_act = 0) has no action row. obs_tok [T, B, Q, E]; act_tok
+// [T, B, E] (has_act) or [T - 1, B, E]: row j is the action in front of slot j (has_act) or slot j + 1. One workgroup per sample. Every token of
+// this path is valid, so the position ids are posbase[b] + row index and need no scan; a restarted sample (fresh[b], has_act) has only the chunk's
+// FIRST action row masked: zeros are embedded at the id posbase[b] (as seq_embed_step_kernel does; act_tok is not read), it takes no id and the rows
+// behind it count from posbase[b]. Ids are clamped to the table like seq_embed_kernel's. Writes the key-mask bytes of the chunk's rows, advances
+// posbase by the valid rows and consumes fresh.
+template <typename T>
+__global__ __launch_bounds__(256) void seq_embed_chunk_kernel(const float* __restrict__ obs_tok, const float* __restrict__ act_tok,
+                                                              const float* __restrict__ pos_table, int n_pos, float* x32, T* xT,
+                                                              uint8_t* cache_mask, int* posbase, uint8_t* fresh, int row0, int Tn, int B, int Q,
+                                                              int has_act, int E) {
+  const int b = blockIdx.x;
+  const int lead = has_act ? 0 : 1;
+  const int Ln = Tn * (Q + 1) - lead;
+  const int base = posbase[b];
+  const int skip = (has_act && fresh[b]) ? 1 : 0;
+  __syncthreads();   // every thread holds the old state before it is advanced
+  if (threadIdx.x == 0) {
+    posbase[b] = base + Ln - skip;
+    fresh[b] = 0;
+  }
+  for (int i = threadIdx.x; i < Ln; i += 256) cache_mask[(long long)b * n_pos + row0 + i] = (uint8_t)((i == 0 && skip) ? 0 : 1);
+  const int e4 = E >> 2;
+  for (int i = threadIdx.x; i < Ln * e4; i += 256) {
+    const int l = i / e4, c = (i % e4) * 4;
+    const int u = (l + lead) / (Q + 1), s = (l + lead) % (Q + 1);
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (s == 0) {
+      if (!(l == 0 && skip)) a = *reinterpret_cast<const float4*>(act_tok + ((long long)(u - lead) * B + b) * E + c);
+    } else {
+      a = *reinterpret_cast<const float4*>(obs_tok + (((long long)u * B + b) * Q + (s - 1)) * E + c);
+    }
+    int p = base + l - (l > 0 ? skip : 0);
+    p = p < 0 ? 0 : (p >= n_pos ? n_pos - 1 : p);
+    const float4 pp = *reinterpret_cast<const float4*>(pos_table + (long long)p * E + c);
+    const float4 o = make_float4(a.x + pp.x, a.y + pp.y, a.z + pp.z, a.w + pp.w);
+    const long long off = ((long long)b * Ln + l) * E + c;
+    *reinterpret_cast<float4*>(x32 + off) = o;
+    store4(xT + off, o);
+  }
+}
+
 // Per-sample restart: the listed samples forget their history rows [lo, hi) (every cached key of the old episode masked; rows [0, lo) are
 // rewritten by the prefill of the new prompt) and their next action slot is marked absent. One workgroup per listed sample.
 __global__ __launch_bounds__(256) void seq_restart_kernel(const int* __restrict__ list, uint8_t* cache_mask, uint8_t* fresh, int lo, int hi,
@@ -254,6 +299,32 @@ __global__ __launch_bounds__(256) void seq_restart_kernel(const int* __restrict_
   const int b = list[blockIdx.x];
   for (int i = lo + threadIdx.x; i < hi; i += 256) cache_mask[(long long)b * n_pos + i] = 0;
   if (threadIdx.x == 0) fresh[b] = 1;
+}
+
+// The episode state of an installed history (vima_seq_decode_restart_history), one workgroup per listed sample b = list[r]: what seq_restart_kernel
+// does to the old episode (rows [lo, hi) masked), then the key mask of the L compact rows of the call ([prompt | sep | history], mask [n, L]) at the
+// cache rows rowmap[l] (DEVICE array [L], shared by the samples; the identity over the prefix), posbase[b] = the number of valid rows (nv + 1 + the
+// history's) and fresh[b] = 0: the sample is mid-episode and its next step consumes its action token.
+__global__ __launch_bounds__(256) void seq_history_install_kernel(const uint8_t* __restrict__ mask, const int* __restrict__ list,
+                                                                  const int* __restrict__ rowmap, int L, int lo, int hi, int n_pos,
+                                                                  uint8_t* cache_mask, int* posbase, uint8_t* fresh) {
+  __shared__ float part[4];
+  const int r = blockIdx.x, b = list[r];
+  for (int i = lo + threadIdx.x; i < hi; i += 256) cache_mask[(long long)b * n_pos + i] = 0;
+  __syncthreads();   // the mapped rows below lie inside [lo, hi): written after the clearing
+  float cnt = 0.f;
+  for (int l = threadIdx.x; l < L; l += 256) {
+    const uint8_t mk = mask[(long long)r * L + l] ? 1 : 0;
+    cache_mask[(long long)b * n_pos + rowmap[l]] = mk;
+    cnt += (float)mk;
+  }
+  cnt = wave_sum(cnt);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    posbase[b] = (int)((part[0] + part[1]) + (part[2] + part[3]));
+    fresh[b] = 0;
+  }
 }
 
 // K | V of a prefill to the episode cache: rows [n * L] of width N at row stride ld_in (the k | v columns of a dense q | k | v buffer) -> rows
@@ -309,16 +380,16 @@ int launch_broadcast_rows(const float* src, float* out, long long rows, int E, i
 
 int launch_seq_embed(const float* prompt, long long sb, long long sl, const uint8_t* pmask, const float* sep, const float* obs_tok,
                      const float* act_tok, const float* pos_table, int n_pos, float* x32, void* xT, uint8_t* mask, int B, int L, int Lp,
-                     int Q, int E, bool is_bf16, hipStream_t st) {
+                     int Q, int E, bool is_bf16, hipStream_t st, const int* list) {
   if (B <= 0 || L <= 0) return 0;
   if (E % 4 || sb % 4 || sl % 4) return (int)hipErrorInvalidValue;
   const long long rows = (long long)B * L;
   if (is_bf16)
     hipLaunchKernelGGL(seq_embed_kernel<bf16_t>, dim3(nblk(rows, 4)), dim3(256), 0, st, prompt, sb, sl, pmask, sep, obs_tok, act_tok, pos_table,
-                       n_pos, x32, (bf16_t*)xT, mask, B, L, Lp, Q, E);
+                       n_pos, x32, (bf16_t*)xT, mask, list, B, L, Lp, Q, E);
   else
     hipLaunchKernelGGL(seq_embed_kernel<float>, dim3(nblk(rows, 4)), dim3(256), 0, st, prompt, sb, sl, pmask, sep, obs_tok, act_tok, pos_table,
-                       n_pos, x32, (float*)xT, mask, B, L, Lp, Q, E);
+                       n_pos, x32, (float*)xT, mask, list, B, L, Lp, Q, E);
   return (int)hipGetLastError();
 }
 
@@ -348,6 +419,31 @@ int launch_seq_embed_step(const float* obs_tok, const float* act_tok, const floa
   else
     hipLaunchKernelGGL(seq_embed_step_kernel<float>, dim3(B), dim3(256), 0, st, obs_tok, act_tok, pos_table, n_pos, x32, (float*)xT, cache_mask,
                        posbase, fresh, row0, Q, has_act, E);
+  return (int)hipGetLastError();
+}
+
+int launch_seq_embed_chunk(const float* obs_tok, const float* act_tok, const float* pos_table, int n_pos, float* x32, void* xT,
+                           uint8_t* cache_mask, int* posbase, uint8_t* fresh, int row0, int T, int B, int Q, int has_act, int E, bool is_bf16,
+                           hipStream_t st) {
+  if (B <= 0) return 0;
+  const long long Ln = (long long)T * (Q + 1) - (has_act ? 0 : 1);
+  if (T < 1 || Q < 1 || E <= 0 || E % 4 || row0 < 0 || row0 + Ln > n_pos || Ln * (E / 4) > 0x7fffffffLL || !obs_tok || !pos_table || !x32 || !xT ||
+      !cache_mask || !posbase || !fresh || (Ln > Q && !act_tok))
+    return (int)hipErrorInvalidValue;
+  if (is_bf16)
+    hipLaunchKernelGGL(seq_embed_chunk_kernel<bf16_t>, dim3(B), dim3(256), 0, st, obs_tok, act_tok, pos_table, n_pos, x32, (bf16_t*)xT, cache_mask,
+                       posbase, fresh, row0, T, B, Q, has_act ? 1 : 0, E);
+  else
+    hipLaunchKernelGGL(seq_embed_chunk_kernel<float>, dim3(B), dim3(256), 0, st, obs_tok, act_tok, pos_table, n_pos, x32, (float*)xT, cache_mask,
+                       posbase, fresh, row0, T, B, Q, has_act ? 1 : 0, E);
+  return (int)hipGetLastError();
+}
+
+int launch_seq_history_install(const uint8_t* mask, const int* list, const int* rowmap, int n, int L, int lo, int hi, int n_pos,
+                               uint8_t* cache_mask, int* posbase, uint8_t* fresh, hipStream_t st) {
+  if (n <= 0) return 0;
+  if (L <= 0 || L > n_pos || lo < 0 || hi > n_pos || !mask || !list || !rowmap || !cache_mask || !posbase || !fresh) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(seq_history_install_kernel, dim3(n), dim3(256), 0, st, mask, list, rowmap, L, lo, hi, n_pos, cache_mask, posbase, fresh);
   return (int)hipGetLastError();
 }
 

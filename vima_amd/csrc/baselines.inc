@@ -157,8 +157,9 @@ int baseline_ready(VimaHandle* h, const char* fn) {
 // row-remap epilogue: the attention of these rows reads the dense q | k | v of the call, so the remap would need the k | v columns twice (a
 // second GEMM launch per layer), while the copy is one HBM-bound pass over 2E columns, leaves the arithmetic of `vima_seq_decode` untouched
 // (same GEMM, same attention launch: the prefilled rows carry its bits) and serves the full prefill and the listed restart alike.
+// kv_rowmap (vima_seq_decode_restart_history; DEVICE array [L], needs kv_list): row l goes to cache row kv_rowmap[l] instead of l -- still one launch per layer.
 int hfgpt_stack(Run& R, float* x32, void* xT, const uint8_t* mask, int B, int L, void* kv_cache = nullptr, const int* kv_list = nullptr,
-                int kv_B = 0, int kv_Lmax = 0) {
+                int kv_B = 0, int kv_Lmax = 0, const int* kv_rowmap = nullptr) {
   VimaHandle* h = R.h;
   const int E = h->cfg.embed_dim, Hs = h->cfg.sattn_n_heads, rq = B * L;
   void* qkv = R.wsT((size_t)rq * 3 * E);
@@ -172,7 +173,10 @@ int hfgpt_stack(Run& R, float* x32, void* xT, const uint8_t* mask, int B, int L,
   for (int i = 0; i < h->cfg.xf_n_layers; ++i) {
     auto& D = h->dec[i];
     R.linear(xT, E, D.c_attn, rq, ACT_NONE, nullptr, 0, nullptr, 0, nullptr, 0, qkv, 3 * E);
-    if (kv_cache)
+    if (kv_cache && kv_rowmap)
+      OTHER(R, launch_kv_scatter_rows(R.offT(qkv, E), 3 * E, R.offT(kv_cache, (long long)i * kv_B * kv_Lmax * 2 * E), kv_list, kv_rowmap, B, L, kv_Lmax,
+                                      2 * E, h->bf16, R.st), "kv_scatter_rows");
+    else if (kv_cache)
       OTHER(R, launch_seq_kv_store(R.offT(qkv, E), 3 * E, R.offT(kv_cache, (long long)i * kv_B * kv_Lmax * 2 * E), kv_list, B, L, 2 * E, kv_Lmax,
                                    h->bf16, R.st), "seq_kv_store");
     AttnArgs s;   // Attention._attn (gpt/gpt.py:268-301): /sqrt(d), w*b + -1e4*(1-b), + (1-mask)*finfo.min

@@ -277,7 +277,7 @@ int launch_broadcast_rows(const float* src, float* out, long long rows, int E, i
 // decoder-only input [B,L,E]: [prompt | sep | (Q obs tokens, action)*] + positions_embed, key mask [B,L]
 int launch_seq_embed(const float* prompt, long long sb, long long sl, const uint8_t* pmask, const float* sep, const float* obs_tok,
                      const float* act_tok, const float* pos_table, int n_pos, float* x32, void* xT, uint8_t* mask, int B, int L, int Lp,
-                     int Q, int E, bool is_bf16, hipStream_t st);
+                     int Q, int E, bool is_bf16, hipStream_t st, const int* list = nullptr);
 // incremental decoding of the decoder-only policies. Episode state on the device: cache_mask [B][n_pos] (key mask at the cache's row stride),
 // posbase[b] (position id of sample b's next valid row), fresh[b] (1 after a restart: the next action slot is absent).
 // rows [0, Lp] ([prompt | sep] + positions) of n samples -> x32 / xT / mask [n, Lp + 1]; block r comes from sample list[r] (DEVICE array,
@@ -290,6 +290,15 @@ int launch_seq_embed_prefill(const float* prompt, long long sb, long long sl, co
 int launch_seq_embed_step(const float* obs_tok, const float* act_tok, const float* pos_table, int n_pos, float* x32, void* xT,
                           uint8_t* cache_mask, int* posbase, uint8_t* fresh, int row0, int B, int Q, int has_act, int E, bool is_bf16,
                           hipStream_t st);
+// the rows of T env steps as one chunk: T (Q + 1) rows per sample (one fewer without has_act: the first slot of batch step 0 has no action row) at
+// cache rows [row0, ..); obs_tok [T, B, Q, E], act_tok [T, B, E] (has_act) / [T - 1, B, E]. No row limit beyond row0 + rows <= n_pos.
+int launch_seq_embed_chunk(const float* obs_tok, const float* act_tok, const float* pos_table, int n_pos, float* x32, void* xT,
+                           uint8_t* cache_mask, int* posbase, uint8_t* fresh, int row0, int T, int B, int Q, int has_act, int E, bool is_bf16,
+                           hipStream_t st);
+// installed history of the n listed samples: cache_mask[list[r]][lo .. hi) = 0, then cache_mask[list[r]][rowmap[l]] = mask[r][l] (l < L),
+// posbase[list[r]] = the number of valid rows, fresh[list[r]] = 0
+int launch_seq_history_install(const uint8_t* mask, const int* list, const int* rowmap, int n, int L, int lo, int hi, int n_pos,
+                               uint8_t* cache_mask, int* posbase, uint8_t* fresh, hipStream_t st);
 // for the n listed samples (DEVICE array): cache_mask[b][lo .. hi) = 0, fresh[b] = 1
 int launch_seq_restart(const int* list, int n, uint8_t* cache_mask, uint8_t* fresh, int lo, int hi, int n_pos, hipStream_t st);
 // rows [n * L] of width N (operand type, row stride ld_in) -> rows [0, L) of sample list[r]'s (optional: r's) block of a cache of Lmax rows per sample

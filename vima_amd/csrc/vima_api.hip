@@ -2724,9 +2724,17 @@ int vima_seq_prefill(VimaHandle* h, const float* prompt, int64_t stride_b, int64
                                     h->ep_poscnt, nullptr, B, Lp, E, h->bf16, R.st), "seq_embed_prefill");
   if (hfgpt_stack(R, x32, xT, mask, B, L, h->ep_kv, nullptr, B, Lmax)) return R.err;
   h->seq_live = true; h->seq_next = 0; h->seq_row = L;
+  h->ep_slots.clear();   // the slot record of vima_seq_decode_step / _chunk (GPT / GATO handles never run vima_decode_step: the record is theirs)
   h->seq_hw = L; h->seq_age.assign((size_t)B, 0);   // option seq_ring: write pointer (seq_row) = high-water mark = P0, every age 0
   h->ep_B = B; h->ep_Q = rgb_tokens_per_image(h->cfg.policy_kind); h->ep_Lp = Lp; h->ep_Lmax = Lmax;
   return 0;
+}
+
+// One record per env step of a successful vima_seq_decode_step / _chunk (host bookkeeping only): (first obs row, ring rows advanced). T slots of
+// [action row, Q obs rows] from `row` on; the first slot of batch step 0 has no action row, and a chunk's skipped tail counts with its first step.
+static void seq_record(VimaHandle* h, int row, int has_act, int T, int Q, int advance) {
+  for (int u = 0; u < T; ++u) h->ep_slots.push_back({row + u * (Q + 1) + has_act, u == 0 ? advance - (T - 1) * (Q + 1) : Q + 1});
+  if ((int)h->ep_slots.size() > h->ep_Lmax) h->ep_slots.erase(h->ep_slots.begin(), h->ep_slots.end() - h->ep_Lmax);
 }
 
 static int seq_step_launch(VimaHandle* h, const float* obs_tok, const float* act_tok, int B, int Q, int has_act, int row, int Lk, int win_end,
@@ -2783,6 +2791,7 @@ int vima_seq_decode_step(VimaHandle* h, const float* obs_tok, const float* act_t
   }, warm);
   if (!rc) {
     h->seq_next = step + 1; h->seq_row = row + Lq;
+    seq_record(h, row, has_act, 1, Q, advance);
     if (ring) {
       for (int& a : h->seq_age) a += advance;
       h->seq_hw = Lk;
@@ -2819,6 +2828,146 @@ int vima_seq_decode_restart(VimaHandle* h, const uint8_t* restart, int B, const 
   hfgpt_stack(R, x32, xT, mask, n_r, L, h->ep_kv, list, B, Lmax);
   if (!R.err && h->seq_ring)
     for (int b : h->restart_list) h->seq_age[b] = 0;   // the sample's ring rows are dead: later steps may overwrite them (a restart itself takes none)
+  return R.err;
+}
+
+// T env steps of the running episode batch as ONE pass of hfgpt_step_stack: Lq = T (Q + 1) rows per sample (one fewer at batch step 0) at one row
+// offset -- one unit of the ring -- instead of T passes of Q + 1 rows; 1 / T of the launches. T = 1 IS vima_seq_decode_step (graph keys included).
+// A longer chunk runs eager also with option "graphs" (a rare call: prefill, resume; every (T, row, keys read) would be a graph of its own); the
+// step graphs captured before stay valid -- they read the episode state from the device and their plan from the key.
+int vima_seq_decode_chunk(VimaHandle* h, const float* obs_tok, const float* act_tok, int step, int T, int B, float* out, vima_stream_t stream) {
+  if (T == 1) return vima_seq_decode_step(h, obs_tok, act_tok, step, B, out, stream);
+  const char* fn = "vima_seq_decode_chunk";
+  if (int e = seq_ready(h, fn)) return e;
+  if (!obs_tok || !out) return fail("vima_seq_decode_chunk: null argument");
+  if (step < 0 || T < 1 || B <= 0) return fail("vima_seq_decode_chunk: step must be >= 0, T >= 1 and B > 0");
+  if (!(h->seq_live && h->seq_next == step && h->ep_B == B))
+    return fail("vima_seq_decode_chunk: step " + std::to_string(step) + " of " + std::to_string(B) + " samples does not continue the episode state (" +
+                (h->seq_live ? "next step " + std::to_string(h->seq_next) + " of " + std::to_string(h->ep_B) + " samples" : std::string("no episode")) +
+                "); start an episode with vima_seq_prefill");
+  if (!act_tok) return fail("vima_seq_decode_chunk: the action tokens between the chunk's steps are required");
+  const int has_act = step > 0 ? 1 : 0, Q = h->ep_Q, Lmax = h->ep_Lmax, E = h->cfg.embed_dim;
+  const bool ring = h->seq_ring != 0;
+  const long long Lq64 = (long long)T * (Q + 1) - (has_act ? 0 : 1);
+  int row = h->seq_row, advance = 0, win_end = 0;
+  if (!ring) {
+    if (row + Lq64 > Lmax)
+      return fail("vima_seq_decode_chunk: " + std::to_string(T) + " steps from step " + std::to_string(step) + " need " + std::to_string(row + Lq64) +
+                  " cache rows > n_positions " + std::to_string(Lmax) + " (room for " + std::to_string((Lmax - row + (has_act ? 0 : 1)) / (Q + 1)) +
+                  " more steps)", 34);
+    advance = (int)Lq64;
+  } else {   // the chunk is ONE unit of the ring: never split, legal iff every row it overwrites or skips is dead for every sample
+    const int P0 = h->ep_Lp + 1;
+    if (Lq64 > Lmax) return fail("vima_seq_decode_chunk: a chunk of " + std::to_string(Lq64) + " rows is longer than n_positions " + std::to_string(Lmax), 34);
+    const RingStep rs = seq_ring_next(h->seq_row, (int)Lq64, P0, Lmax);   // a chunk longer than the ring advances more than R rows: refused below
+    for (int b = 0; b < B; ++b)
+      if (h->seq_age[b] + rs.advance > Lmax - P0)
+        return fail("vima_seq_decode_chunk: the episode of sample " + std::to_string(b) + " is longer than the ring behind its prompt (" +
+                    std::to_string(h->seq_age[b]) + " + " + std::to_string(rs.advance) + " ring rows > n_positions " + std::to_string(Lmax) + " - " +
+                    std::to_string(P0) + "): restart it with vima_seq_decode_restart, or take fewer steps at once (a chunk skips the ring's tail as ONE unit)", 34);
+    row = rs.row; advance = rs.advance; win_end = row + (int)Lq64;
+  }
+  const int Lq = (int)Lq64;
+  const int Lk = ring && h->seq_hw > row + Lq ? h->seq_hw : row + Lq;
+  Run R{h, (hipStream_t)stream};
+  float* x32 = R.ws<float>((size_t)B * Lq * E);
+  void* xT = R.wsT((size_t)B * Lq * E);
+  if (R.err) return R.err;
+  OTHER(R, launch_seq_embed_chunk(obs_tok, act_tok, h->pos_emb, Lmax, x32, xT, h->ep_mask, h->ep_poscnt, h->ep_fresh, row, T, B, Q, has_act, E, h->bf16,
+                                  R.st), "seq_embed_chunk");
+  if (hfgpt_step_stack(R, x32, xT, B, Lq, row, Lmax, Lk, win_end)) return R.err;
+  OTHER(R, launch_gather_pred(x32, out, T, B, Q, Lq, E, R.st, has_act), "gather_pred");   // the last obs row of every slot
+  if (R.err) return R.err;
+  h->seq_next = step + T; h->seq_row = row + Lq;
+  seq_record(h, row, has_act, T, Q, advance);
+  if (ring) {
+    for (int& a : h->seq_age) a += advance;
+    h->seq_hw = Lk;
+  }
+  return 0;
+}
+
+// The largest history vima_seq_decode_restart_history can install now: the batch steps whose rows are all still there. Linear cache: every step since
+// the prefill; ring: the last r steps whose advances sum to at most R (a sample restarted right before them would still be legal now).
+static int seq_history_room(const VimaHandle* h) {
+  if (!h->seq_ring) return (int)h->ep_slots.size();
+  const int R = h->ep_Lmax - (h->ep_Lp + 1);
+  int r = 0, sum = 0;
+  for (int j = (int)h->ep_slots.size() - 1; j >= 0 && sum + h->ep_slots[j].adv <= R; --j) { sum += h->ep_slots[j].adv; ++r; }
+  return r;
+}
+
+int vima_seq_history_room(VimaHandle* h, int32_t* steps_host) {
+  if (int e = seq_ready(h, "vima_seq_history_room")) return e;
+  if (!steps_host) return fail("vima_seq_history_room: null argument");
+  if (!h->seq_live) return fail("vima_seq_history_room: no running episode batch (start one with vima_seq_prefill)");
+  *steps_host = seq_history_room(h);
+  return 0;
+}
+
+// vima_seq_decode_restart with a history: ONE full pass of the vima_seq_decode form over the n_r flagged samples, [prompt | sep | o_0, a_0, .., o_{T-1}],
+// L = Lp + T (Q + 1) rows through hfgpt_stack, in place of the restart's prefix prefill. Per layer the K | V rows are scattered by (sample list, row map)
+// in one launch: the prefix to rows [0, Lp], history step s to the cache rows batch step t - T + s wrote (t: the next batch step). Then one kernel
+// writes the episode state. 3 launches + one stack pass (one launch more than the plain restart), whatever n_r. Host: the samples' ring age becomes that of a sample restarted right before
+// batch step t - T.
+int vima_seq_decode_restart_history(VimaHandle* h, const uint8_t* restart, int B, const float* prompt, int64_t stride_b, int64_t stride_l,
+                                    const uint8_t* prompt_mask, int Lp, const float* hist_obs, const float* hist_act, int T, float* out,
+                                    vima_stream_t stream) {
+  if (T == 0) return vima_seq_decode_restart(h, restart, B, prompt, stride_b, stride_l, prompt_mask, Lp, stream);
+  const char* fn = "vima_seq_decode_restart_history";
+  if (int e = seq_ready(h, fn)) return e;
+  if (T < 0) return fail("vima_seq_decode_restart_history: T must be >= 0");
+  if (!restart || !prompt || !prompt_mask || !hist_obs || (T > 1 && !hist_act)) return fail("vima_seq_decode_restart_history: null argument");
+  if (!(h->seq_live && h->ep_B == B && h->ep_Lp == Lp))
+    return fail("vima_seq_decode_restart_history: no running episode batch with this B / Lp (start one with vima_seq_prefill)");
+  const int E = h->cfg.embed_dim, Q = h->ep_Q, Lmax = h->ep_Lmax, P0 = Lp + 1;
+  const int room = seq_history_room(h);
+  if (T > room)
+    return fail("vima_seq_decode_restart_history: a history of " + std::to_string(T) + " steps does not fit: room for " + std::to_string(room) +
+                " (the batch steps whose cache rows are all still there)", 34);
+  const long long L64 = (long long)Lp + (long long)T * (Q + 1);
+  if (L64 > h->cfg.n_positions)
+    return fail("vima_seq_decode_restart_history: sequence of " + std::to_string(L64) + " tokens (prompt, separator and " + std::to_string(T) +
+                " steps) exceeds n_positions " + std::to_string(h->cfg.n_positions), 34);
+  const int L = (int)L64;
+  std::vector<int> flagged;
+  for (int b = 0; b < B; ++b)
+    if (restart[b]) flagged.push_back(b);
+  const int n_r = (int)flagged.size();
+  if (n_r == 0) return 0;
+  // compact row l of the sequence -> cache row: the identity over the prefix; history step s sits in the slot of batch step t - T + s, its Q obs rows
+  // in the slot's obs rows and a_s in the action row of the NEXT slot (the first slot's own action row, if it has one, stays masked)
+  const VimaHandle::EpSlot* S = h->ep_slots.data() + (h->ep_slots.size() - (size_t)T);
+  std::vector<int> rowmap((size_t)L);
+  for (int l = 0; l <= Lp; ++l) rowmap[(size_t)l] = l;
+  int age = 0;
+  const int hi = h->seq_ring ? h->seq_hw : h->seq_row;
+  for (int s = 0; s < T; ++s) {
+    age += S[s].adv;
+    int* m = rowmap.data() + P0 + (size_t)s * (Q + 1);
+    for (int q = 0; q < Q; ++q) m[q] = S[s].obs_row + q;
+    if (s + 1 < T) m[Q] = S[s + 1].obs_row - 1;
+  }
+  for (int l = P0; l < L; ++l)
+    if (rowmap[(size_t)l] < P0 || rowmap[(size_t)l] >= hi) return fail("vima_seq_decode_restart_history: internal error: history row outside the written cache");
+  h->restart_list = flagged;
+  h->hist_rowmap = rowmap;
+  Run R{h, (hipStream_t)stream};
+  int* list = R.ws<int>((size_t)n_r);
+  int* hmap = R.ws<int>((size_t)L);
+  float* x32 = R.ws<float>((size_t)n_r * L * E);
+  void* xT = R.wsT((size_t)n_r * L * E);
+  uint8_t* mask = R.ws<uint8_t>((size_t)n_r * L);
+  if (R.err) return R.err;
+  HIPCK(hipMemcpyAsync(list, h->restart_list.data(), (size_t)n_r * sizeof(int), hipMemcpyHostToDevice, R.st));
+  HIPCK(hipMemcpyAsync(hmap, h->hist_rowmap.data(), (size_t)L * sizeof(int), hipMemcpyHostToDevice, R.st));
+  OTHER(R, launch_seq_embed(prompt, stride_b, stride_l, prompt_mask, h->sep_token, hist_obs, hist_act, h->pos_emb, h->cfg.n_positions, x32, xT, mask,
+                            n_r, L, Lp, Q, E, h->bf16, R.st, list), "seq_embed");
+  if (hfgpt_stack(R, x32, xT, mask, n_r, L, h->ep_kv, list, B, Lmax, hmap)) return R.err;
+  if (out) OTHER(R, launch_gather_pred(x32 + (size_t)P0 * E, out, T, n_r, Q, L, E, R.st), "gather_pred");   // teacher-forced: the last obs row of every history step
+  OTHER(R, launch_seq_history_install(mask, list, hmap, n_r, L, P0, hi, Lmax, h->ep_mask, h->ep_poscnt, h->ep_fresh, R.st), "seq_history_install");
+  if (!R.err && h->seq_ring)
+    for (int b : h->restart_list) h->seq_age[b] = age;
   return R.err;
 }
 
@@ -3479,6 +3628,33 @@ int vima_op_seq_embed_step(VimaHandle* h, const float* obs_tok, const float* act
   OTHER(R, launch_seq_embed_step(obs_tok, act_tok, pos_table, n_pos, x32, oT, cache_mask, posbase, fresh, row0, B, Q, has_act, E, h->bf16, R.st),
         "vima_op_seq_embed_step: seq_embed_step");
   return xT ? op_widen(R, oT, xT, n) : R.err;
+}
+
+int vima_op_seq_embed_chunk(VimaHandle* h, const float* obs_tok, const float* act_tok, const float* pos_table, int n_pos, int row0, int T, int B, int Q,
+                            int has_act, int E, float* x32, float* xT, uint8_t* cache_mask, int32_t* posbase, uint8_t* fresh, vima_stream_t stream) {
+  const char* fn = "vima_op_seq_embed_chunk";
+  if (int e = op_begin(h, fn)) return e;
+  OP_REQ(obs_tok && pos_table && x32 && cache_mask && posbase && fresh, "null argument");
+  OP_REQ(T > 0 && B > 0 && Q > 0 && E > 0 && n_pos > 0 && (has_act == 0 || has_act == 1), "T, B, Q, E and n_pos must be positive, has_act 0 or 1");
+  Run R{h, (hipStream_t)stream};
+  const long long n = (long long)B * ((long long)T * (Q + 1) - (has_act ? 0 : 1)) * E;
+  void* oT = R.wsT((size_t)n);
+  if (R.err) return R.err;
+  OTHER(R, launch_seq_embed_chunk(obs_tok, act_tok, pos_table, n_pos, x32, oT, cache_mask, posbase, fresh, row0, T, B, Q, has_act, E, h->bf16, R.st),
+        "vima_op_seq_embed_chunk: seq_embed_chunk");
+  return xT ? op_widen(R, oT, xT, n) : R.err;
+}
+
+int vima_op_seq_history_install(VimaHandle* h, const uint8_t* mask, const int32_t* list, const int32_t* rowmap, int n, int L, int lo, int hi, int n_pos,
+                                uint8_t* cache_mask, int32_t* posbase, uint8_t* fresh, vima_stream_t stream) {
+  const char* fn = "vima_op_seq_history_install";
+  if (int e = op_begin(h, fn)) return e;
+  OP_REQ(mask && list && rowmap && cache_mask && posbase && fresh, "null argument");
+  OP_REQ(n > 0 && L > 0 && n_pos > 0, "n, L and n_pos must be positive");
+  Run R{h, (hipStream_t)stream};
+  OTHER(R, launch_seq_history_install(mask, list, rowmap, n, L, lo, hi, n_pos, cache_mask, posbase, fresh, R.st),
+        "vima_op_seq_history_install: seq_history_install");
+  return R.err;
 }
 
 int vima_op_seq_restart(VimaHandle* h, const int32_t* list, int n, int lo, int hi, int n_pos, uint8_t* cache_mask, uint8_t* fresh, vima_stream_t stream) {
