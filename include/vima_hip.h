@@ -151,13 +151,17 @@ int vima_decode(VimaHandle* h, const float* obs_tok, const uint8_t* obs_mask, co
  * episode; any other step must follow step-1 with the same B, Q, Lp.
  * The histories of the B samples share ONE row index space of n_positions rows: step s writes rows s (Q + 1) - 1 .. of every sample, so a batch
  * takes (n_positions + 1) / (Q + 1) steps after its step 0 (code 34 beyond), restarts or not.
- * Option "decode_ring" = 1 turns that row space into a ring, for batches that never stop (vectorised environments): a step's Q + 1 rows go
- * to the ring's write pointer, or to row 0 when they do not fit in front of row n_positions (the tail is skipped: a step's rows are never split).
- * `step` keeps its meaning (previous + 1) and is unbounded. A call is legal iff every row it overwrites or skips is dead for every sample:
- * age[b] + rows advanced <= n_positions, age[b] = ring rows advanced (skipped ones included) since sample b's episode began; otherwise it fails
- * with code 34, names the first such sample, changes nothing, and succeeds once that sample has been restarted (vima_decode_restart gives a
- * sample's rows back; vima_decode_steps_left tells in advance). A sample's own episode is thus still bounded by n_positions tokens, the
- * position table and the reference's limit. The self-attention reads the written part of the ring with a WINDOWED causal rule (key j is
+ * Option "decode_ring" = 1 turns that row space into a ring, for batches that never stop (vectorised environments). `step` keeps its meaning
+ * (previous + 1) and is unbounded.
+ * THE ROW BOOKKEEPING of this ring and of option "seq_ring" of the decoder-only policies (vima_seq_decode_restart below) is one piece of host
+ * code (vima_amd/csrc/episode_book.h): rows [0, P0) are a fixed prefix (P0 = 0 here, P0 = Lp + 1 there), rows [P0, n_positions) the ring of
+ * R = n_positions - P0 rows. The host keeps wp (next row), hw (one past the highest row written since step 0 / the prefill, both = P0 there) and
+ * age[b] (ring rows advanced since sample b's episode began, 0 there). A call of Lq rows (Q at step 0 of the batch, Q + 1 afterwards, T times as
+ * many for a chunk) goes to row = wp and advances Lq rows, or, when wp + Lq > n_positions, to row = P0 and advances n_positions - wp + Lq rows
+ * (the tail is skipped: a call's rows are never split). It is legal iff every row it overwrites or skips is dead for every sample:
+ * age[b] + advance <= R; otherwise it fails with code 34, names the first such sample, changes nothing, and succeeds once that sample has been
+ * restarted (a restart sets age[b] = 0 and takes no rows; vima_decode_steps_left tells in advance). On success age[b] += advance, wp = row + Lq,
+ * hw = max(hw, wp). A sample's own episode is thus still bounded by n_positions tokens, the position table and the reference's limit. The self-attention reads the written part of the ring with a WINDOWED causal rule (key j is
  * "future" for the step's query i iff i + write pointer < j < write pointer + Q + 1; the rows behind the window hold older history): the
  * predictions of a sample depend on its own episode only and equal those of the linear cache up to the order of the softmax sums. With
  * option "graphs" the captured graphs are keyed on (write pointer, rows read, action slot), and one eager step warms them all; the set stops growing once the
@@ -364,12 +368,8 @@ int vima_seq_decode_step(VimaHandle* h, const float* obs_tok, const float* act_t
  * Option "seq_ring" = 1 (default 0: every call behaves bit for bit as described above; changing it ends a running episode) makes the rows
  * behind the prefix a ring, for batches that never stop. Rows [0, P0), P0 = Lp + 1, of every sample's cache block stay the fixed prefix
  * (prompt + separator; a restart rewrites them in place); rows [P0, n_positions) are the ring, R = n_positions - P0 rows, still ONE row index
- * space for the whole batch. The host keeps wp (next row), hw (one past the highest row written since the prefill) and age[b] (ring rows
- * advanced since sample b's episode began); vima_seq_prefill sets wp = hw = P0 and every age to 0. A step of Lq rows (Q at step 0 of the
- * batch, Q + 1 afterwards) goes to row = wp and advances Lq rows, or, when wp + Lq > n_positions, to row = P0 and advances
- * n_positions - wp + Lq rows (the tail is skipped: a step's rows are never split). The step is legal iff age[b] + advance <= R for every
- * sample; otherwise it fails with code 34, names the first such sample, changes nothing, and succeeds once that sample has been restarted
- * (vima_decode_steps_left tells in advance). On success age[b] += advance, wp = row + Lq, hw = max(hw, wp). `step` keeps its meaning
+ * space for the whole batch. wp, hw, age[b], where a step's rows go and when it is legal (code 34 naming the first sample over age, nothing
+ * changed, otherwise) are THE ROW BOOKKEEPING described at vima_decode_step, with this P0; vima_seq_prefill begins it. `step` keeps its meaning
  * (previous + 1) and is unbounded. The step's k | v go to rows [row, row + Lq) and its queries read the written image [0, hw) under the
  * WINDOWED causal rule of vima_decode_step's ring (key j is "future" for the step's query i iff i + row < j < row + Lq; the rows from
  * row + Lq on hold older history) and the cache's key mask; rows at and beyond hw were never written and are never read. In the first lap

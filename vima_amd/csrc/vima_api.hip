@@ -3,6 +3,7 @@
 // sequence of hand-written gfx950 kernels (gemm.hip / attention.hip / elementwise.hip) on the caller's stream.
 #include "../../include/vima_hip.h"
 #include "kernels.h"
+#include "episode_book.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -229,27 +230,15 @@ struct VimaHandle {
   uint8_t* ep_fresh = nullptr;   // [B] 1 = the sample was restarted (vima_decode_restart): its next step has no previous action
   int ep_B = 0, ep_Q = 0, ep_Lmax = 0, ep_Lp = 0, ep_step = -1;
   // decoder-only episode (vima_seq_prefill / vima_seq_decode_step; GPT / GATO handles, which never run vima_decode_step: ep_kv / ep_mask / ep_poscnt /
-  // ep_fresh and ep_B / ep_Q / ep_Lp / ep_Lmax are theirs): seq_next = the step number the next call must carry, seq_row = cache rows in use
-  // (Lp + 1 + the rows of the steps so far) = the row the next step writes at
-  bool seq_live = false; int seq_next = 0, seq_row = 0;
-  // option "seq_ring": rows [P0, Lmax), P0 = ep_Lp + 1, of that row space are a ring behind the fixed prefix [0, P0) (prompt + separator, which a restart
-  // rewrites in place). seq_row is then the ring's write pointer, seq_hw = one past the highest row written since the prefill (rows beyond it hold
-  // hipMalloc garbage and are never read), seq_age[b] = ring rows advanced (skipped tail rows included) since sample b's episode began
-  int seq_ring = 0, seq_hw = 0;
-  std::vector<int> seq_age;
-  // option "decode_ring": the ONE row index space of the episode caches is a ring. Host bookkeeping (decode_prepare plans, decode_commit stores):
-  // ring_wp = next row to write, ring_hw = one past the highest row written since step 0 (rows beyond it hold hipMalloc garbage and are never
-  // read), ring_age[b] = ring rows advanced (skipped tail rows included) since sample b's episode began
-  int decode_ring = 0;
-  int ring_wp = 0, ring_hw = 0;
-  std::vector<int> ring_age;
+  // ep_fresh, ep_B / ep_Q / ep_Lp / ep_Lmax and the book are theirs)
+  bool seq_live = false;
+  // The ONE row index space of the episode caches behind the fixed prefix (XAttnGPT: none; GPT / GATO: prompt + separator), linear or a ring (options
+  // "decode_ring" / "seq_ring"): write pointer, high-water mark, next batch step, per-sample ages and the slot record (episode_book.h). Valid while
+  // ep_step >= 0 / seq_live; decode_prepare / seq_prepare plan, decode_commit / the seq entries commit
+  EpisodeBook book;
+  int seq_ring = 0, decode_ring = 0;
   int restart_batched = 1;                       // option "restart_batched": vima_decode_restart rebuilds the flagged samples' prompt K / V together (0: one sample at a time)
   std::vector<int> restart_list;                 // host copy of the flagged sample indices (source of the upload)
-  // vima_decode_restart_history: where the recent batch steps wrote (decode_commit appends, chunks included; step 0 clears). obs_row = the slot's first
-  // observation row (its action row, absent at batch step 0, is obs_row - 1); adv = the ring rows the step advanced (a chunk's skipped tail counts
-  // with its first step; without the ring: the slot's rows). Trimmed to n_positions entries: a step advances at least one row
-  struct EpSlot { int obs_row, adv; };
-  std::vector<EpSlot> ep_slots;
   std::vector<int> hist_rowmap;                  // host copy of the history's compact row -> cache row map (source of the upload)
   // hipGraph replay of the per-env-step entry points (option "graphs"): at small batch a step is ~1300 launches of
   // microsecond kernels and the HOST launch rate is the bound. The launch sequence of a call is captured the second time
@@ -2010,16 +1999,22 @@ int vima_prompt_encode(VimaHandle* h, const int64_t* word_ids, int n_words, cons
 // tokens of env step `step` are processed against the episode's cached self-attention K/V) share three stages:
 // decode_prepare (validation, cache (re)allocation, state invalidation -- host only), decode_launch (the pure launch
 // sequence: eager, captured or replayed) and decode_commit (host state after a successful launch).
-// row: first episode-cache row this call writes (= the history length L_hist, or the ring's write pointer); Lk / win_end: keys the self-attention reads and
-// the end of its causal window (AttnArgs); ring / advance / wp / hw: the ring bookkeeping decode_commit stores
-struct DecodePlan { bool inc; int has_act, row, Lq, Lmax, kv_mode, Lk, win_end; bool ring; int advance, wp, hw; };
+// u: the unit of the episode book this call writes (episode_book.h: first cache row = the history length or the ring's write pointer, rows, keys the
+// self-attention reads and the end of its causal window); a full-history call has only u.Lq
+struct DecodePlan { bool inc; int has_act, kv_mode; EpisodeBook::Plan u; };
 
-// One step of the ring's bookkeeping: Lq rows at write pointer wp of a ring of Lmax rows. A step's rows are never split across the wrap: when they do not
-// fit, the tail [wp, Lmax) is skipped (and counts as advanced) and the rows go to [0, Lq).
-struct RingStep { int row, advance; };
-static RingStep ring_next(int wp, int Lq, int Lmax) { return wp + Lq > Lmax ? RingStep{0, Lmax - wp + Lq} : RingStep{wp, Lq}; }
-// The same for the ring [P0, Lmax) behind a fixed prefix (option seq_ring of the decoder-only policies): the rows go to [P0, P0 + Lq) after a skipped tail.
-static RingStep seq_ring_next(int wp, int Lq, int P0, int Lmax) { return wp + Lq > Lmax ? RingStep{P0, Lmax - wp + Lq} : RingStep{wp, Lq}; }
+// A unit the book refuses (vima_decode_step / _chunk, vima_seq_decode_step / _chunk): code 34, nothing has changed
+static int plan_refused(const char* fn, const char* restart_fn, const EpisodeBook& bk, const EpisodeBook::Plan& p, int T) {
+  const std::string what = std::string(fn) + ": " + std::to_string(T) + " step(s) from step " + std::to_string(bk.next);
+  const std::string space = "n_positions " + std::to_string(bk.Lmax) + " - " + std::to_string(bk.P0);
+  if (p.refused == EpisodeBook::FULL)
+    return fail(what + " do not fit in front of n_positions " + std::to_string(bk.Lmax) + " (" + std::to_string(bk.wp) + " cache rows in use, room for " +
+                std::to_string(p.fit) + " more steps)", 34);
+  if (p.refused == EpisodeBook::TOO_LONG) return fail(what + " are longer than the whole ring (" + space + " rows)", 34);
+  return fail(what + ": the episode of sample " + std::to_string(p.sample) + " is longer than the ring (" + std::to_string(p.age) + " + " +
+              std::to_string(p.advance) + " ring rows > " + space + "): restart it with " + restart_fn +
+              ", or take fewer steps at once (a chunk skips the ring's tail as ONE unit)", 34);
+}
 
 // The episode caches for B samples of Lmax rows: per-layer self-attention K | V [layer][B][Lmax][2E], key mask [B][Lmax], position counter and
 // restart flag [B]. Grown (never shrunk) on demand; a reallocation invalidates the captured graphs.
@@ -2071,24 +2066,22 @@ static int decode_prepare(VimaHandle* h, const float* act_tok, int T, int B, int
   if (Lp > h->cfg.xattn_n_positions)   // xattn_gpt.py:110 assert
     return fail("AssertionError: prompt_tokens.size(1) <= xattn_n_positions (" + std::to_string(Lp) + " > " +
                 std::to_string(h->cfg.xattn_n_positions) + ")", 33);
+  EpisodeBook::Plan u{};
+  u.Lq = Lq;
   if (inc) {
     if (has_act && !act_tok) return fail("vima_decode_step: the previous action token is required for step > 0");
     if (chunk && !act_tok) return fail("vima_decode_chunk: the action tokens between the chunk's steps are required");
     if (step > 0 && !(h->ep_step == step - 1 && h->ep_B == B && h->ep_Q == Q && h->ep_Lp == Lp && h->kv_valid))
       return fail(std::string(fn) + ": step " + std::to_string(step) + " does not continue the episode state (last step " +
                   std::to_string(h->ep_step) + "); start an episode with step 0");
-    if (ring && step > 0) {   // legal iff every row about to be overwritten or skipped is dead for every sample (a chunk is ONE unit of Lq rows)
-      const RingStep rs = ring_next(h->ring_wp, Lq, Lmax);
-      for (int b = 0; b < B; ++b)
-        if (h->ring_age[b] + rs.advance > Lmax)
-          return fail(std::string(fn) + ": the episode of sample " + std::to_string(b) + " is longer than n_positions (" + std::to_string(h->ring_age[b]) + " + " +
-                      std::to_string(rs.advance) + " ring rows > " + std::to_string(Lmax) + "): restart it with vima_decode_restart", 34);
-    }
     kv_cache_mode = step == 0 ? 1 : 2;
-    if (step == 0) {
+    if (step == 0) {   // a new episode batch: the one that ran ends here
       if (int e = ep_reserve(h, B, Lmax)) return e;
       h->ep_step = -1;
+      h->book.begin(B, Q, 0, Lmax, ring);
     }
+    u = h->book.plan(T);   // the book is at `step` (the continuity check above): a chunk is ONE unit of Lq rows
+    if (u.refused) return plan_refused(fn, "vima_decode_restart", h->book, u, T);
   }
   if (kv_cache_mode < 0 || kv_cache_mode > 2) return fail("vima_decode: kv_cache_mode must be 0, 1 or 2");
   if (kv_cache_mode == 2 && !(h->kv_valid && h->kv_B == B && h->kv_Lp == Lp))
@@ -2106,33 +2099,16 @@ static int decode_prepare(VimaHandle* h, const float* act_tok, int T, int B, int
     }
   }
   if (!inc) h->ep_step = -1;   // a full-history call may rebuild the prompt cache: the episode state no longer matches
-  P = DecodePlan{inc, has_act, L_hist, Lq, Lmax, kv_cache_mode, L_hist + Lq, 0, ring, 0, 0, 0};
-  if (ring) {
-    const RingStep rs = step > 0 ? ring_next(h->ring_wp, Lq, Lmax) : RingStep{0, Lq};
-    P.row = rs.row; P.advance = rs.advance; P.wp = rs.row + Lq;
-    P.hw = step > 0 && h->ring_hw > P.wp ? h->ring_hw : P.wp;
-    P.Lk = P.hw; P.win_end = P.wp;
-  }
+  P = DecodePlan{inc, has_act, kv_cache_mode, u};
   return 0;
 }
 
-// step: the first env step of the call; T: how many it took (vima_decode_chunk)
-static void decode_commit(VimaHandle* h, const DecodePlan& P, int B, int Q, int Lp, int step, int T = 1) {
+// T: how many env steps the call took (vima_decode_chunk)
+static void decode_commit(VimaHandle* h, const DecodePlan& P, int B, int Q, int Lp, int T = 1) {
   if (P.kv_mode == 1) { h->kv_valid = true; h->kv_B = B; h->kv_Lp = Lp; }
   if (P.inc) {
-    h->ep_step = step + T - 1; h->ep_B = B; h->ep_Q = Q; h->ep_Lp = Lp; h->ep_Lmax = P.Lmax;
-    if (step == 0) h->ep_slots.clear();
-    for (int u = 0; u < T; ++u) {   // slot u = [action row, Q obs rows] at P.row + u (Q + 1); the first slot of batch step 0 has no action row
-      const int obs_row = P.row + u * (Q + 1) + (P.has_act ? 1 : 0);
-      const int rows = (step == 0 && u == 0) ? Q : Q + 1;
-      h->ep_slots.push_back({obs_row, u == 0 ? (P.ring ? P.advance : P.Lq) - (T - 1) * (Q + 1) : rows});
-    }
-    if ((int)h->ep_slots.size() > P.Lmax) h->ep_slots.erase(h->ep_slots.begin(), h->ep_slots.end() - P.Lmax);
-  }
-  if (P.ring) {
-    if (step == 0) h->ring_age.assign((size_t)B, 0);
-    for (int& a : h->ring_age) a += P.advance;
-    h->ring_wp = P.wp; h->ring_hw = P.hw;
+    h->book.commit(P.u, T);
+    h->ep_step = h->book.next - 1; h->ep_B = B; h->ep_Q = Q; h->ep_Lp = Lp; h->ep_Lmax = h->book.Lmax;
   }
 }
 
@@ -2145,7 +2121,7 @@ static int decode_launch(VimaHandle* h, const float* obs_tok, const uint8_t* obs
   if (int e = check_ready(h)) return e;
   const int E = h->cfg.embed_dim;
   const bool inc = P.inc;
-  const int has_act = P.has_act, L_hist = P.row, Lq = P.Lq, Lmax = P.Lmax, kv_cache_mode = P.kv_mode;
+  const int has_act = P.has_act, L_hist = P.u.row, Lq = P.u.Lq, Lmax = h->cfg.n_positions, kv_cache_mode = P.kv_mode;
   if (inc && !has_act) {   // step 0
     HIPCK(hipMemsetAsync(h->ep_poscnt, 0, (size_t)B * sizeof(int), stream));
     HIPCK(hipMemsetAsync(h->ep_fresh, 0, (size_t)B, stream));
@@ -2341,7 +2317,7 @@ static int decode_launch(VimaHandle* h, const float* obs_tok, const uint8_t* obs
       R.gemm(gk);
       }
       s.q = qkv; s.ldq = E; s.k = cache; s.ldk = 2 * E; s.v = R.offT(cache, E); s.ldv = 2 * E;
-      s.kmask = h->ep_mask; s.Lk = P.Lk; s.Lk_rows = Lmax; s.q_off = L_hist; s.win_end = P.win_end;
+      s.kmask = h->ep_mask; s.Lk = P.u.Lk; s.Lk_rows = Lmax; s.q_off = L_hist; s.win_end = P.u.win_end;
     } else {
       R.linear(xT, E, D.c_attn, rq, ACT_NONE, nullptr, 0, nullptr, 0, nullptr, 0, qkv, 3 * E);
       s.q = qkv; s.ldq = 3 * E; s.k = R.offT(qkv, E); s.ldk = 3 * E; s.v = R.offT(qkv, 2 * E); s.ldv = 3 * E;
@@ -2382,7 +2358,7 @@ int vima_decode(VimaHandle* h, const float* obs_tok, const uint8_t* obs_mask, co
   const int rc = run_graphed(h, key, (hipStream_t)stream, [&](hipStream_t st) {
     return decode_launch(h, obs_tok, obs_mask, act_tok, T, B, Q, L_act, prompt, stride_b, stride_l, prompt_mask, Lp, P, out, st);
   });
-  if (!rc) decode_commit(h, P, B, Q, Lp, -1);
+  if (!rc) decode_commit(h, P, B, Q, Lp);
   return rc;
 }
 
@@ -2394,17 +2370,17 @@ int vima_decode_step(VimaHandle* h, const float* obs_tok, const uint8_t* obs_mas
   if (int e = decode_prepare(h, act_tok, 1, B, Q, 0, Lp, 0, step, P)) return e;
   // ring mode: the launch sequence depends on (write pointer, keys read, action slot), not on the step number -- from the second lap on the write
   // pointers repeat, so the set of captured graphs stays bounded however long the rollout runs
-  const long long kstep = P.ring ? -1 - (((long long)P.row * (P.Lmax + 1) + P.Lk) * 2 + P.has_act) : step;
+  const long long kstep = h->book.ring ? -1 - (((long long)P.u.row * (h->book.Lmax + 1) + P.u.Lk) * 2 + P.has_act) : step;
   const std::string key = gkey("decode_step", {(long long)(uintptr_t)obs_tok, (long long)(uintptr_t)obs_mask, (long long)(uintptr_t)act_tok, kstep,
                                                B, Q, (long long)(uintptr_t)prompt, stride_b, stride_l, (long long)(uintptr_t)prompt_mask,
                                                Lp, (long long)(uintptr_t)out, (long long)(uintptr_t)h->kv_cache, (long long)(uintptr_t)h->ep_kv});
   // ... and one eager step with an action slot warms all of them (same shapes, same workspace, same kernels: the attention launcher picks by Lk < 64 / >= 64):
   // each (write pointer, keys read) is captured when first seen
-  const std::string warm = P.ring && P.has_act ? gkey("decode_step_ring", {B, Q, Lp, P.Lk >= 64 ? 1 : 0}) : std::string();
+  const std::string warm = h->book.ring && P.has_act ? gkey("decode_step_ring", {B, Q, Lp, P.u.Lk >= 64 ? 1 : 0}) : std::string();
   const int rc = run_graphed(h, key, (hipStream_t)stream, [&](hipStream_t st) {
     return decode_launch(h, obs_tok, obs_mask, act_tok, 1, B, Q, 0, prompt, stride_b, stride_l, prompt_mask, Lp, P, out, st);
   }, warm);
-  if (!rc) decode_commit(h, P, B, Q, Lp, step);
+  if (!rc) decode_commit(h, P, B, Q, Lp);
   return rc;
 }
 
@@ -2421,7 +2397,7 @@ int vima_decode_chunk(VimaHandle* h, const float* obs_tok, const uint8_t* obs_ma
   DecodePlan P;
   if (int e = decode_prepare(h, act_tok, T, B, Q, 0, Lp, 0, step, P)) return e;
   const int rc = decode_launch(h, obs_tok, obs_mask, act_tok, T, B, Q, 0, prompt, stride_b, stride_l, prompt_mask, Lp, P, out, (hipStream_t)stream);
-  if (!rc) decode_commit(h, P, B, Q, Lp, step, T);
+  if (!rc) decode_commit(h, P, B, Q, Lp, T);
   return rc;
 }
 
@@ -2431,7 +2407,7 @@ int vima_decode_chunk(VimaHandle* h, const float* obs_tok, const uint8_t* obs_ma
 // at the same cache rows), its position counter restarts at 0, its next step carries no previous action, and its rows of the per-layer
 // prompt K/V cache are rebuilt from its row of `prompt` (the NEW prompts; rows of the other samples are not read). The batch keeps
 // stepping with vima_decode_step(step + 1, ...); n_positions bounds the number of steps since the last step 0 of the whole batch -- unless the
-// row index space is a ring (option decode_ring), where a restart gives the sample's rows back (ring_age[b] = 0).
+// row index space is a ring (option decode_ring), where a restart gives the sample's rows back (EpisodeBook::restart).
 // The prompt K / V rows of ALL flagged samples are rebuilt together (option restart_batched, prompts longer than 32 tokens): one gather of their
 // prompts + positions into [n_r * Lp, E], per layer one GEMM of n_r * Lp rows and one scatter into the cache (either layout) -- 1 + 2 NL launches
 // whatever n_r is, against n_r (1 + NL .. 2 NL) for the per-sample loop. The tile GEMM kernels agree bit for bit at every row count (option
@@ -2483,19 +2459,8 @@ int vima_decode_restart(VimaHandle* h, const uint8_t* restart, int B, const floa
       }
     }
   }
-  if (!R.err && h->decode_ring && (int)h->ring_age.size() == B)
-    for (int b : h->restart_list) h->ring_age[b] = 0;   // the sample's rows are dead: the ring may overwrite them
+  if (!R.err) h->book.restart(h->restart_list);
   return R.err;
-}
-
-// The largest history vima_decode_restart_history can install: the batch steps whose rows are all still there. Without the ring: every step since
-// step 0; with it: the last R steps whose advances sum to at most n_positions (a sample restarted right before them would still be legal now).
-static int history_room(const VimaHandle* h) {
-  if (h->ep_step < 0) return 0;
-  if (!h->decode_ring) return (int)h->ep_slots.size();
-  int R = 0, sum = 0;
-  for (int j = (int)h->ep_slots.size() - 1; j >= 0 && sum + h->ep_slots[j].adv <= h->ep_Lmax; --j) { sum += h->ep_slots[j].adv; ++R; }
-  return R;
 }
 
 int vima_decode_history_room(VimaHandle* h, int32_t* steps_host) {
@@ -2503,7 +2468,7 @@ int vima_decode_history_room(VimaHandle* h, int32_t* steps_host) {
   if (h->cfg.policy_kind != VIMA_POLICY_VIMA && h->cfg.policy_kind != VIMA_POLICY_FLAMINGO)
     return fail("vima_decode_history_room: the handle's policy has no XAttnGPT episode caches");
   if (h->ep_step < 0) return fail("vima_decode_history_room: no running episode batch (start one with vima_decode_step(step = 0))");
-  *steps_host = history_room(h);
+  *steps_host = h->book.room();
   return 0;
 }
 
@@ -2524,7 +2489,7 @@ int vima_decode_restart_history(VimaHandle* h, const uint8_t* restart, int B, co
   if (!(h->ep_step >= 0 && h->ep_B == B && h->ep_Lp == Lp && h->kv_valid && h->kv_B == B && h->kv_Lp == Lp))
     return fail("vima_decode_restart_history: no running episode batch with this B / Lp (start one with vima_decode_step(step = 0))");
   const int Q = h->ep_Q, Lmax = h->ep_Lmax;
-  const int room = history_room(h);
+  const int room = h->book.room();
   if (T > room)
     return fail("vima_decode_restart_history: a history of " + std::to_string(T) + " steps does not fit: room for " + std::to_string(room) +
                 " (the batch steps whose cache rows are all still there)", 34);
@@ -2535,64 +2500,26 @@ int vima_decode_restart_history(VimaHandle* h, const uint8_t* restart, int B, co
   if (n_r == 0) return 0;
   // history step s sits in the slot of batch step t - T + s: its Q obs rows in the slot's obs rows, a_{s-1} in its action row (s > 0; the first
   // slot's action row stays masked). Compact rows (dec_embed_kernel): [o_0 (Q), a_0, o_1 (Q), a_1, ...]
-  const VimaHandle::EpSlot* S = h->ep_slots.data() + (h->ep_slots.size() - (size_t)T);
   h->hist_rowmap.resize((size_t)Lh);
-  int age = 0;
-  for (int s = 0; s < T; ++s) {
-    age += S[s].adv;
-    for (int q = 0; q < Q; ++q) h->hist_rowmap[(size_t)s * (Q + 1) + q] = S[s].obs_row + q;
-    if (s + 1 < T) h->hist_rowmap[(size_t)s * (Q + 1) + Q] = S[s + 1].obs_row - 1;
-  }
+  const int age = h->book.history_rows(T, h->hist_rowmap.data());
   for (int r : h->hist_rowmap)
     if (r < 0 || r >= Lmax) return fail("vima_decode_restart_history: internal error: history row outside the cache");
-  const DecodePlan P{false, 0, 0, (int)Lh, Lmax, 0, (int)Lh, 0, false, 0, 0, 0};
+  DecodePlan P{false, 0, 0, {}};
+  P.u.Lq = (int)Lh;
   const int rc = decode_launch(h, hist_obs, hist_mask, hist_act, T, n_r, Q, T - 1, prompt, stride_b, stride_l, prompt_mask, Lp, P, out,
                                (hipStream_t)stream, true);
-  if (!rc && h->decode_ring && (int)h->ring_age.size() == B)
-    for (int b : h->restart_list) h->ring_age[b] = age;
+  if (!rc) h->book.install(h->restart_list, age);
   return rc;
 }
 
-// Host-only: how many further vima_decode_step calls would succeed if sample b alone were never restarted (the bookkeeping of decode_prepare run forward).
+// Host-only: how many further vima_decode_step / vima_seq_decode_step calls would succeed if sample b alone were never restarted (EpisodeBook::steps_left).
 int vima_decode_steps_left(VimaHandle* h, int B, int32_t* out_host) {
   if (!h || !out_host) return fail("vima_decode_steps_left: null argument");
-  if (h->cfg.policy_kind == VIMA_POLICY_GPT || h->cfg.policy_kind == VIMA_POLICY_GATO) {   // the episode of vima_seq_prefill / vima_seq_decode_step
-    if (!(h->seq_live && h->ep_B == B))
-      return fail("vima_decode_steps_left: no running episode batch of this size (start one with vima_seq_prefill)");
-    if (h->seq_ring) {   // the bookkeeping of vima_seq_decode_step run forward, per sample
-      const int P0 = h->ep_Lp + 1, Lmax = h->ep_Lmax;
-      for (int b = 0; b < B; ++b) {
-        int n = 0, wp = h->seq_row, age = h->seq_age[b], Lq = h->ep_Q + (h->seq_next == 0 ? 0 : 1);
-        for (;;) {
-          const RingStep rs = seq_ring_next(wp, Lq, P0, Lmax);
-          if (age + rs.advance > Lmax - P0) break;
-          age += rs.advance; wp = rs.row + Lq; Lq = h->ep_Q + 1; ++n;
-        }
-        out_host[b] = n;
-      }
-      return 0;
-    }
-    // every step takes Q + 1 rows (after a restart the action slot is a masked row), except step 0 of the batch: Q
-    const int left = h->ep_Lmax - h->seq_row + (h->seq_next == 0 ? 1 : 0);
-    for (int b = 0; b < B; ++b) out_host[b] = left / (h->ep_Q + 1);
-    return 0;
-  }
-  if (!(h->ep_step >= 0 && h->ep_B == B)) return fail("vima_decode_steps_left: no running episode batch of this size (start one with vima_decode_step(step = 0))");
-  const int Lq = h->ep_Q + 1, Lmax = h->ep_Lmax;
-  if (!h->decode_ring) {   // step s needs (s + 1) (Q + 1) - 1 <= n_positions rows since the batch's step 0
-    const int last = (Lmax + 1) / Lq - 1;
-    for (int b = 0; b < B; ++b) out_host[b] = last > h->ep_step ? last - h->ep_step : 0;
-    return 0;
-  }
-  for (int b = 0; b < B; ++b) {
-    int n = 0, wp = h->ring_wp, age = h->ring_age[b];
-    for (;;) {
-      const RingStep rs = ring_next(wp, Lq, Lmax);
-      if (age + rs.advance > Lmax) break;
-      age += rs.advance; wp = rs.row + Lq; ++n;
-    }
-    out_host[b] = n;
-  }
+  const bool seq = h->cfg.policy_kind == VIMA_POLICY_GPT || h->cfg.policy_kind == VIMA_POLICY_GATO;   // the episode of vima_seq_prefill / vima_seq_decode_step
+  if (!((seq ? h->seq_live : h->ep_step >= 0) && h->ep_B == B))
+    return fail(std::string("vima_decode_steps_left: no running episode batch of this size (start one with ") +
+                (seq ? "vima_seq_prefill)" : "vima_decode_step(step = 0))"));
+  for (int b = 0; b < B; ++b) out_host[b] = h->book.steps_left(b);
   return 0;
 }
 
@@ -2723,18 +2650,10 @@ int vima_seq_prefill(VimaHandle* h, const float* prompt, int64_t stride_b, int64
   OTHER(R, launch_seq_embed_prefill(prompt, stride_b, stride_l, prompt_mask, h->sep_token, h->pos_emb, Lmax, x32, xT, mask, h->ep_mask,
                                     h->ep_poscnt, nullptr, B, Lp, E, h->bf16, R.st), "seq_embed_prefill");
   if (hfgpt_stack(R, x32, xT, mask, B, L, h->ep_kv, nullptr, B, Lmax)) return R.err;
-  h->seq_live = true; h->seq_next = 0; h->seq_row = L;
-  h->ep_slots.clear();   // the slot record of vima_seq_decode_step / _chunk (GPT / GATO handles never run vima_decode_step: the record is theirs)
-  h->seq_hw = L; h->seq_age.assign((size_t)B, 0);   // option seq_ring: write pointer (seq_row) = high-water mark = P0, every age 0
+  h->seq_live = true;
+  h->book.begin(B, rgb_tokens_per_image(h->cfg.policy_kind), L, Lmax, h->seq_ring != 0);   // the fixed prefix: prompt + separator
   h->ep_B = B; h->ep_Q = rgb_tokens_per_image(h->cfg.policy_kind); h->ep_Lp = Lp; h->ep_Lmax = Lmax;
   return 0;
-}
-
-// One record per env step of a successful vima_seq_decode_step / _chunk (host bookkeeping only): (first obs row, ring rows advanced). T slots of
-// [action row, Q obs rows] from `row` on; the first slot of batch step 0 has no action row, and a chunk's skipped tail counts with its first step.
-static void seq_record(VimaHandle* h, int row, int has_act, int T, int Q, int advance) {
-  for (int u = 0; u < T; ++u) h->ep_slots.push_back({row + u * (Q + 1) + has_act, u == 0 ? advance - (T - 1) * (Q + 1) : Q + 1});
-  if ((int)h->ep_slots.size() > h->ep_Lmax) h->ep_slots.erase(h->ep_slots.begin(), h->ep_slots.end() - h->ep_Lmax);
 }
 
 static int seq_step_launch(VimaHandle* h, const float* obs_tok, const float* act_tok, int B, int Q, int has_act, int row, int Lk, int win_end,
@@ -2752,51 +2671,37 @@ static int seq_step_launch(VimaHandle* h, const float* obs_tok, const float* act
   return R.err;
 }
 
-int vima_seq_decode_step(VimaHandle* h, const float* obs_tok, const float* act_tok, int step, int B, float* out, vima_stream_t stream) {
-  if (int e = seq_ready(h, "vima_seq_decode_step")) return e;
-  if (!obs_tok || !out) return fail("vima_seq_decode_step: null argument");
-  if (step < 0 || B <= 0) return fail("vima_seq_decode_step: step must be >= 0 and B > 0");
-  if (!(h->seq_live && h->seq_next == step && h->ep_B == B))
-    return fail("vima_seq_decode_step: step " + std::to_string(step) + " of " + std::to_string(B) + " samples does not continue the episode state (" +
-                (h->seq_live ? "next step " + std::to_string(h->seq_next) + " of " + std::to_string(h->ep_B) + " samples" : std::string("no episode")) +
+// vima_seq_decode_step (T = 1) and vima_seq_decode_chunk: validation, the continuity check and the plan -- host only, nothing changes
+static int seq_prepare(VimaHandle* h, const char* fn, const float* obs_tok, const float* act_tok, int step, int T, int B, const float* out,
+                       EpisodeBook::Plan& P) {
+  if (int e = seq_ready(h, fn)) return e;
+  if (!obs_tok || !out) return fail(std::string(fn) + ": null argument");
+  if (step < 0 || T < 1 || B <= 0) return fail(std::string(fn) + ": step must be >= 0, T >= 1 and B > 0");
+  if (!(h->seq_live && h->book.next == step && h->ep_B == B))
+    return fail(std::string(fn) + ": step " + std::to_string(step) + " of " + std::to_string(B) + " samples does not continue the episode state (" +
+                (h->seq_live ? "next step " + std::to_string(h->book.next) + " of " + std::to_string(h->ep_B) + " samples" : std::string("no episode")) +
                 "); start an episode with vima_seq_prefill");
-  const int has_act = step > 0 ? 1 : 0, Q = h->ep_Q, Lq = Q + has_act, Lmax = h->ep_Lmax;
-  const bool ring = h->seq_ring != 0;
-  if (has_act && !act_tok) return fail("vima_seq_decode_step: the previous action token is required for step > 0");
-  // row: first cache row this call writes; Lk / win_end: keys the self-attention reads and the end of its causal window (0: the plain rule)
-  int row = h->seq_row, Lk = row + Lq, win_end = 0, advance = Lq;
-  if (!ring) {
-    if (row + Lq > Lmax)
-      return fail("vima_seq_decode_step: sequence of " + std::to_string(row + Lq) + " tokens exceeds n_positions " + std::to_string(Lmax), 34);
-  } else {   // legal iff every ring row about to be overwritten or skipped is dead for every sample
-    const int P0 = h->ep_Lp + 1;
-    const RingStep rs = seq_ring_next(h->seq_row, Lq, P0, Lmax);
-    for (int b = 0; b < B; ++b)
-      if (h->seq_age[b] + rs.advance > Lmax - P0)
-        return fail("vima_seq_decode_step: the episode of sample " + std::to_string(b) + " is longer than the ring behind its prompt (" +
-                    std::to_string(h->seq_age[b]) + " + " + std::to_string(rs.advance) + " ring rows > n_positions " + std::to_string(Lmax) + " - " +
-                    std::to_string(P0) + "): restart it with vima_seq_decode_restart", 34);
-    row = rs.row; advance = rs.advance; win_end = row + Lq;
-    Lk = h->seq_hw > win_end ? h->seq_hw : win_end;
-  }
+  if ((step > 0 || T > 1) && !act_tok)
+    return fail(std::string(fn) + ": the action tokens are required (the previous action for step > 0, those between a chunk's steps)");
+  P = h->book.plan(T);
+  return P.refused ? plan_refused(fn, "vima_seq_decode_restart", h->book, P, T) : 0;
+}
+
+int vima_seq_decode_step(VimaHandle* h, const float* obs_tok, const float* act_tok, int step, int B, float* out, vima_stream_t stream) {
+  EpisodeBook::Plan P;
+  if (int e = seq_prepare(h, "vima_seq_decode_step", obs_tok, act_tok, step, 1, B, out, P)) return e;
+  const int has_act = step > 0 ? 1 : 0, Q = h->ep_Q;
   // ring mode: the launch sequence depends on (write pointer, keys read, action slot), not on the step number -- from the second lap on every step
   // has Q + 1 rows and the write pointers repeat, so the set of captured graphs stays bounded however long the rollout runs ...
-  const std::string key = gkey("seq_step", {(long long)(uintptr_t)obs_tok, (long long)(uintptr_t)act_tok, (long long)(uintptr_t)out, B, row, has_act,
-                                            (long long)(uintptr_t)h->ep_kv, Lk, win_end});
+  const std::string key = gkey("seq_step", {(long long)(uintptr_t)obs_tok, (long long)(uintptr_t)act_tok, (long long)(uintptr_t)out, B, P.row, has_act,
+                                            (long long)(uintptr_t)h->ep_kv, P.Lk, P.win_end});
   // ... and one eager step with an action slot warms all of them (same shapes, same workspace, same kernels: the attention launcher picks by Lk < 64 / >= 64):
   // each (write pointer, keys read) is captured when first seen
-  const std::string warm = ring && has_act ? gkey("seq_step_ring", {B, Lk >= 64 ? 1 : 0}) : std::string();
+  const std::string warm = h->book.ring && has_act ? gkey("seq_step_ring", {B, P.Lk >= 64 ? 1 : 0}) : std::string();
   const int rc = run_graphed(h, key, (hipStream_t)stream, [&](hipStream_t st) {
-    return seq_step_launch(h, obs_tok, has_act ? act_tok : nullptr, B, Q, has_act, row, Lk, win_end, out, st);
+    return seq_step_launch(h, obs_tok, has_act ? act_tok : nullptr, B, Q, has_act, P.row, P.Lk, P.win_end, out, st);
   }, warm);
-  if (!rc) {
-    h->seq_next = step + 1; h->seq_row = row + Lq;
-    seq_record(h, row, has_act, 1, Q, advance);
-    if (ring) {
-      for (int& a : h->seq_age) a += advance;
-      h->seq_hw = Lk;
-    }
-  }
+  if (!rc) h->book.commit(P, 1);
   return rc;
 }
 
@@ -2822,12 +2727,11 @@ int vima_seq_decode_restart(VimaHandle* h, const uint8_t* restart, int B, const 
   if (R.err) return R.err;
   HIPCK(hipMemcpyAsync(list, h->restart_list.data(), (size_t)n_r * sizeof(int), hipMemcpyHostToDevice, R.st));
   // ring mode: the sample's history may lie anywhere in the written part [P0, hw) of the ring
-  OTHER(R, launch_seq_restart(list, n_r, h->ep_mask, h->ep_fresh, L, h->seq_ring ? h->seq_hw : h->seq_row, Lmax, R.st), "seq_restart");
+  OTHER(R, launch_seq_restart(list, n_r, h->ep_mask, h->ep_fresh, L, h->book.written_end(), Lmax, R.st), "seq_restart");
   OTHER(R, launch_seq_embed_prefill(prompt, stride_b, stride_l, prompt_mask, h->sep_token, h->pos_emb, Lmax, x32, xT, mask, h->ep_mask,
                                     h->ep_poscnt, list, n_r, Lp, E, h->bf16, R.st), "seq_embed_prefill");
   hfgpt_stack(R, x32, xT, mask, n_r, L, h->ep_kv, list, B, Lmax);
-  if (!R.err && h->seq_ring)
-    for (int b : h->restart_list) h->seq_age[b] = 0;   // the sample's ring rows are dead: later steps may overwrite them (a restart itself takes none)
+  if (!R.err) h->book.restart(h->restart_list);
   return R.err;
 }
 
@@ -2837,71 +2741,27 @@ int vima_seq_decode_restart(VimaHandle* h, const uint8_t* restart, int B, const 
 // step graphs captured before stay valid -- they read the episode state from the device and their plan from the key.
 int vima_seq_decode_chunk(VimaHandle* h, const float* obs_tok, const float* act_tok, int step, int T, int B, float* out, vima_stream_t stream) {
   if (T == 1) return vima_seq_decode_step(h, obs_tok, act_tok, step, B, out, stream);
-  const char* fn = "vima_seq_decode_chunk";
-  if (int e = seq_ready(h, fn)) return e;
-  if (!obs_tok || !out) return fail("vima_seq_decode_chunk: null argument");
-  if (step < 0 || T < 1 || B <= 0) return fail("vima_seq_decode_chunk: step must be >= 0, T >= 1 and B > 0");
-  if (!(h->seq_live && h->seq_next == step && h->ep_B == B))
-    return fail("vima_seq_decode_chunk: step " + std::to_string(step) + " of " + std::to_string(B) + " samples does not continue the episode state (" +
-                (h->seq_live ? "next step " + std::to_string(h->seq_next) + " of " + std::to_string(h->ep_B) + " samples" : std::string("no episode")) +
-                "); start an episode with vima_seq_prefill");
-  if (!act_tok) return fail("vima_seq_decode_chunk: the action tokens between the chunk's steps are required");
-  const int has_act = step > 0 ? 1 : 0, Q = h->ep_Q, Lmax = h->ep_Lmax, E = h->cfg.embed_dim;
-  const bool ring = h->seq_ring != 0;
-  const long long Lq64 = (long long)T * (Q + 1) - (has_act ? 0 : 1);
-  int row = h->seq_row, advance = 0, win_end = 0;
-  if (!ring) {
-    if (row + Lq64 > Lmax)
-      return fail("vima_seq_decode_chunk: " + std::to_string(T) + " steps from step " + std::to_string(step) + " need " + std::to_string(row + Lq64) +
-                  " cache rows > n_positions " + std::to_string(Lmax) + " (room for " + std::to_string((Lmax - row + (has_act ? 0 : 1)) / (Q + 1)) +
-                  " more steps)", 34);
-    advance = (int)Lq64;
-  } else {   // the chunk is ONE unit of the ring: never split, legal iff every row it overwrites or skips is dead for every sample
-    const int P0 = h->ep_Lp + 1;
-    if (Lq64 > Lmax) return fail("vima_seq_decode_chunk: a chunk of " + std::to_string(Lq64) + " rows is longer than n_positions " + std::to_string(Lmax), 34);
-    const RingStep rs = seq_ring_next(h->seq_row, (int)Lq64, P0, Lmax);   // a chunk longer than the ring advances more than R rows: refused below
-    for (int b = 0; b < B; ++b)
-      if (h->seq_age[b] + rs.advance > Lmax - P0)
-        return fail("vima_seq_decode_chunk: the episode of sample " + std::to_string(b) + " is longer than the ring behind its prompt (" +
-                    std::to_string(h->seq_age[b]) + " + " + std::to_string(rs.advance) + " ring rows > n_positions " + std::to_string(Lmax) + " - " +
-                    std::to_string(P0) + "): restart it with vima_seq_decode_restart, or take fewer steps at once (a chunk skips the ring's tail as ONE unit)", 34);
-    row = rs.row; advance = rs.advance; win_end = row + (int)Lq64;
-  }
-  const int Lq = (int)Lq64;
-  const int Lk = ring && h->seq_hw > row + Lq ? h->seq_hw : row + Lq;
+  EpisodeBook::Plan P;
+  if (int e = seq_prepare(h, "vima_seq_decode_chunk", obs_tok, act_tok, step, T, B, out, P)) return e;
+  const int has_act = step > 0 ? 1 : 0, Q = h->ep_Q, Lmax = h->ep_Lmax, E = h->cfg.embed_dim, Lq = P.Lq;
   Run R{h, (hipStream_t)stream};
   float* x32 = R.ws<float>((size_t)B * Lq * E);
   void* xT = R.wsT((size_t)B * Lq * E);
   if (R.err) return R.err;
-  OTHER(R, launch_seq_embed_chunk(obs_tok, act_tok, h->pos_emb, Lmax, x32, xT, h->ep_mask, h->ep_poscnt, h->ep_fresh, row, T, B, Q, has_act, E, h->bf16,
+  OTHER(R, launch_seq_embed_chunk(obs_tok, act_tok, h->pos_emb, Lmax, x32, xT, h->ep_mask, h->ep_poscnt, h->ep_fresh, P.row, T, B, Q, has_act, E, h->bf16,
                                   R.st), "seq_embed_chunk");
-  if (hfgpt_step_stack(R, x32, xT, B, Lq, row, Lmax, Lk, win_end)) return R.err;
+  if (hfgpt_step_stack(R, x32, xT, B, Lq, P.row, Lmax, P.Lk, P.win_end)) return R.err;
   OTHER(R, launch_gather_pred(x32, out, T, B, Q, Lq, E, R.st, has_act), "gather_pred");   // the last obs row of every slot
   if (R.err) return R.err;
-  h->seq_next = step + T; h->seq_row = row + Lq;
-  seq_record(h, row, has_act, T, Q, advance);
-  if (ring) {
-    for (int& a : h->seq_age) a += advance;
-    h->seq_hw = Lk;
-  }
+  h->book.commit(P, T);
   return 0;
-}
-
-// The largest history vima_seq_decode_restart_history can install now: the batch steps whose rows are all still there. Linear cache: every step since
-// the prefill; ring: the last r steps whose advances sum to at most R (a sample restarted right before them would still be legal now).
-static int seq_history_room(const VimaHandle* h) {
-  if (!h->seq_ring) return (int)h->ep_slots.size();
-  const int R = h->ep_Lmax - (h->ep_Lp + 1);
-  int r = 0, sum = 0;
-  for (int j = (int)h->ep_slots.size() - 1; j >= 0 && sum + h->ep_slots[j].adv <= R; --j) { sum += h->ep_slots[j].adv; ++r; }
-  return r;
 }
 
 int vima_seq_history_room(VimaHandle* h, int32_t* steps_host) {
   if (int e = seq_ready(h, "vima_seq_history_room")) return e;
   if (!steps_host) return fail("vima_seq_history_room: null argument");
   if (!h->seq_live) return fail("vima_seq_history_room: no running episode batch (start one with vima_seq_prefill)");
-  *steps_host = seq_history_room(h);
+  *steps_host = h->book.room();
   return 0;
 }
 
@@ -2921,7 +2781,7 @@ int vima_seq_decode_restart_history(VimaHandle* h, const uint8_t* restart, int B
   if (!(h->seq_live && h->ep_B == B && h->ep_Lp == Lp))
     return fail("vima_seq_decode_restart_history: no running episode batch with this B / Lp (start one with vima_seq_prefill)");
   const int E = h->cfg.embed_dim, Q = h->ep_Q, Lmax = h->ep_Lmax, P0 = Lp + 1;
-  const int room = seq_history_room(h);
+  const int room = h->book.room();
   if (T > room)
     return fail("vima_seq_decode_restart_history: a history of " + std::to_string(T) + " steps does not fit: room for " + std::to_string(room) +
                 " (the batch steps whose cache rows are all still there)", 34);
@@ -2937,17 +2797,9 @@ int vima_seq_decode_restart_history(VimaHandle* h, const uint8_t* restart, int B
   if (n_r == 0) return 0;
   // compact row l of the sequence -> cache row: the identity over the prefix; history step s sits in the slot of batch step t - T + s, its Q obs rows
   // in the slot's obs rows and a_s in the action row of the NEXT slot (the first slot's own action row, if it has one, stays masked)
-  const VimaHandle::EpSlot* S = h->ep_slots.data() + (h->ep_slots.size() - (size_t)T);
   std::vector<int> rowmap((size_t)L);
   for (int l = 0; l <= Lp; ++l) rowmap[(size_t)l] = l;
-  int age = 0;
-  const int hi = h->seq_ring ? h->seq_hw : h->seq_row;
-  for (int s = 0; s < T; ++s) {
-    age += S[s].adv;
-    int* m = rowmap.data() + P0 + (size_t)s * (Q + 1);
-    for (int q = 0; q < Q; ++q) m[q] = S[s].obs_row + q;
-    if (s + 1 < T) m[Q] = S[s + 1].obs_row - 1;
-  }
+  const int age = h->book.history_rows(T, rowmap.data() + P0), hi = h->book.written_end();
   for (int l = P0; l < L; ++l)
     if (rowmap[(size_t)l] < P0 || rowmap[(size_t)l] >= hi) return fail("vima_seq_decode_restart_history: internal error: history row outside the written cache");
   h->restart_list = flagged;
@@ -2966,8 +2818,7 @@ int vima_seq_decode_restart_history(VimaHandle* h, const uint8_t* restart, int B
   if (hfgpt_stack(R, x32, xT, mask, n_r, L, h->ep_kv, list, B, Lmax, hmap)) return R.err;
   if (out) OTHER(R, launch_gather_pred(x32 + (size_t)P0 * E, out, T, n_r, Q, L, E, R.st), "gather_pred");   // teacher-forced: the last obs row of every history step
   OTHER(R, launch_seq_history_install(mask, list, hmap, n_r, L, P0, hi, Lmax, h->ep_mask, h->ep_poscnt, h->ep_fresh, R.st), "seq_history_install");
-  if (!R.err && h->seq_ring)
-    for (int b : h->restart_list) h->seq_age[b] = age;
+  if (!R.err) h->book.install(h->restart_list, age);
   return R.err;
 }
 
