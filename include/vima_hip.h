@@ -543,8 +543,9 @@ int vima_op_prompt_assemble(VimaHandle* h, const int32_t* tok_src, const int64_t
  * mask [B, T Q + L_act]; L_act = T or T - 1. */
 int vima_op_dec_embed(VimaHandle* h, const float* obs_tok, const uint8_t* obs_mask, const float* act_tok, const float* pos_table, int n_pos,
                       int T, int B, int Q, int L_act, int E, float* x32, float* xT, uint8_t* mask, vima_stream_t stream);
-/* launch_dec_embed_step: obs_tok [B, Q, E], obs_mask [B, Q], act_tok [B, E] (has_act) -> x32 / xT (optional) [B, Q + has_act, E]; hist_mask
- * [B, Lmax] rows [L_hist, L_hist + Q + has_act), poscnt [B] and fresh [B] (optional) are updated. */
+/* One env step = launch_dec_embed_chunk, the chunk kernel at T = 1: obs_tok [B, Q, E], obs_mask [B, Q], act_tok [B, E] (has_act) -> x32 / xT
+ * (optional) [B, Q + has_act, E]; hist_mask [B, Lmax] rows [L_hist, L_hist + Q + has_act), poscnt [B] and fresh [B] (optional) are updated.
+ * Refused: Q + has_act > 64, rows past Lmax, E % 4. */
 int vima_op_dec_embed_step(VimaHandle* h, const float* obs_tok, const uint8_t* obs_mask, const float* act_tok, const float* pos_table, int n_pos,
                            int L_hist, int Lmax, int B, int Q, int has_act, int E, float* x32, float* xT, uint8_t* hist_mask, int32_t* poscnt,
                            uint8_t* fresh, vima_stream_t stream);
@@ -573,7 +574,8 @@ int vima_op_kv_scatter(VimaHandle* h, const float* in, const int32_t* list, int 
 int vima_op_seq_kv_store(VimaHandle* h, const float* in, int64_t ld_in, const int32_t* list, int n, int L, int N, int Lmax, int n_blocks,
                          float* out, vima_stream_t stream);
 int vima_op_broadcast_rows(VimaHandle* h, const float* src, int64_t rows, int E, int period, float* out, vima_stream_t stream);
-/* The decoder-only sequence (launch_seq_embed, _prefill, _step, launch_seq_restart): prompt (element strides sb, sl), pmask [samples, Lp],
+/* The decoder-only sequence (launch_seq_embed, _prefill, launch_seq_restart; vima_op_seq_embed_step is launch_seq_embed_chunk, the chunk kernel at
+ * T = 1, and refuses Q + has_act > 64, rows past n_pos, E % 4): prompt (element strides sb, sl), pmask [samples, Lp],
  * sep [E], obs_tok [T, B, Q, E] / act_tok [T, B, E] (step: [B, Q, E] / [B, E]) -> x32 and xT (optional) [B, L, E] / [n, Lp + 1, E] /
  * [B, Q + has_act, E], mask; cache_mask [samples, n_pos], posbase [samples], fresh [samples] are the episode state. */
 int vima_op_seq_embed(VimaHandle* h, const float* prompt, int64_t sb, int64_t sl, const uint8_t* pmask, const float* sep, const float* obs_tok,

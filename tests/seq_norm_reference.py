@@ -4,9 +4,10 @@ launch per case, per output element):
 
   layernorm_kernel<T>, <bf16, bf16>, layernorm_rows2_kernel<1..4>, layernorm2_kernel, rms_stats_kernel              (vima_op_norm)
   prompt_assemble_kernel, prompt_assemble_stats_kernel                                                               (vima_op_prompt_assemble)
-  dec_embed_kernel, dec_embed_step_kernel, restart_samples_kernel, prompt_pos_kernel, gather_pred_kernel            (vima_op_dec_embed ...)
+  dec_embed_kernel, dec_embed_chunk_kernel at T = 1, restart_samples_kernel, prompt_pos_kernel, gather_pred_kernel  (vima_op_dec_embed, _step ...)
   action_l1_kernel, add_row_table_kernel, rows_to_headmajor_kernel, kv_scatter_kernel                               (vima_op_action_l1 ...)
-  seq_embed_kernel, seq_embed_prefill_kernel, seq_embed_step_kernel, seq_restart_kernel, seq_kv_store_kernel, broadcast_rows_kernel
+  seq_embed_kernel, seq_embed_prefill_kernel, seq_embed_chunk_kernel at T = 1 (vima_op_seq_embed_step), seq_restart_kernel, seq_kv_store_kernel,
+  broadcast_rows_kernel
 
 References are fp64 (norms, ssq, action_l1) or exact fp32 (everything else: a gather plus ONE IEEE fp32 add, which torch on the CPU performs
 with the same bits), and are written with cumsum / cat / index_select / reshape / permute only -- none of the kernels' index arithmetic.

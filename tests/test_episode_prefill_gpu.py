@@ -423,6 +423,24 @@ def test_refused_chunk_in_the_linear_cache_changes_nothing():
     _same_next_step(run, twin)
 
 
+def test_a_call_of_more_than_512_rows_is_refused_and_changes_nothing():
+    """The position scan of the incremental embedding holds 512 rows, so every incremental call is bounded by its T slots of Q + 1 rows,
+    T (Q + 1) <= 512: a single step (Q = 512: a slot of 513; at batch step 0, whose slot lacks the action row, the same T and Q are refused
+    although the call has 512 rows) like a chunk (T = 2, Q = 256: 514). The refusal names the call and comes before anything changes: step 0
+    would otherwise end the running episode batch."""
+    (run, _), (twin, _) = _twins(0, 7)
+    left = run.pol.steps_left().tolist()
+    E = run.otok.shape[-1]
+    wide, wmask = torch.zeros(B, 512, E, device=DEV), torch.ones(B, 512, dtype=torch.bool, device=DEV)
+    for step, act in ((0, None), (run.t, run.atok[run.t - 1])):
+        with pytest.raises(RuntimeError, match="vima_decode_step: .*at most 512 rows"):
+            run.pol.forward_step(wide, wmask, act, run.pt, run.pm, step)
+    with pytest.raises(RuntimeError, match="vima_decode_chunk: .*at most 512 rows"):
+        run.pol.forward_steps(torch.stack([wide[:, :256]] * 2), torch.stack([wmask[:, :256]] * 2), run.atok[run.t - 1:run.t + 1], run.pt, run.pm, run.t)
+    assert run.pol.steps_left().tolist() == left
+    _same_next_step(run, twin)
+
+
 def test_refused_chunk_in_the_ring_changes_nothing():
     """Sample 2 is never restarted: at batch step 8 it has age 39 and one step left (it would write rows 39 .. 43); a 2-step chunk does not fit in
     front of row 48, would skip 9 rows and write 10."""

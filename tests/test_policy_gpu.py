@@ -334,6 +334,33 @@ def test_incremental_decoding_matches_full_history(prec, cfgname, T):
     assert max_rel(pol.forward(otok, omask.to(DEV), atok, ptok, pmask.to(DEV)), full) < 1e-6
 
 
+@pytest.mark.parametrize("prec", ["fp32", "bf16"])
+def test_incremental_decoding_with_64_object_tokens(prec):
+    """Q = 64: a step of 64 / 65 rows, the smallest size beyond the 64 rows a step's embedding once held (a step is a chunk of one:
+    dec_embed_chunk_kernel, up to 512 rows). Every step against the re-fed history, random object masks with the first token valid;
+    forward_steps with one step is forward_step, bit for bit, on a twin policy."""
+    cfg = syn.config("2M")
+    sd = syn.make_state_dict(cfg, 11)
+    pol, twin = loaded_policy(cfg, sd, prec), loaded_policy(cfg, sd, prec)
+    g = torch.Generator().manual_seed(6)
+    B, Lp, Q, E, T = 2, 8, 64, cfg.embed_dim, 3
+    ptok = torch.randn(Lp, B, E, generator=g).to(DEV)
+    pmask = torch.ones(B, Lp, dtype=torch.bool)
+    pmask[1, 5:] = False
+    otok = torch.randn(T, B, Q, E, generator=g).to(DEV)
+    omask = torch.rand(T, B, Q, generator=g) > 0.25
+    omask[:, :, 0] = True
+    atok = torch.randn(T - 1, B, E, generator=g).to(DEV)
+    full = pol.forward(otok, omask.to(DEV), atok, ptok, pmask.to(DEV))
+    tol = 2e-5 if prec == "fp32" else 4e-2
+    for t in range(T):
+        step = pol.forward_step(otok[t], omask[t], atok[t - 1] if t > 0 else None, ptok, pmask, t)
+        assert step.shape == (B, E) and torch.isfinite(step).all()
+        assert max_rel(step, full[t]) < tol, (prec, t, max_rel(step, full[t]))
+        one = twin.forward_steps(otok[t:t + 1], omask[t:t + 1], atok[t - 1:t] if t > 0 else None, ptok, pmask, t)
+        assert one.shape == (1, B, E) and torch.equal(one[0], step)
+
+
 def test_incremental_decoding_full_size_200m():
     """VIMA-200M, batch 64, 512-token prompt, T = 3: the episode-cache path against the re-fed history at the
     benchmark's model size (persistent / 128x128 / 64x64 GEMM tiles and the split-key attention kernel all take part)."""

@@ -353,7 +353,7 @@ def test_c_dec_embed_step_rows_are_dec_embed_rows(E, B, Q, n_pos, prec):
 
 @pytest.mark.parametrize("prec", R.PRECS)
 def test_b_dec_embed_step_fills_pos_s(prec):
-    """Q + has_act = 64: all of pos_s[64]."""
+    """Q + has_act = 64: the most rows vima_op_dec_embed_step takes (the chunk kernel at T = 1; one row per thread of its scan up to 256)."""
     E, B, Q, n_pos = 256, 2, 63, 40
     gen = R._gen(81)
     obs, act, table = torch.randn(B, Q, E, generator=gen), torch.randn(B, E, generator=gen), torch.randn(n_pos, E, generator=gen)
@@ -366,6 +366,24 @@ def test_b_dec_embed_step_fills_pos_s(prec):
     assert rc == 0, msg
     _same("dec_embed_step Q63", "x32", x, want), _same("dec_embed_step Q63", "xT", xT, R.rounded(prec, want))
     st.check("dec_embed_step Q63")
+
+
+@pytest.mark.parametrize("prec", R.PRECS)
+@pytest.mark.parametrize("has_act", [0, 1])
+def test_b_dec_embed_step_without_fresh(has_act, prec):
+    """fresh = NULL: no sample is fresh. Rows, hist_mask and poscnt against the reference with no restart flag set, bit for bit."""
+    E, B, Q, n_pos, L_hist, Lmax = 256, 2, 4, 512, 3, 12
+    table, steps = R.dec_chain(E, B, Q, n_pos, seed=3)
+    obs, mask, act, _ = steps[1]
+    st = _DecState(B, Lmax)
+    st.cpu["poscnt"][:] = torch.tensor([0, 5], dtype=torch.int32)
+    st.dev["poscnt"].copy_(st.cpu["poscnt"])
+    want = R.dec_step_ref(st.cpu, obs, mask, act, table, n_pos, L_hist, has_act)
+    x, xT, rc, msg = run_dec_step(prec, {**st.dev, "fresh": None}, obs, mask, act, table, n_pos, L_hist, Lmax, has_act)
+    assert rc == 0, msg
+    cid = f"dec_embed_step no fresh-{prec}-act{has_act}"
+    _same(cid, "x32", x, want), _same(cid, "xT", xT, R.rounded(prec, want))
+    st.check(cid)
 
 
 def run_prompt_pos(prec, store, sb, sl, mask, table, n_pos, lst, B, Lp, E):
@@ -628,7 +646,7 @@ def test_e_sequence_refusals(prec):
     assert "L_act" in _refused(lib.vima_op_dec_embed, prec, outs, ptr(f), ptr(u8), ptr(f), ptr(f), 512, 3, 1, 4, 1, E, ptr(out), ptr(out2), ptr(mk))
     assert "null" in _refused(lib.vima_op_dec_embed, prec, outs, ptr(f), None, ptr(f), ptr(f), 512, 2, 1, 4, 2, E, ptr(out), ptr(out2), ptr(mk))
     step = lambda *a: _refused(lib.vima_op_dec_embed_step, prec, outs, ptr(f), ptr(u8), ptr(f), ptr(f), 512, *a, E, ptr(out), ptr(out2), ptr(mk), ptr(cnt), ptr(fr))
-    assert "dec_embed_step" in step(0, 128, 1, 64, 1)                      # Q + has_act = 65: one more than pos_s[64]
+    assert "dec_embed_step" in step(0, 128, 1, 64, 1)                      # Q + has_act = 65: one more than the op takes  
     assert "dec_embed_step" in step(10, 14, 1, 4, 1)                       # L_hist + Ln = 15 > Lmax = 14
     assert "gather_pred" in _refused(lib.vima_op_gather_pred, prec, outs, ptr(f), 2, 1, 4, 8, E, ptr(out))       # row 3 + 5 = 8 of 8
     assert "prompt_pos" in _refused(lib.vima_op_prompt_pos, prec, outs, ptr(f), 258, 6, ptr(u8), ptr(f), 8, None, 1, 2, E, ptr(out))   # strides % 4

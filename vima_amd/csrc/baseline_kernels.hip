@@ -203,59 +203,14 @@ __global__ __launch_bounds__(256) void seq_embed_prefill_kernel(const float* __r
   }
 }
 
-// The rows of ONE env step, Ln = has_act + Q per sample ([a_{t-1} |] o_t^1 .. o_t^Q) at cache rows [row0, row0 + Ln); one workgroup per sample.
-// Position id = posbase[b] + running count of the rows (clamped to the table like seq_embed_kernel); the new key-mask bytes and the advanced
-// posbase are written back. fresh[b] is consumed: a restarted sample has no previous action, its action row is a masked key that takes no
-// position id, and zeros are embedded in place of the caller's act_tok row, so whatever that row holds cannot reach K / V.
-template <typename T>
-__global__ __launch_bounds__(256) void seq_embed_step_kernel(const float* __restrict__ obs_tok, const float* __restrict__ act_tok,
-                                                             const float* __restrict__ pos_table, int n_pos, float* x32, T* xT,
-                                                             uint8_t* cache_mask, int* posbase, uint8_t* fresh, int row0, int Q,
-                                                             int has_act, int E) {
-  __shared__ int pos_s[64];
-  __shared__ int skip_act;
-  const int b = blockIdx.x;
-  const int Ln = Q + has_act;
-  if (threadIdx.x == 0) {
-    int run = posbase[b];
-    const int fr = fresh[b];
-    if (fr) fresh[b] = 0;
-    skip_act = has_act && fr;
-    for (int i = 0; i < Ln; ++i) {
-      const int mk = (has_act && i == 0 && fr) ? 0 : 1;
-      int p = run;
-      run += mk;
-      p = p < 0 ? 0 : (p >= n_pos ? n_pos - 1 : p);
-      pos_s[i] = p;
-      cache_mask[(long long)b * n_pos + row0 + i] = (uint8_t)mk;
-    }
-    posbase[b] = run;
-  }
-  __syncthreads();
-  const int e4 = E >> 2;
-  for (int i = threadIdx.x; i < Ln * e4; i += 256) {
-    const int l = i / e4, c = (i % e4) * 4;
-    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (has_act && l == 0) {
-      if (!skip_act) a = *reinterpret_cast<const float4*>(act_tok + (long long)b * E + c);
-    } else {
-      a = *reinterpret_cast<const float4*>(obs_tok + ((long long)b * Q + (l - has_act)) * E + c);
-    }
-    const float4 pp = *reinterpret_cast<const float4*>(pos_table + (long long)pos_s[l] * E + c);
-    const float4 o = make_float4(a.x + pp.x, a.y + pp.y, a.z + pp.z, a.w + pp.w);
-    const long long off = ((long long)b * Ln + l) * E + c;
-    *reinterpret_cast<float4*>(x32 + off) = o;
-    store4(xT + off, o);
-  }
-}
-
-// The rows of T env steps as ONE chunk (vima_seq_decode_chunk), Ln = T (Q + 1) - (1 - has_act) per sample at cache rows [row0, row0 + Ln): slot u is
-// [a, o^1 .. o^Q] at u (Q + 1) - (1 - has_act); the first slot of batch step 0 (has_act = 0) has no action row. obs_tok [T, B, Q, E]; act_tok
-// [T, B, E] (has_act) or [T - 1, B, E]: row j is the action in front of slot j (has_act) or slot j + 1. One workgroup per sample. Every token of
-// this path is valid, so the position ids are posbase[b] + row index and need no scan; a restarted sample (fresh[b], has_act) has only the chunk's
-// FIRST action row masked: zeros are embedded at the id posbase[b] (as seq_embed_step_kernel does; act_tok is not read), it takes no id and the rows
-// behind it count from posbase[b]. Ids are clamped to the table like seq_embed_kernel's. Writes the key-mask bytes of the chunk's rows, advances
-// posbase by the valid rows and consumes fresh.
+// The rows of T env steps as ONE chunk (vima_seq_decode_step is T = 1, vima_seq_decode_chunk T > 1), Ln = T (Q + 1) - (1 - has_act) per sample at
+// cache rows [row0, row0 + Ln): slot u is [a, o^1 .. o^Q] at u (Q + 1) - (1 - has_act); the first slot of batch step 0 (has_act = 0) has no action
+// row. obs_tok [T, B, Q, E]; act_tok [T, B, E] (has_act) or [T - 1, B, E]: row j is the action in front of slot j (has_act) or slot j + 1. One
+// workgroup per sample. Every token of this path is valid, so the position ids are posbase[b] + row index and need no scan; a restarted sample
+// (fresh[b], has_act) has no previous action, so only the chunk's FIRST action row is masked: zeros are embedded at the id posbase[b] in place of
+// the caller's act_tok row (which is not read, so whatever it holds cannot reach K / V), it takes no id and the rows behind it count from
+// posbase[b]. Ids are clamped to the table like seq_embed_kernel's. Writes the key-mask bytes of the chunk's rows, advances posbase by the valid
+// rows and consumes fresh.
 template <typename T>
 __global__ __launch_bounds__(256) void seq_embed_chunk_kernel(const float* __restrict__ obs_tok, const float* __restrict__ act_tok,
                                                               const float* __restrict__ pos_table, int n_pos, float* x32, T* xT,
@@ -405,20 +360,6 @@ int launch_seq_embed_prefill(const float* prompt, long long sb, long long sl, co
   else
     hipLaunchKernelGGL(seq_embed_prefill_kernel<float>, dim3(nblk(rows, 4)), dim3(256), 0, st, prompt, sb, sl, pmask, sep, pos_table, n_pos, x32,
                        (float*)xT, mask, cache_mask, posbase, list, n, Lp, E);
-  return (int)hipGetLastError();
-}
-
-int launch_seq_embed_step(const float* obs_tok, const float* act_tok, const float* pos_table, int n_pos, float* x32, void* xT,
-                          uint8_t* cache_mask, int* posbase, uint8_t* fresh, int row0, int B, int Q, int has_act, int E, bool is_bf16,
-                          hipStream_t st) {
-  if (B <= 0) return 0;
-  if (Q <= 0 || Q + has_act > 64 || E % 4 || row0 < 0 || row0 + Q + has_act > n_pos || (has_act && !act_tok)) return (int)hipErrorInvalidValue;
-  if (is_bf16)
-    hipLaunchKernelGGL(seq_embed_step_kernel<bf16_t>, dim3(B), dim3(256), 0, st, obs_tok, act_tok, pos_table, n_pos, x32, (bf16_t*)xT, cache_mask,
-                       posbase, fresh, row0, Q, has_act, E);
-  else
-    hipLaunchKernelGGL(seq_embed_step_kernel<float>, dim3(B), dim3(256), 0, st, obs_tok, act_tok, pos_table, n_pos, x32, (float*)xT, cache_mask,
-                       posbase, fresh, row0, Q, has_act, E);
   return (int)hipGetLastError();
 }
 

@@ -150,8 +150,34 @@ int baseline_ready(VimaHandle* h, const char* fn) {
   return check_ready(h);
 }
 
+// Workspace of one pass of HFGPT blocks over rq rows: q | k | v of the call (qcols = 3E) or its q alone (E: k | v go to the episode cache)
+struct HfgptWs { void *qkv, *ctx; float *a32, *n32; void *nT, *g, *u; };
+HfgptWs hfgpt_ws(Run& R, int rq, int qcols) {
+  const int E = R.h->cfg.embed_dim;
+  HfgptWs w;
+  w.qkv = R.wsT((size_t)rq * qcols);
+  w.ctx = R.wsT((size_t)rq * E);
+  w.a32 = R.ws<float>((size_t)rq * E);
+  w.n32 = R.ws<float>((size_t)rq * E);
+  w.nT = R.wsT((size_t)rq * E);
+  w.g = R.wsT((size_t)rq * 4 * E);
+  w.u = R.wsT((size_t)rq * 4 * E);
+  return w;
+}
+
+// A post-LN block behind its attention (gpt/gpt.py:231-246), per row: a = w.ctx; n = ln_1(x + c_proj(a)); h = ln_2(n + mlp(n)) -> x32 / xT
+int hfgpt_block_tail(Run& R, const VimaHandle::DecLayer& D, const HfgptWs& w, float* x32, void* xT, int rq) {
+  const int E = R.h->cfg.embed_dim;
+  R.linear(w.ctx, E, D.c_proj, rq, ACT_NONE, nullptr, 0, x32, E, w.a32, E, nullptr, 0);   // x + a
+  R.ln(w.a32, E, D.ln1_g, D.ln1_b, 1e-5f, 0, rq, E, w.n32, w.nT);                         // n = ln_1(x + a)
+  R.linear(w.nT, E, D.mgate, rq, ACT_NONE, nullptr, 0, nullptr, 0, nullptr, 0, w.g, 4 * E);
+  R.linear(w.nT, E, D.fc, rq, ACT_GELU, w.g, 4 * E, nullptr, 0, nullptr, 0, w.u, 4 * E);   // gelu(c_fc(n)) * gated_layer(n)
+  R.linear(w.u, 4 * E, D.mproj, rq, ACT_NONE, nullptr, 0, w.n32, E, w.a32, E, nullptr, 0);  // n + m
+  return R.ln(w.a32, E, D.ln2_g, D.ln2_b, 1e-5f, 0, rq, E, x32, xT);                        // h = ln_2(n + m)
+}
+
 // HFGPT.forward (gpt/gpt.py:45-80) on an assembled sequence: x32 / xT [B*L, E] (positions already added), key mask [B, L].
-// Post-LN blocks (gpt/gpt.py:231-246): a = attn(x); n = ln_1(x + a); h = ln_2(n + mlp(n)). Result in x32 (and xT).
+// Post-LN blocks: a = attn(x), then hfgpt_block_tail. Result in x32 (and xT).
 // kv_cache (vima_seq_prefill / vima_seq_decode_restart): every layer's k | v rows are also COPIED to rows [0, L) of the episode cache
 // [layer][kv_B][kv_Lmax][2E], block kv_list[r] (DEVICE array; nullptr: r) for the r-th sample of this call. A copy, not the c_attn GEMM's
 // row-remap epilogue: the attention of these rows reads the dense q | k | v of the call, so the remap would need the k | v columns twice (a
@@ -162,13 +188,8 @@ int hfgpt_stack(Run& R, float* x32, void* xT, const uint8_t* mask, int B, int L,
                 int kv_B = 0, int kv_Lmax = 0, const int* kv_rowmap = nullptr) {
   VimaHandle* h = R.h;
   const int E = h->cfg.embed_dim, Hs = h->cfg.sattn_n_heads, rq = B * L;
-  void* qkv = R.wsT((size_t)rq * 3 * E);
-  void* ctx = R.wsT((size_t)rq * E);
-  float* a32 = R.ws<float>((size_t)rq * E);
-  float* n32 = R.ws<float>((size_t)rq * E);
-  void* nT = R.wsT((size_t)rq * E);
-  void* g = R.wsT((size_t)rq * 4 * E);
-  void* u = R.wsT((size_t)rq * 4 * E);
+  const HfgptWs w = hfgpt_ws(R, rq, 3 * E);
+  void* qkv = w.qkv;   // q | k | v of the call
   if (R.err) return R.err;
   for (int i = 0; i < h->cfg.xf_n_layers; ++i) {
     auto& D = h->dec[i];
@@ -181,69 +202,32 @@ int hfgpt_stack(Run& R, float* x32, void* xT, const uint8_t* mask, int B, int L,
                                    h->bf16, R.st), "seq_kv_store");
     AttnArgs s;   // Attention._attn (gpt/gpt.py:268-301): /sqrt(d), w*b + -1e4*(1-b), + (1-mask)*finfo.min
     s.q = qkv; s.ldq = 3 * E; s.k = R.offT(qkv, E); s.ldk = 3 * E; s.v = R.offT(qkv, 2 * E); s.ldv = 3 * E;
-    s.out = ctx; s.ldo = E; s.B = B; s.H = Hs; s.Lq = L; s.Lk = L; s.D = E / Hs; s.kmask = mask;
+    s.out = w.ctx; s.ldo = E; s.B = B; s.H = Hs; s.Lq = L; s.Lk = L; s.D = E / Hs; s.kmask = mask;
     s.scale = 1.0f / sqrtf((float)(E / Hs)); s.mode = ATTN_CAUSAL;
     R.attn(s, h->attn_impl);
-    R.linear(ctx, E, D.c_proj, rq, ACT_NONE, nullptr, 0, x32, E, a32, E, nullptr, 0);   // x + a
-    R.ln(a32, E, D.ln1_g, D.ln1_b, 1e-5f, 0, rq, E, n32, nT);                           // n = ln_1(x + a)
-    R.linear(nT, E, D.mgate, rq, ACT_NONE, nullptr, 0, nullptr, 0, nullptr, 0, g, 4 * E);
-    R.linear(nT, E, D.fc, rq, ACT_GELU, g, 4 * E, nullptr, 0, nullptr, 0, u, 4 * E);     // gelu(c_fc(n)) * gated_layer(n)
-    R.linear(u, 4 * E, D.mproj, rq, ACT_NONE, nullptr, 0, n32, E, a32, E, nullptr, 0);  // n + m
-    R.ln(a32, E, D.ln2_g, D.ln2_b, 1e-5f, 0, rq, E, x32, xT);                           // h = ln_2(n + m)
-    if (R.err) return R.err;
+    if (hfgpt_block_tail(R, D, w, x32, xT, rq)) return R.err;
   }
   return R.err;
 }
 
-// The same blocks for the rows of ONE env step against the episode cache (vima_seq_decode_step): x32 / xT [B * Lq, E] are the new rows at cache
-// rows [row, row + Lq) of every sample. c_attn appends their k | v to the layer's cache through the GEMM's row-remap epilogue (row b Lq + i ->
-// b Lmax + row + i; one launch with the q columns dense where decode_launch has that form, two otherwise) and the new queries attend to
-// [0, row + Lq) with the causal offset `row` and the cache's key mask. Everything after the attention acts per row, as in hfgpt_stack.
-// Lk / win_end: the keys read and the end of the causal window -- row + Lq / 0 (the plain rule) for the linear cache; with option seq_ring the
-// written image [0, hw) and row + Lq: the rows from win_end on hold OLDER history of the ring, which stays visible (AttnArgs::win_end).
+// The same blocks for the rows of ONE unit (T env steps; vima_seq_decode_step: T = 1) against the episode cache: x32 / xT [B * Lq, E] are the new
+// rows at cache rows [row, row + Lq) of every sample. c_attn appends their k | v to the layer's cache (c_attn_append) and the new queries attend
+// to the cache (attn_from_cache: Lk keys, causal window [row, win_end)). Everything after the attention acts per row, as in hfgpt_stack.
 int hfgpt_step_stack(Run& R, float* x32, void* xT, int B, int Lq, int row, int Lmax, int Lk, int win_end) {
   VimaHandle* h = R.h;
   const int E = h->cfg.embed_dim, Hs = h->cfg.sattn_n_heads, rq = B * Lq;
-  void* q = R.wsT((size_t)rq * E);
-  void* ctx = R.wsT((size_t)rq * E);
-  float* a32 = R.ws<float>((size_t)rq * E);
-  float* n32 = R.ws<float>((size_t)rq * E);
-  void* nT = R.wsT((size_t)rq * E);
-  void* g = R.wsT((size_t)rq * 4 * E);
-  void* u = R.wsT((size_t)rq * 4 * E);
+  const HfgptWs w = hfgpt_ws(R, rq, E);
   if (R.err) return R.err;
   for (int i = 0; i < h->cfg.xf_n_layers; ++i) {
     auto& D = h->dec[i];
     void* cache = R.offT(h->ep_kv, (long long)i * B * Lmax * 2 * E);
-    if (h->bf16 && !D.c_attn.ws && E % 128 == 0 && !gemm_splitk_enabled(&h->tune)) {
-      GemmArgs gq;
-      gq.A = xT; gq.lda = E; R.setW(gq, D.c_attn, 0); gq.M = rq; gq.N = 3 * E; gq.K = E; gq.bias = D.c_attn.b;
-      gq.outT_lo = q; gq.ldT_lo = E; gq.split_n = E;
-      gq.outT = cache; gq.ldT = 2 * E; gq.rb = Lq; gq.s_hi = Lmax; gq.s_lo = 1; gq.ro = row;
-      R.gemm(gq);
-    } else {
-      GemmArgs gq;
-      gq.A = xT; gq.lda = E; R.setW(gq, D.c_attn, 0); gq.M = rq; gq.N = E; gq.K = E; gq.bias = D.c_attn.b;
-      gq.outT = q; gq.ldT = E;
-      R.gemm(gq);
-      GemmArgs gk;
-      gk.A = xT; gk.lda = E; R.setW(gk, D.c_attn, E); gk.M = rq; gk.N = 2 * E; gk.K = E;
-      gk.bias = D.c_attn.b ? D.c_attn.b + E : nullptr;
-      gk.outT = cache; gk.ldT = 2 * E; gk.rb = Lq; gk.s_hi = Lmax; gk.s_lo = 1; gk.ro = row;
-      R.gemm(gk);
-    }
+    c_attn_append(R, D.c_attn, xT, rq, Lq, row, Lmax, cache, w.qkv);
     AttnArgs s;
-    s.q = q; s.ldq = E; s.k = cache; s.ldk = 2 * E; s.v = R.offT(cache, E); s.ldv = 2 * E;
-    s.out = ctx; s.ldo = E; s.B = B; s.H = Hs; s.Lq = Lq; s.Lk = Lk; s.Lk_rows = Lmax; s.q_off = row; s.win_end = win_end; s.D = E / Hs;
-    s.kmask = h->ep_mask; s.scale = 1.0f / sqrtf((float)(E / Hs)); s.mode = ATTN_CAUSAL;
+    attn_from_cache(R, s, w.qkv, cache, row, Lmax, Lk, win_end);
+    s.out = w.ctx; s.ldo = E; s.B = B; s.H = Hs; s.Lq = Lq; s.D = E / Hs;
+    s.scale = 1.0f / sqrtf((float)(E / Hs)); s.mode = ATTN_CAUSAL;
     R.attn(s, h->attn_impl);
-    R.linear(ctx, E, D.c_proj, rq, ACT_NONE, nullptr, 0, x32, E, a32, E, nullptr, 0);   // x + a
-    R.ln(a32, E, D.ln1_g, D.ln1_b, 1e-5f, 0, rq, E, n32, nT);                           // n = ln_1(x + a)
-    R.linear(nT, E, D.mgate, rq, ACT_NONE, nullptr, 0, nullptr, 0, nullptr, 0, g, 4 * E);
-    R.linear(nT, E, D.fc, rq, ACT_GELU, g, 4 * E, nullptr, 0, nullptr, 0, u, 4 * E);     // gelu(c_fc(n)) * gated_layer(n)
-    R.linear(u, 4 * E, D.mproj, rq, ACT_NONE, nullptr, 0, n32, E, a32, E, nullptr, 0);  // n + m
-    R.ln(a32, E, D.ln2_g, D.ln2_b, 1e-5f, 0, rq, E, x32, xT);                           // h = ln_2(n + m)
-    if (R.err) return R.err;
+    if (hfgpt_block_tail(R, D, w, x32, xT, rq)) return R.err;
   }
   return R.err;
 }

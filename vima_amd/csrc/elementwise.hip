@@ -493,53 +493,14 @@ __global__ __launch_bounds__(256) void dec_embed_kernel(const float* __restrict_
   }
 }
 
-// Incremental form of dec_embed_kernel for ONE env step: the newest tokens of every sample ([a_{t-1},] o_t^1 .. o_t^Q) get
-// position ids that continue the sample's running count of valid tokens (cumsum(mask) - 1 over the whole history,
-// xattn_gpt.py:96-103), the count and the history key mask are updated in the episode state.
-template <typename T>
-__global__ __launch_bounds__(256) void dec_embed_step_kernel(const float* __restrict__ obs_tok,
-                                                              const uint8_t* __restrict__ obs_mask,
-                                                              const float* __restrict__ act_tok,
-                                                              const float* __restrict__ pos_table, int n_pos, float* x32,
-                                                              T* xT, uint8_t* hist_mask, int* poscnt, int L_hist, int Lmax,
-                                                              int Q, int has_act, int E, uint8_t* fresh) {
-  __shared__ int pos_s[64];
-  const int b = blockIdx.x;
-  const int Ln = Q + has_act;
-  if (threadIdx.x == 0) {
-    int run = poscnt[b];
-    // a sample restarted by vima_decode_restart has no previous action: its action slot of this step is a masked (invalid) token
-    const int fr = fresh ? fresh[b] : 0;
-    if (fr) fresh[b] = 0;
-    for (int i = 0; i < Ln; ++i) {
-      const int mk = (has_act && i == 0) ? (fr ? 0 : 1) : (obs_mask[(long long)b * Q + (i - has_act)] ? 1 : 0);
-      run += mk;
-      int p = run - 1;
-      p = p < 0 ? 0 : (p >= n_pos ? n_pos - 1 : p);
-      pos_s[i] = p;
-      hist_mask[(long long)b * Lmax + L_hist + i] = (uint8_t)mk;
-    }
-    poscnt[b] = run;
-  }
-  __syncthreads();
-  const int e4 = E >> 2;
-  for (int i = threadIdx.x; i < Ln * e4; i += 256) {
-    const int l = i / e4, c = (i % e4) * 4;
-    const float* src = (has_act && l == 0) ? act_tok + (long long)b * E : obs_tok + ((long long)b * Q + (l - has_act)) * E;
-    const float4 a = *reinterpret_cast<const float4*>(src + c);
-    const float4 pp = *reinterpret_cast<const float4*>(pos_table + (long long)pos_s[l] * E + c);
-    const float4 o = make_float4(a.x + pp.x, a.y + pp.y, a.z + pp.z, a.w + pp.w);
-    const long long off = ((long long)b * Ln + l) * E + c;
-    store4(x32 + off, o);
-    if (xT) store4(xT + off, o);
-  }
-}
-
-// Multi-step form of dec_embed_step_kernel (vima_decode_chunk): Tn env steps of every sample in one pass. The chunk's rows are the slots
+// Incremental form of dec_embed_kernel (vima_decode_step is Tn = 1, vima_decode_chunk Tn > 1): Tn env steps of every sample in one pass, the newest
+// tokens get position ids that continue the sample's running count of valid tokens (cumsum(mask) - 1 over the whole history, xattn_gpt.py:96-103),
+// the count and the history key mask are updated in the episode state. The chunk's rows are the slots
 // [a_{t-1}, o_t^1 .. o_t^Q] of steps t = step .. step + Tn - 1 back to back; at batch step 0 (has_act = 0) the first slot has no action row, so
 // Ln = Tn (Q + 1) - (1 - has_act) <= 512 rows. obs_tok [Tn,B,Q,E], obs_mask [Tn,B,Q]; act_tok [Tn,B,E] (has_act) or [Tn-1,B,E]: the action row of
 // slot u is act_tok[u - (1 - has_act)]. Position ids continue poscnt[b] over the chunk: each thread owns a contiguous run of rows, block-wide
-// scan of the run totals in LDS as in prompt_pos_kernel (no thread walks the rows alone). fresh[b] masks the action row of the FIRST slot only.
+// scan of the run totals in LDS as in prompt_pos_kernel (no thread walks the rows alone). fresh[b] (a sample restarted by vima_decode_restart has
+// no previous action) masks the action row of the FIRST slot only; fresh == nullptr: no sample is fresh.
 // One workgroup per sample: it alone reads and then writes poscnt[b] / fresh[b].
 template <typename T>
 __global__ __launch_bounds__(256) void dec_embed_chunk_kernel(const float* __restrict__ obs_tok, const uint8_t* __restrict__ obs_mask,
@@ -551,7 +512,7 @@ __global__ __launch_bounds__(256) void dec_embed_chunk_kernel(const float* __res
   const int b = blockIdx.x;
   const int shift = 1 - has_act;              // chunk row l is row l + shift of a chunk whose every slot has an action row
   const int Ln = Tn * (Q + 1) - shift;
-  const int fr = fresh[b];
+  const int fr = fresh ? fresh[b] : 0;
   const int base = poscnt[b];
   const int per = (Ln + 255) / 256;
   const int l0 = threadIdx.x * per;
@@ -1060,26 +1021,12 @@ int launch_dec_embed(const float* obs_tok, const uint8_t* obs_mask, const float*
   return (int)hipGetLastError();
 }
 
-int launch_dec_embed_step(const float* obs_tok, const uint8_t* obs_mask, const float* act_tok, const float* pos_table, int n_pos,
-                          float* x32, void* xT, uint8_t* hist_mask, int* poscnt, int L_hist, int Lmax, int B, int Q,
-                          int has_act, int E, bool is_bf16, hipStream_t st, uint8_t* fresh) {
-  if (B <= 0) return 0;
-  if (Q + has_act > 64 || E % 4 || L_hist + Q + has_act > Lmax) return (int)hipErrorInvalidValue;
-  if (is_bf16)
-    hipLaunchKernelGGL(dec_embed_step_kernel<bf16_t>, dim3(B), dim3(256), 0, st, obs_tok, obs_mask, act_tok, pos_table, n_pos,
-                       x32, (bf16_t*)xT, hist_mask, poscnt, L_hist, Lmax, Q, has_act, E, fresh);
-  else
-    hipLaunchKernelGGL(dec_embed_step_kernel<float>, dim3(B), dim3(256), 0, st, obs_tok, obs_mask, act_tok, pos_table, n_pos,
-                       x32, (float*)xT, hist_mask, poscnt, L_hist, Lmax, Q, has_act, E, fresh);
-  return (int)hipGetLastError();
-}
-
 int launch_dec_embed_chunk(const float* obs_tok, const uint8_t* obs_mask, const float* act_tok, const float* pos_table, int n_pos,
                            float* x32, void* xT, uint8_t* hist_mask, int* poscnt, int row0, int Lmax, int T, int B, int Q,
                            int has_act, int E, bool is_bf16, hipStream_t st, uint8_t* fresh) {
   if (B <= 0) return 0;
   const long long Ln = (long long)T * (Q + 1) - (has_act ? 0 : 1);
-  if (T < 1 || Q < 1 || Ln < 1 || Ln > 512 || E % 4 || row0 < 0 || row0 + Ln > Lmax || !fresh || !poscnt || !hist_mask || (Ln > Q && !act_tok))
+  if (T < 1 || Q < 1 || Ln < 1 || Ln > 512 || E % 4 || row0 < 0 || row0 + Ln > Lmax || !poscnt || !hist_mask || (Ln > Q && !act_tok))
     return (int)hipErrorInvalidValue;
   if (is_bf16)
     hipLaunchKernelGGL(dec_embed_chunk_kernel<bf16_t>, dim3(B), dim3(256), 0, st, obs_tok, obs_mask, act_tok, pos_table, n_pos,

@@ -231,19 +231,15 @@ int launch_rows_to_headmajor(const void* in, void* out, int L, int N, int D, boo
 int launch_dec_embed(const float* obs_tok, const uint8_t* obs_mask, const float* act_tok, const float* pos_table,
                      int n_pos, float* x32, void* xT, uint8_t* mask, int T, int B, int Q, int L_act, int E,
                      bool is_bf16, hipStream_t st);
-// one env step of incremental decoding: newest tokens ([prev action,] Q observation tokens) of every sample -> x32 / xT
-// [B, Q+has_act, E]; position ids continue poscnt[b]; hist_mask[b][L_hist + i] and poscnt[b] are updated
-int launch_dec_embed_step(const float* obs_tok, const uint8_t* obs_mask, const float* act_tok, const float* pos_table, int n_pos,
-                          float* x32, void* xT, uint8_t* hist_mask, int* poscnt, int L_hist, int Lmax, int B, int Q,
-                          int has_act, int E, bool is_bf16, hipStream_t st, uint8_t* fresh = nullptr);
-// T env steps of incremental decoding in one pass (vima_decode_chunk): obs_tok [T,B,Q,E], obs_mask [T,B,Q], act_tok [T,B,E] (has_act) or
-// [T-1,B,E] (batch step 0: the first slot has no action row) -> x32 / xT [B, Ln, E], Ln = T (Q + 1) - (1 - has_act) <= 512 rows = the slots
-// [action, Q obs] back to back; position ids continue poscnt[b]; hist_mask[b][row0 + l], poscnt[b] and fresh[b] (first slot only) are updated
+// T >= 1 env steps of incremental decoding in one pass (vima_decode_step is T = 1): obs_tok [T,B,Q,E], obs_mask [T,B,Q], act_tok [T,B,E] (has_act)
+// or [T-1,B,E] (batch step 0: the first slot has no action row) -> x32 / xT [B, Ln, E], Ln = T (Q + 1) - (1 - has_act) <= 512 rows = the slots
+// [action, Q obs] back to back; position ids continue poscnt[b]; hist_mask[b][row0 + l], poscnt[b] and fresh[b] (first slot only; optional: nullptr
+// = no sample is fresh) are updated
 int launch_dec_embed_chunk(const float* obs_tok, const uint8_t* obs_mask, const float* act_tok, const float* pos_table, int n_pos,
                            float* x32, void* xT, uint8_t* hist_mask, int* poscnt, int row0, int Lmax, int T, int B, int Q,
                            int has_act, int E, bool is_bf16, hipStream_t st, uint8_t* fresh);
 // per-sample episode restart: for flags[b] != 0 (device array) mask sample b's whole history, reset its position counter, mark its
-// next action slot absent (fresh[b] = 1, consumed by launch_dec_embed_step)
+// next action slot absent (fresh[b] = 1, consumed by launch_dec_embed_chunk)
 int launch_restart_samples(const uint8_t* flags, uint8_t* hist_mask, int* poscnt, uint8_t* fresh, int B, int Lmax, hipStream_t st);
 // prompt + xattn_positions_embed[cumsum(mask)-1] -> T [B*Lp, E]; input strides in elements (seq-first views ok)
 // list (DEVICE array [B], optional): output block r is computed from sample list[r] of prompt / mask instead of sample r
@@ -285,13 +281,10 @@ int launch_seq_embed(const float* prompt, long long sb, long long sl, const uint
 int launch_seq_embed_prefill(const float* prompt, long long sb, long long sl, const uint8_t* pmask, const float* sep, const float* pos_table,
                              int n_pos, float* x32, void* xT, uint8_t* mask, uint8_t* cache_mask, int* posbase, const int* list, int n, int Lp,
                              int E, bool is_bf16, hipStream_t st);
-// the rows of one env step ([prev action,] Q observation tokens) of every sample -> x32 / xT [B, Q + has_act, E]; positions continue posbase[b];
-// cache_mask[b][row0 + i] and posbase[b] are updated, fresh[b] is consumed (a fresh sample's action row: zeros, key mask 0, no position id)
-int launch_seq_embed_step(const float* obs_tok, const float* act_tok, const float* pos_table, int n_pos, float* x32, void* xT,
-                          uint8_t* cache_mask, int* posbase, uint8_t* fresh, int row0, int B, int Q, int has_act, int E, bool is_bf16,
-                          hipStream_t st);
-// the rows of T env steps as one chunk: T (Q + 1) rows per sample (one fewer without has_act: the first slot of batch step 0 has no action row) at
-// cache rows [row0, ..); obs_tok [T, B, Q, E], act_tok [T, B, E] (has_act) / [T - 1, B, E]. No row limit beyond row0 + rows <= n_pos.
+// the rows of T >= 1 env steps as one chunk (vima_seq_decode_step is T = 1): T (Q + 1) rows per sample (one fewer without has_act: the first slot of
+// batch step 0 has no action row) at cache rows [row0, ..); obs_tok [T, B, Q, E], act_tok [T, B, E] (has_act) / [T - 1, B, E] -> x32 / xT; positions
+// continue posbase[b]; cache_mask[b][row0 + i] and posbase[b] are updated, fresh[b] is consumed (a fresh sample's first action row: zeros, key
+// mask 0, no position id). No row limit beyond row0 + rows <= n_pos.
 int launch_seq_embed_chunk(const float* obs_tok, const float* act_tok, const float* pos_table, int n_pos, float* x32, void* xT,
                            uint8_t* cache_mask, int* posbase, uint8_t* fresh, int row0, int T, int B, int Q, int has_act, int E, bool is_bf16,
                            hipStream_t st);

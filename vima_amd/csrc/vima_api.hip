@@ -892,6 +892,39 @@ struct Run {
     (run).other(e___, what);                \
   } while (0)
 
+// ------------------------------------------------------------------------------------------------ episode cache (decode_launch, hfgpt_step_stack)
+// c_attn of the new rows xT [rq = B Lq, E]: q dense [rq, E], k | v APPENDED to the layer's episode cache [B][Lmax][2E] by the GEMM's row-remap
+// epilogue (row b Lq + i -> b Lmax + row + i). One launch (q columns dense, k | v columns remapped) where the split form exists, two otherwise.
+int c_attn_append(Run& R, const Lin& c_attn, const void* xT, int rq, int Lq, int row, int Lmax, void* cache, void* q) {
+  VimaHandle* h = R.h;
+  const int E = h->cfg.embed_dim;
+  if (h->bf16 && !c_attn.ws && E % 128 == 0 && !gemm_splitk_enabled(&h->tune)) {
+    GemmArgs gq;
+    gq.A = xT; gq.lda = E; R.setW(gq, c_attn, 0); gq.M = rq; gq.N = 3 * E; gq.K = E; gq.bias = c_attn.b;
+    gq.outT_lo = q; gq.ldT_lo = E; gq.split_n = E;
+    gq.outT = cache; gq.ldT = 2 * E; gq.rb = Lq; gq.s_hi = Lmax; gq.s_lo = 1; gq.ro = row;
+    return R.gemm(gq);
+  }
+  GemmArgs gq;
+  gq.A = xT; gq.lda = E; R.setW(gq, c_attn, 0); gq.M = rq; gq.N = E; gq.K = E; gq.bias = c_attn.b;
+  gq.outT = q; gq.ldT = E;
+  R.gemm(gq);
+  GemmArgs gk;
+  gk.A = xT; gk.lda = E; R.setW(gk, c_attn, E); gk.M = rq; gk.N = 2 * E; gk.K = E;
+  gk.bias = c_attn.b ? c_attn.b + E : nullptr;
+  gk.outT = cache; gk.ldT = 2 * E; gk.rb = Lq; gk.s_hi = Lmax; gk.s_lo = 1; gk.ro = row;
+  return R.gemm(gk);
+}
+
+// The new queries q [B Lq, E] against the layer's episode cache: keys [0, Lk) under the episode key mask with the causal offset `row`. Linear cache:
+// Lk = row + Lq, win_end = 0 (the plain rule). Ring: row is the write pointer, the keys are the whole written image [0, hw) and only the unit's own
+// rows [row, win_end = row + Lq) are causal; the rows behind hold OLDER history of the ring, which stays visible (AttnArgs::win_end).
+void attn_from_cache(Run& R, AttnArgs& s, const void* q, void* cache, int row, int Lmax, int Lk, int win_end) {
+  const int E = R.h->cfg.embed_dim;
+  s.q = q; s.ldq = E; s.k = cache; s.ldk = 2 * E; s.v = R.offT(cache, E); s.ldv = 2 * E;
+  s.kmask = R.h->ep_mask; s.Lk = Lk; s.Lk_rows = Lmax; s.q_off = row; s.win_end = win_end;
+}
+
 // ------------------------------------------------------------------------------------------------ stages
 // aux stream starts after everything already queued on the caller's stream / caller's stream waits for aux
 int fork_aux(Run& R) {
@@ -2003,6 +2036,14 @@ int vima_prompt_encode(VimaHandle* h, const int64_t* word_ids, int n_words, cons
 // self-attention reads and the end of its causal window); a full-history call has only u.Lq
 struct DecodePlan { bool inc; int has_act, kv_mode; EpisodeBook::Plan u; };
 
+// the samples a restart call flags (restart: HOST array [B])
+static std::vector<int> flagged_list(const uint8_t* restart, int B) {
+  std::vector<int> list;
+  for (int b = 0; b < B; ++b)
+    if (restart[b]) list.push_back(b);
+  return list;
+}
+
 // A unit the book refuses (vima_decode_step / _chunk, vima_seq_decode_step / _chunk): code 34, nothing has changed
 static int plan_refused(const char* fn, const char* restart_fn, const EpisodeBook& bk, const EpisodeBook::Plan& p, int T) {
   const std::string what = std::string(fn) + ": " + std::to_string(T) + " step(s) from step " + std::to_string(bk.next);
@@ -2054,8 +2095,9 @@ static int decode_prepare(VimaHandle* h, const float* act_tok, int T, int B, int
   const int Lmax = h->cfg.n_positions;
   const bool chunk = inc && T > 1;
   const char* fn = chunk ? "vima_decode_chunk" : "vima_decode_step";
-  if (chunk && (long long)T * (Q + 1) > 512)
-    return fail("vima_decode_chunk: a chunk holds at most 512 rows (T (Q + 1) = " + std::to_string((long long)T * (Q + 1)) + ")");
+  // dec_embed_chunk_kernel's pos_s[512]. The bound is on T full slots of Q + 1 rows: batch step 0 has one row fewer and is held to the same T and Q
+  if (inc && (long long)T * (Q + 1) > 512)
+    return fail(std::string(fn) + ": an incremental call holds at most 512 rows in T slots of Q + 1 (T (Q + 1) = " + std::to_string((long long)T * (Q + 1)) + ")");
   const int Lq = inc ? T * (Q + 1) - (has_act ? 0 : 1) : T * Q + L_act;
   const bool ring = inc && h->decode_ring != 0;
   if (chunk && !ring && L_hist + Lq > Lmax)
@@ -2179,12 +2221,9 @@ static int decode_launch(VimaHandle* h, const float* obs_tok, const uint8_t* obs
     OTHER(R, launch_mask_rows_gather(prompt_mask, hpmask, hlist, B, Lp, R.st), "mask_rows_gather");
     prompt_mask = hpmask;
   }
-  if (inc && T > 1)   // a chunk of T env steps (vima_decode_chunk): Lq = T (Q + 1) [- 1 at step 0] rows per sample at row L_hist
+  if (inc)   // T env steps (a step is a chunk of one): Lq = T (Q + 1) [- 1 at step 0] rows per sample at row L_hist
     OTHER(R, launch_dec_embed_chunk(obs_tok, obs_mask, act_tok, h->pos_emb, h->cfg.n_positions, x32, xT, h->ep_mask, h->ep_poscnt,
                                     L_hist, Lmax, T, B, Q, has_act, E, h->bf16, R.st, h->ep_fresh), "dec_embed_chunk");
-  else if (inc)
-    OTHER(R, launch_dec_embed_step(obs_tok, obs_mask, act_tok, h->pos_emb, h->cfg.n_positions, x32, xT, h->ep_mask, h->ep_poscnt,
-                                   L_hist, Lmax, B, Q, has_act, E, h->bf16, R.st, h->ep_fresh), "dec_embed_step");
   else
     OTHER(R, launch_dec_embed(obs_tok, obs_mask, act_tok, h->pos_emb, h->cfg.n_positions, x32, xT, dmask, T, B, Q, L_act, E,
                               h->bf16, R.st), "dec_embed");
@@ -2295,29 +2334,10 @@ static int decode_launch(VimaHandle* h, const float* obs_tok, const uint8_t* obs
     s.out = ctx; s.ldo = E; s.B = B; s.H = Hs; s.Lq = Lq; s.D = E / Hs;
     s.scale = 1.0f / sqrtf((float)(E / Hs)); s.mode = ATTN_CAUSAL;
     if (inc) {
-      // q of the new tokens; their k / v rows are APPENDED to the layer's episode cache by the GEMM's row-remap epilogue
-      // (row b*Lq + i -> b*Lmax + L_hist + i); the new queries attend to history + themselves with a causal offset. Ring mode: L_hist is the ring's
-      // write pointer, the keys are the whole written image [0, hw) and only the step's own rows [L_hist, L_hist + Lq) are causal (AttnArgs::win_end)
+      // q of the new tokens, their k | v rows appended to the layer's episode cache at rows [L_hist, L_hist + Lq); history + themselves are the keys
       void* cache = reinterpret_cast<char*>(h->ep_kv) + (size_t)i * B * Lmax * 2 * E * h->esz();
-      if (h->bf16 && !D.c_attn.ws && E % 128 == 0 && !gemm_splitk_enabled(&h->tune)) {   // one launch: q columns dense, k | v columns appended to the cache
-        GemmArgs gq;
-        gq.A = xT; gq.lda = E; R.setW(gq, D.c_attn, 0); gq.M = rq; gq.N = 3 * E; gq.K = E; gq.bias = D.c_attn.b;
-        gq.outT_lo = qkv; gq.ldT_lo = E; gq.split_n = E;
-        gq.outT = cache; gq.ldT = 2 * E; gq.rb = Lq; gq.s_hi = Lmax; gq.s_lo = 1; gq.ro = L_hist;
-        R.gemm(gq);
-      } else {
-      GemmArgs gq;
-      gq.A = xT; gq.lda = E; R.setW(gq, D.c_attn, 0); gq.M = rq; gq.N = E; gq.K = E; gq.bias = D.c_attn.b;
-      gq.outT = qkv; gq.ldT = E;
-      R.gemm(gq);
-      GemmArgs gk;
-      gk.A = xT; gk.lda = E; R.setW(gk, D.c_attn, E); gk.M = rq; gk.N = 2 * E; gk.K = E;
-      gk.bias = D.c_attn.b ? D.c_attn.b + E : nullptr;
-      gk.outT = cache; gk.ldT = 2 * E; gk.rb = Lq; gk.s_hi = Lmax; gk.s_lo = 1; gk.ro = L_hist;
-      R.gemm(gk);
-      }
-      s.q = qkv; s.ldq = E; s.k = cache; s.ldk = 2 * E; s.v = R.offT(cache, E); s.ldv = 2 * E;
-      s.kmask = h->ep_mask; s.Lk = P.u.Lk; s.Lk_rows = Lmax; s.q_off = L_hist; s.win_end = P.u.win_end;
+      c_attn_append(R, D.c_attn, xT, rq, Lq, L_hist, Lmax, cache, qkv);
+      attn_from_cache(R, s, qkv, cache, L_hist, Lmax, P.u.Lk, P.u.win_end);
     } else {
       R.linear(xT, E, D.c_attn, rq, ACT_NONE, nullptr, 0, nullptr, 0, nullptr, 0, qkv, 3 * E);
       s.q = qkv; s.ldq = 3 * E; s.k = R.offT(qkv, E); s.ldk = 3 * E; s.v = R.offT(qkv, 2 * E); s.ldv = 3 * E;
@@ -2339,8 +2359,7 @@ static int decode_launch(VimaHandle* h, const float* obs_tok, const uint8_t* obs
     }
     if (R.err) return R.err;
   }
-  if (inc && T > 1) OTHER(R, launch_gather_pred(x32, out, T, B, Q, Lq, E, R.st, has_act), "gather_pred");   // the last obs row of every slot of the chunk
-  else if (inc) OTHER(R, launch_gather_pred(x32, out, 1, B, Lq, Lq, E, R.st), "gather_pred");   // the last new token of every sample
+  if (inc) OTHER(R, launch_gather_pred(x32, out, T, B, Q, Lq, E, R.st, has_act), "gather_pred");   // the last obs row of every slot (T = 1: row Lq - 1)
   else if (out) OTHER(R, launch_gather_pred(x32, out, T, B, Q, Lq, E, R.st), "gather_pred");
   if (hist) OTHER(R, launch_history_install(dmask, hlist, hmap, B, Lq, Lmax, h->ep_mask, h->ep_poscnt, h->ep_fresh, R.st), "history_install");
   if (dual && join_aux(R)) return 1;
@@ -2362,43 +2381,49 @@ int vima_decode(VimaHandle* h, const float* obs_tok, const uint8_t* obs_mask, co
   return rc;
 }
 
+// T env steps of the running episode batch as ONE pass of the incremental branch: Lq = T (Q + 1) rows per sample (one fewer at batch step 0) at
+// one row offset -- one unit of the ring -- instead of T passes of Q + 1 rows; 1 / T of the launches. vima_decode_step is T = 1, the only form
+// that is graphed. A longer chunk runs eager also with option "graphs": it is a rare call (prefill, resume), and every distinct (T, row, keys
+// read) would be a graph of its own; the step graphs captured before stay valid (they read the episode state from the device and the plan from
+// their key) and are replayed again from the next step on.
+static int decode_unit(VimaHandle* h, const float* obs_tok, const uint8_t* obs_mask, const float* act_tok, int step, int T, int B, int Q,
+                       const float* prompt, int64_t stride_b, int64_t stride_l, const uint8_t* prompt_mask, int Lp, float* out, hipStream_t stream) {
+  DecodePlan P;
+  if (int e = decode_prepare(h, act_tok, T, B, Q, 0, Lp, 0, step, P)) return e;
+  auto launch = [&](hipStream_t st) {
+    return decode_launch(h, obs_tok, obs_mask, act_tok, T, B, Q, 0, prompt, stride_b, stride_l, prompt_mask, Lp, P, out, st);
+  };
+  int rc;
+  if (T > 1) {
+    rc = launch(stream);
+  } else {
+    // ring mode: the launch sequence depends on (write pointer, keys read, action slot), not on the step number -- from the second lap on the write
+    // pointers repeat, so the set of captured graphs stays bounded however long the rollout runs
+    const long long kstep = h->book.ring ? -1 - (((long long)P.u.row * (h->book.Lmax + 1) + P.u.Lk) * 2 + P.has_act) : step;
+    const std::string key = gkey("decode_step", {(long long)(uintptr_t)obs_tok, (long long)(uintptr_t)obs_mask, (long long)(uintptr_t)act_tok, kstep,
+                                                 B, Q, (long long)(uintptr_t)prompt, stride_b, stride_l, (long long)(uintptr_t)prompt_mask,
+                                                 Lp, (long long)(uintptr_t)out, (long long)(uintptr_t)h->kv_cache, (long long)(uintptr_t)h->ep_kv});
+    // ... and one eager step with an action slot warms all of them (same shapes, same workspace, same kernels: the attention launcher picks by Lk < 64 / >= 64):
+    // each (write pointer, keys read) is captured when first seen
+    const std::string warm = h->book.ring && P.has_act ? gkey("decode_step_ring", {B, Q, Lp, P.u.Lk >= 64 ? 1 : 0}) : std::string();
+    rc = run_graphed(h, key, stream, launch, warm);
+  }
+  if (!rc) decode_commit(h, P, B, Q, Lp, T);
+  return rc;
+}
+
 int vima_decode_step(VimaHandle* h, const float* obs_tok, const uint8_t* obs_mask, const float* act_tok, int step, int B, int Q,
                      const float* prompt, int64_t stride_b, int64_t stride_l, const uint8_t* prompt_mask, int Lp, float* out,
                      vima_stream_t stream) {
   if (step < 0) return fail("vima_decode_step: step must be >= 0");
-  DecodePlan P;
-  if (int e = decode_prepare(h, act_tok, 1, B, Q, 0, Lp, 0, step, P)) return e;
-  // ring mode: the launch sequence depends on (write pointer, keys read, action slot), not on the step number -- from the second lap on the write
-  // pointers repeat, so the set of captured graphs stays bounded however long the rollout runs
-  const long long kstep = h->book.ring ? -1 - (((long long)P.u.row * (h->book.Lmax + 1) + P.u.Lk) * 2 + P.has_act) : step;
-  const std::string key = gkey("decode_step", {(long long)(uintptr_t)obs_tok, (long long)(uintptr_t)obs_mask, (long long)(uintptr_t)act_tok, kstep,
-                                               B, Q, (long long)(uintptr_t)prompt, stride_b, stride_l, (long long)(uintptr_t)prompt_mask,
-                                               Lp, (long long)(uintptr_t)out, (long long)(uintptr_t)h->kv_cache, (long long)(uintptr_t)h->ep_kv});
-  // ... and one eager step with an action slot warms all of them (same shapes, same workspace, same kernels: the attention launcher picks by Lk < 64 / >= 64):
-  // each (write pointer, keys read) is captured when first seen
-  const std::string warm = h->book.ring && P.has_act ? gkey("decode_step_ring", {B, Q, Lp, P.u.Lk >= 64 ? 1 : 0}) : std::string();
-  const int rc = run_graphed(h, key, (hipStream_t)stream, [&](hipStream_t st) {
-    return decode_launch(h, obs_tok, obs_mask, act_tok, 1, B, Q, 0, prompt, stride_b, stride_l, prompt_mask, Lp, P, out, st);
-  }, warm);
-  if (!rc) decode_commit(h, P, B, Q, Lp);
-  return rc;
+  return decode_unit(h, obs_tok, obs_mask, act_tok, step, 1, B, Q, prompt, stride_b, stride_l, prompt_mask, Lp, out, (hipStream_t)stream);
 }
 
-// T env steps of the running episode batch as ONE pass of the incremental branch: Lq = T (Q + 1) rows per sample (one fewer at batch step 0) at
-// one row offset -- one unit of the ring -- instead of T passes of Q + 1 rows; 1 / T of the launches. T = 1 IS vima_decode_step (graph keys
-// included). A longer chunk runs eager also with option "graphs": it is a rare call (prefill, resume), and every distinct (T, row, keys read)
-// would be a graph of its own; the step graphs captured before stay valid (they read the episode state from the device and the plan from
-// their key) and are replayed again from the next vima_decode_step on.
 int vima_decode_chunk(VimaHandle* h, const float* obs_tok, const uint8_t* obs_mask, const float* act_tok, int step, int T, int B, int Q,
                       const float* prompt, int64_t stride_b, int64_t stride_l, const uint8_t* prompt_mask, int Lp, float* out,
                       vima_stream_t stream) {
-  if (T == 1) return vima_decode_step(h, obs_tok, obs_mask, act_tok, step, B, Q, prompt, stride_b, stride_l, prompt_mask, Lp, out, stream);
   if (step < 0 || T < 1) return fail("vima_decode_chunk: step must be >= 0 and T >= 1");
-  DecodePlan P;
-  if (int e = decode_prepare(h, act_tok, T, B, Q, 0, Lp, 0, step, P)) return e;
-  const int rc = decode_launch(h, obs_tok, obs_mask, act_tok, T, B, Q, 0, prompt, stride_b, stride_l, prompt_mask, Lp, P, out, (hipStream_t)stream);
-  if (!rc) decode_commit(h, P, B, Q, Lp, T);
-  return rc;
+  return decode_unit(h, obs_tok, obs_mask, act_tok, step, T, B, Q, prompt, stride_b, stride_l, prompt_mask, Lp, out, (hipStream_t)stream);
 }
 
 // Per-sample episode restart inside a running batch of incremental decoding (batched environments whose episodes end at different
@@ -2421,9 +2446,7 @@ int vima_decode_restart(VimaHandle* h, const uint8_t* restart, int B, const floa
     return fail("vima_decode_restart: no running episode batch with this B / Lp (start one with vima_decode_step(step = 0))");
   const int E = h->cfg.embed_dim, NL = h->cfg.xf_n_layers;
   Run R{h, (hipStream_t)stream};
-  h->restart_list.clear();
-  for (int b = 0; b < B; ++b)
-    if (restart[b]) h->restart_list.push_back(b);
+  h->restart_list = flagged_list(restart, B);
   const int n_r = (int)h->restart_list.size();
   const bool batched = h->restart_batched != 0 && Lp > 32 && n_r > 0;
   const int n_ws = batched ? n_r : 1;
@@ -2656,18 +2679,19 @@ int vima_seq_prefill(VimaHandle* h, const float* prompt, int64_t stride_b, int64
   return 0;
 }
 
-static int seq_step_launch(VimaHandle* h, const float* obs_tok, const float* act_tok, int B, int Q, int has_act, int row, int Lk, int win_end,
+// One unit of T env steps (plan P): embed its rows, the blocks against the episode cache, the last obs row of every slot (T = 1: the last new row)
+static int seq_step_launch(VimaHandle* h, const float* obs_tok, const float* act_tok, int T, int B, int Q, int has_act, const EpisodeBook::Plan& P,
                            float* out, hipStream_t stream) {
   if (int e = check_ready(h)) return e;
-  const int E = h->cfg.embed_dim, Lmax = h->ep_Lmax, Lq = Q + has_act;
+  const int E = h->cfg.embed_dim, Lmax = h->ep_Lmax, Lq = P.Lq;
   Run R{h, stream};
   float* x32 = R.ws<float>((size_t)B * Lq * E);
   void* xT = R.wsT((size_t)B * Lq * E);
   if (R.err) return R.err;
-  OTHER(R, launch_seq_embed_step(obs_tok, act_tok, h->pos_emb, Lmax, x32, xT, h->ep_mask, h->ep_poscnt, h->ep_fresh, row, B, Q, has_act, E,
-                                 h->bf16, R.st), "seq_embed_step");
-  if (hfgpt_step_stack(R, x32, xT, B, Lq, row, Lmax, Lk, win_end)) return R.err;
-  OTHER(R, launch_gather_pred(x32, out, 1, B, Lq, Lq, E, R.st), "gather_pred");   // the last new row of every sample
+  OTHER(R, launch_seq_embed_chunk(obs_tok, act_tok, h->pos_emb, Lmax, x32, xT, h->ep_mask, h->ep_poscnt, h->ep_fresh, P.row, T, B, Q, has_act, E, h->bf16,
+                                  R.st), "seq_embed_chunk");
+  if (hfgpt_step_stack(R, x32, xT, B, Lq, P.row, Lmax, P.Lk, P.win_end)) return R.err;
+  OTHER(R, launch_gather_pred(x32, out, T, B, Q, Lq, E, R.st, has_act), "gather_pred");
   return R.err;
 }
 
@@ -2687,22 +2711,38 @@ static int seq_prepare(VimaHandle* h, const char* fn, const float* obs_tok, cons
   return P.refused ? plan_refused(fn, "vima_seq_decode_restart", h->book, P, T) : 0;
 }
 
-int vima_seq_decode_step(VimaHandle* h, const float* obs_tok, const float* act_tok, int step, int B, float* out, vima_stream_t stream) {
+// T env steps of the running episode batch as ONE pass of hfgpt_step_stack: Lq = T (Q + 1) rows per sample (one fewer at batch step 0) at one row
+// offset -- one unit of the ring -- instead of T passes of Q + 1 rows; 1 / T of the launches. vima_seq_decode_step is T = 1, the only form that is
+// graphed. A longer chunk runs eager also with option "graphs" (a rare call: prefill, resume; every (T, row, keys read) would be a graph of its
+// own); the step graphs captured before stay valid -- they read the episode state from the device and their plan from the key.
+static int seq_unit(VimaHandle* h, const char* fn, const float* obs_tok, const float* act_tok, int step, int T, int B, float* out, hipStream_t stream) {
   EpisodeBook::Plan P;
-  if (int e = seq_prepare(h, "vima_seq_decode_step", obs_tok, act_tok, step, 1, B, out, P)) return e;
+  if (int e = seq_prepare(h, fn, obs_tok, act_tok, step, T, B, out, P)) return e;
   const int has_act = step > 0 ? 1 : 0, Q = h->ep_Q;
-  // ring mode: the launch sequence depends on (write pointer, keys read, action slot), not on the step number -- from the second lap on every step
-  // has Q + 1 rows and the write pointers repeat, so the set of captured graphs stays bounded however long the rollout runs ...
-  const std::string key = gkey("seq_step", {(long long)(uintptr_t)obs_tok, (long long)(uintptr_t)act_tok, (long long)(uintptr_t)out, B, P.row, has_act,
-                                            (long long)(uintptr_t)h->ep_kv, P.Lk, P.win_end});
-  // ... and one eager step with an action slot warms all of them (same shapes, same workspace, same kernels: the attention launcher picks by Lk < 64 / >= 64):
-  // each (write pointer, keys read) is captured when first seen
-  const std::string warm = h->book.ring && has_act ? gkey("seq_step_ring", {B, P.Lk >= 64 ? 1 : 0}) : std::string();
-  const int rc = run_graphed(h, key, (hipStream_t)stream, [&](hipStream_t st) {
-    return seq_step_launch(h, obs_tok, has_act ? act_tok : nullptr, B, Q, has_act, P.row, P.Lk, P.win_end, out, st);
-  }, warm);
-  if (!rc) h->book.commit(P, 1);
+  auto launch = [&](hipStream_t st) { return seq_step_launch(h, obs_tok, has_act || T > 1 ? act_tok : nullptr, T, B, Q, has_act, P, out, st); };
+  int rc;
+  if (T > 1) {
+    rc = launch(stream);
+  } else {
+    // ring mode: the launch sequence depends on (write pointer, keys read, action slot), not on the step number -- from the second lap on every step
+    // has Q + 1 rows and the write pointers repeat, so the set of captured graphs stays bounded however long the rollout runs ...
+    const std::string key = gkey("seq_step", {(long long)(uintptr_t)obs_tok, (long long)(uintptr_t)act_tok, (long long)(uintptr_t)out, B, P.row, has_act,
+                                              (long long)(uintptr_t)h->ep_kv, P.Lk, P.win_end});
+    // ... and one eager step with an action slot warms all of them (same shapes, same workspace, same kernels: the attention launcher picks by Lk < 64 / >= 64):
+    // each (write pointer, keys read) is captured when first seen
+    const std::string warm = h->book.ring && has_act ? gkey("seq_step_ring", {B, P.Lk >= 64 ? 1 : 0}) : std::string();
+    rc = run_graphed(h, key, stream, launch, warm);
+  }
+  if (!rc) h->book.commit(P, T);
   return rc;
+}
+
+int vima_seq_decode_step(VimaHandle* h, const float* obs_tok, const float* act_tok, int step, int B, float* out, vima_stream_t stream) {
+  return seq_unit(h, "vima_seq_decode_step", obs_tok, act_tok, step, 1, B, out, (hipStream_t)stream);
+}
+
+int vima_seq_decode_chunk(VimaHandle* h, const float* obs_tok, const float* act_tok, int step, int T, int B, float* out, vima_stream_t stream) {
+  return seq_unit(h, T == 1 ? "vima_seq_decode_step" : "vima_seq_decode_chunk", obs_tok, act_tok, step, T, B, out, (hipStream_t)stream);
 }
 
 // All flagged samples are rebuilt TOGETHER: one compact prefill of n_flagged x (Lp + 1) rows through the stack, whose k | v copy per layer
@@ -2714,9 +2754,7 @@ int vima_seq_decode_restart(VimaHandle* h, const uint8_t* restart, int B, const 
   if (!(h->seq_live && h->ep_B == B && h->ep_Lp == Lp))
     return fail("vima_seq_decode_restart: no running episode batch with this B / Lp (start one with vima_seq_prefill)");
   const int E = h->cfg.embed_dim, Lmax = h->ep_Lmax, L = Lp + 1;
-  h->restart_list.clear();
-  for (int b = 0; b < B; ++b)
-    if (restart[b]) h->restart_list.push_back(b);
+  h->restart_list = flagged_list(restart, B);
   const int n_r = (int)h->restart_list.size();
   if (n_r == 0) return 0;
   Run R{h, (hipStream_t)stream};
@@ -2733,28 +2771,6 @@ int vima_seq_decode_restart(VimaHandle* h, const uint8_t* restart, int B, const 
   hfgpt_stack(R, x32, xT, mask, n_r, L, h->ep_kv, list, B, Lmax);
   if (!R.err) h->book.restart(h->restart_list);
   return R.err;
-}
-
-// T env steps of the running episode batch as ONE pass of hfgpt_step_stack: Lq = T (Q + 1) rows per sample (one fewer at batch step 0) at one row
-// offset -- one unit of the ring -- instead of T passes of Q + 1 rows; 1 / T of the launches. T = 1 IS vima_seq_decode_step (graph keys included).
-// A longer chunk runs eager also with option "graphs" (a rare call: prefill, resume; every (T, row, keys read) would be a graph of its own); the
-// step graphs captured before stay valid -- they read the episode state from the device and their plan from the key.
-int vima_seq_decode_chunk(VimaHandle* h, const float* obs_tok, const float* act_tok, int step, int T, int B, float* out, vima_stream_t stream) {
-  if (T == 1) return vima_seq_decode_step(h, obs_tok, act_tok, step, B, out, stream);
-  EpisodeBook::Plan P;
-  if (int e = seq_prepare(h, "vima_seq_decode_chunk", obs_tok, act_tok, step, T, B, out, P)) return e;
-  const int has_act = step > 0 ? 1 : 0, Q = h->ep_Q, Lmax = h->ep_Lmax, E = h->cfg.embed_dim, Lq = P.Lq;
-  Run R{h, (hipStream_t)stream};
-  float* x32 = R.ws<float>((size_t)B * Lq * E);
-  void* xT = R.wsT((size_t)B * Lq * E);
-  if (R.err) return R.err;
-  OTHER(R, launch_seq_embed_chunk(obs_tok, act_tok, h->pos_emb, Lmax, x32, xT, h->ep_mask, h->ep_poscnt, h->ep_fresh, P.row, T, B, Q, has_act, E, h->bf16,
-                                  R.st), "seq_embed_chunk");
-  if (hfgpt_step_stack(R, x32, xT, B, Lq, P.row, Lmax, P.Lk, P.win_end)) return R.err;
-  OTHER(R, launch_gather_pred(x32, out, T, B, Q, Lq, E, R.st, has_act), "gather_pred");   // the last obs row of every slot
-  if (R.err) return R.err;
-  h->book.commit(P, T);
-  return 0;
 }
 
 int vima_seq_history_room(VimaHandle* h, int32_t* steps_host) {
@@ -2790,9 +2806,7 @@ int vima_seq_decode_restart_history(VimaHandle* h, const uint8_t* restart, int B
     return fail("vima_seq_decode_restart_history: sequence of " + std::to_string(L64) + " tokens (prompt, separator and " + std::to_string(T) +
                 " steps) exceeds n_positions " + std::to_string(h->cfg.n_positions), 34);
   const int L = (int)L64;
-  std::vector<int> flagged;
-  for (int b = 0; b < B; ++b)
-    if (restart[b]) flagged.push_back(b);
+  const std::vector<int> flagged = flagged_list(restart, B);
   const int n_r = (int)flagged.size();
   if (n_r == 0) return 0;
   // compact row l of the sequence -> cache row: the identity over the prefix; history step s sits in the slot of batch step t - T + s, its Q obs rows
@@ -3305,12 +3319,13 @@ int vima_op_dec_embed_step(VimaHandle* h, const float* obs_tok, const uint8_t* o
   if (int e = op_begin(h, fn)) return e;
   OP_REQ(obs_tok && obs_mask && pos_table && x32 && hist_mask && poscnt && (act_tok || !has_act), "null argument");
   OP_REQ(B > 0 && Q > 0 && E > 0 && n_pos > 0 && L_hist >= 0 && (has_act == 0 || has_act == 1), "B, Q, E, n_pos must be positive, L_hist >= 0, has_act 0 or 1");
+  OP_REQ(Q + has_act <= 64 && E % 4 == 0 && (long long)L_hist + Q + has_act <= Lmax, "dec_embed_step takes Q + has_act <= 64 rows inside Lmax, E % 4 == 0");
   Run R{h, (hipStream_t)stream};
   const long long n = (long long)B * (Q + has_act) * E;
   void* oT = xT ? R.wsT((size_t)n) : nullptr;
   if (R.err) return R.err;
-  OTHER(R, launch_dec_embed_step(obs_tok, obs_mask, act_tok, pos_table, n_pos, x32, oT, hist_mask, poscnt, L_hist, Lmax, B, Q, has_act, E, h->bf16, R.st, fresh),
-        "vima_op_dec_embed_step: dec_embed_step");
+  OTHER(R, launch_dec_embed_chunk(obs_tok, obs_mask, act_tok, pos_table, n_pos, x32, oT, hist_mask, poscnt, L_hist, Lmax, 1, B, Q, has_act, E, h->bf16, R.st, fresh),
+        "vima_op_dec_embed_step: dec_embed_chunk");
   return oT ? op_widen(R, oT, xT, n) : R.err;
 }
 
@@ -3472,12 +3487,14 @@ int vima_op_seq_embed_step(VimaHandle* h, const float* obs_tok, const float* act
   if (int e = op_begin(h, fn)) return e;
   OP_REQ(obs_tok && pos_table && x32 && cache_mask && posbase && fresh, "null argument");
   OP_REQ(B > 0 && E > 0 && n_pos > 0 && (has_act == 0 || has_act == 1), "B, E and n_pos must be positive, has_act 0 or 1");
+  OP_REQ(Q > 0 && Q + has_act <= 64 && E % 4 == 0 && row0 >= 0 && (long long)row0 + Q + has_act <= n_pos && (act_tok || !has_act),
+         "seq_embed_step takes 1 <= Q, Q + has_act <= 64 rows inside n_pos, E % 4 == 0, act_tok with has_act");
   Run R{h, (hipStream_t)stream};
   const long long n = (long long)B * (Q + has_act) * E;
-  void* oT = R.wsT((size_t)(n > 0 ? n : 1));
+  void* oT = R.wsT((size_t)n);
   if (R.err) return R.err;
-  OTHER(R, launch_seq_embed_step(obs_tok, act_tok, pos_table, n_pos, x32, oT, cache_mask, posbase, fresh, row0, B, Q, has_act, E, h->bf16, R.st),
-        "vima_op_seq_embed_step: seq_embed_step");
+  OTHER(R, launch_seq_embed_chunk(obs_tok, act_tok, pos_table, n_pos, x32, oT, cache_mask, posbase, fresh, row0, 1, B, Q, has_act, E, h->bf16, R.st),
+        "vima_op_seq_embed_step: seq_embed_chunk");
   return xT ? op_widen(R, oT, xT, n) : R.err;
 }
 
