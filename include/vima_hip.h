@@ -424,6 +424,28 @@ int vima_seq_decode_restart_history(VimaHandle* h, const uint8_t* restart, int B
                                     vima_stream_t stream);
 int vima_seq_history_room(VimaHandle* h, int32_t* steps_host);
 
+/* ---- branch rollouts: fork a sample's episode into other batch slots (additive, ABI version unchanged) ------------
+ * source: HOST int32 [B]; slot b continues the episode of slot source[b], source[b] == b leaves b untouched. Nothing is recomputed: the
+ * destination's state is a copy of the source's -- in every layer the rows of the episode K | V cache the source's episode has written and that
+ * are still there (EpisodeBook::live_ranges: the last age[source] advanced rows behind the write pointer, at most two ranges in a ring; the
+ * batch shares one row index space, so they already sit at the row numbers the destination needs), its key-mask row (whole), its position
+ * counter and its "fresh" flag; vima_decode_fork also copies the sample's block of every layer's prompt K / V cache (contiguous in either
+ * layout), vima_seq_decode_fork the fixed prefix rows [0, Lp] (prompt | separator) instead. On the host the destination takes its source's ring
+ * age, so its vima_decode_steps_left entry is its source's; write pointer, high-water mark and slot record are batch-wide and stay. The
+ * destination's old episode is dropped, as by a restart. Its next step consumes or ignores its act_tok row exactly as the source's would; fed
+ * the source's inputs it returns the source's bits, fed others it is a branch. vima_decode_fork: the caller passes the SOURCE's prompt mask row
+ * for the destination from the next vima_decode_step on (VIMAPolicy.fork_samples updates the tensors).
+ * Every source must be its own source (source[source[b]] == source[b]: no chains, no swaps), so that the copy runs in place and no slot is both
+ * read and written; any beam reorder can be written that way, survivors keep their slots. Refusals, before anything changes: no running episode
+ * batch of this B (vima_decode_step(step = 0) / vima_seq_prefill); the other policy family's handle (the message names the other entry); a
+ * source map that breaks the rule: code 22, naming the first offending sample. The identity map launches nothing.
+ * Cost, whatever the number of pairs and layers: ONE upload of a job table (host copy kept in the handle) and at most 3 launches -- episode K | V
+ * (episode_fork_kernel: all layers, groups and ranges; a source's chunk is loaded once and stored to each of its destinations, 16-byte accesses),
+ * prompt K / V (the same kernel; vima_decode_fork only) and the per-sample state. Stream-ordered and asynchronous; no allocation beyond the
+ * handle's workspace. Captured step graphs stay valid (no pointer and no plan changes). */
+int vima_decode_fork(VimaHandle* h, const int32_t* source /* HOST [B] */, int B, vima_stream_t stream);
+int vima_seq_decode_fork(VimaHandle* h, const int32_t* source /* HOST [B] */, int B, vima_stream_t stream);
+
 /* ---- image preprocessing in front of the policy ------------------------------------------- */
 /* The per-object work of prepare_obs / prepare_prompt (/root/reference/scripts/example.py:374-473 and :243-371; numpy +
  * cv2 per object on the host there): for every frame and every object id, segmentation mask -> pixel bbox ->
@@ -596,6 +618,14 @@ int vima_op_seq_embed_chunk(VimaHandle* h, const float* obs_tok, const float* ac
                             int has_act, int E, float* x32, float* xT, uint8_t* cache_mask, int32_t* posbase, uint8_t* fresh, vima_stream_t stream);
 int vima_op_seq_history_install(VimaHandle* h, const uint8_t* mask, const int32_t* list, const int32_t* rowmap, int n, int L, int lo, int hi, int n_pos,
                                 uint8_t* cache_mask, int32_t* posbase, uint8_t* fresh, vima_stream_t stream);
+/* launch_episode_fork (episode_fork_kernel) alone, IN PLACE on the caller's DEVICE buffer `cache` [NL][B][L][N] of elem_bytes-wide elements (4: fp32,
+ * 2: bf16; the handle's precision plays no part; N * elem_bytes a multiple of 16 and the buffer 16-byte aligned, else code 22). HOST arrays in CSR
+ * form: group g copies from sample group_src[g] to the samples dsts[group_ptr[g] .. group_ptr[g + 1]) the row ranges [ranges[2 i], ranges[2 i + 1])
+ * for i in [range_ptr[g], range_ptr[g + 1]), in every layer; group_ptr and range_ptr hold n_groups + 1 entries starting at 0. Sources and
+ * destinations must be disjoint sets of distinct samples and every range must lie in [0, L] (refused otherwise); empty ranges and groups without
+ * destinations copy nothing. Rows and samples outside the listed (destination, range) set come back unchanged. */
+int vima_op_episode_fork(VimaHandle* h, void* cache, int elem_bytes, int NL, int B, int L, int N, const int32_t* group_src, const int32_t* group_ptr,
+                         const int32_t* dsts, const int32_t* range_ptr, const int32_t* ranges, int n_groups, vima_stream_t stream);
 /* precision FP8: the calibrated activation scales (dequantisation scale = headroom x max |x| / 448, see VIMA_PRECISION_FP8) of group 0 the T5 stack [12 layers][4 sites:
  * stream before qkv, attention context, stream before wi, ReLU hidden], 1 the ViT [4 blocks][4 sites: ln_1 output, attention output,
  * ln_2 output, QuickGELU hidden], 2 the decoder's prompt K/V projection [1]; returns their number (0 before that group's calibrating

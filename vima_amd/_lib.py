@@ -107,6 +107,11 @@ PROTOTYPES = {
     "vima_seq_decode_chunk": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),
     "vima_seq_decode_restart_history": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, c_i64, c_i64, vp, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp]),
     "vima_seq_history_room": (ctypes.c_int, [vp, ctypes.POINTER(c_i32)]),
+    "vima_decode_fork": (ctypes.c_int, [vp, ctypes.POINTER(c_i32), ctypes.c_int, vp]),
+    "vima_seq_decode_fork": (ctypes.c_int, [vp, ctypes.POINTER(c_i32), ctypes.c_int, vp]),
+    "vima_op_episode_fork": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_i32),
+                                            ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), ctypes.c_int,
+                                            vp]),
     "vima_action_head": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, vp]),
     "vima_action_embed": (ctypes.c_int, [vp, vp * 4, ctypes.c_int, vp, vp]),
     "vima_action_select": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.POINTER(c_f32), vp * 4, vp, vp, vp, vp]),

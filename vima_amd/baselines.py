@@ -182,6 +182,13 @@ class _BaselinePolicy(VIMAPolicy):
             history = (history[0], torch.ones(history[0].shape[:3], dtype=torch.bool, device=self._device), history[1])
         return VIMAPolicy.restart_samples(self, restart, prompt_token, prompt_token_mask, history)
 
+    def fork_samples(self, source, prompt_token, prompt_token_mask):
+        """VIMAPolicy.fork_samples. VIMAFlamingoPolicy only; the decoder-only policies fork with `seq_fork` (their prompt is the cache prefix)."""
+        if self.KIND != "flamingo":
+            raise NotImplementedError("fork_samples needs the XAttnGPT episode caches (VIMAPolicy / VIMAFlamingoPolicy); the decoder-only "
+                                      "policies fork with seq_fork")
+        return VIMAPolicy.fork_samples(self, source, prompt_token, prompt_token_mask)
+
     def history_room(self) -> int:
         if self.KIND != "flamingo":
             raise NotImplementedError("history_room: VIMAPolicy / VIMAFlamingoPolicy only (the decoder-only policies have seq_history_room)")
@@ -330,6 +337,22 @@ class _BaselinePolicy(VIMAPolicy):
             self._handle, ctypes.c_void_p(flags.data_ptr()), B, _ptr(prompt_token), prompt_token.stride(1), prompt_token.stride(0),
             _ptr(prompt_token_mask), Lp, _ptr(obs_token), _ptr(action_token), T, _ptr(out), self._stream()))
         return out
+
+    def seq_fork(self, source):
+        """Branch rollouts inside the stepping batch: slot b continues the episode of slot `source[b]` (length-B ints; `source[b] == b`:
+        untouched). Nothing is recomputed (vima_seq_decode_fork): the source's prefix rows [prompt | sep] and the live rows of its history
+        in every layer's K/V cache, its key mask, position counter and restart flag are copied into the destination's slot, whose old
+        episode is dropped. There are no prompt tensors to update: the prompt is the cache prefix. Every source must be its own source
+        (`source[source[b]] == source[b]`: no chains, no swaps); ValueError otherwise, and nothing changes. The destination's next
+        `seq_step` consumes or ignores its row of `prev_action_token` exactly as the source's would; fed the source's inputs it returns
+        the source's output bit for bit, fed others it is a branch. `steps_left()` of a destination is its source's; a later
+        `seq_restart` (with or without `history=`) of a forked slot works as on any other."""
+        self._seq_only("seq_fork (VIMAFlamingoPolicy forks with fork_samples)")
+        B = getattr(self, "_ep_B", 0)
+        if getattr(self, "_seq_t", None) is None or B <= 0:
+            raise _lib.VimaError("seq_fork: no running episode (call seq_prefill first)")
+        src, src_p = self._fork_source(source, B)
+        _lib.check(self._lib.vima_seq_decode_fork(self._handle, src_p, B, self._stream()))
 
     def seq_history_room(self) -> int:
         """The largest T `seq_restart(..., history=)` accepts now: the most recent batch steps whose cache rows are all still there (without

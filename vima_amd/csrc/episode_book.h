@@ -1,5 +1,5 @@
 // Host bookkeeping of an episode cache: which cache rows the next env steps of a batch write, and which may be overwritten. Plain C++17, no HIP:
-// tests/episode_book_driver.cpp holds it on the CPU against the Python restatements.
+// tests/episode_book_driver.cpp and tests/episode_fork_driver.cpp (forks) hold it on the CPU against the Python restatements.
 //
 // Rows [0, P0) of every sample's cache block are a fixed prefix (P0 = 0 for the XAttnGPT policies, prompt + separator for GPT / Gato); the rows
 // [P0, Lmax) behind it are ONE row index space for the whole batch, linear or a ring (options decode_ring / seq_ring). A call of T env steps is one
@@ -91,6 +91,34 @@ struct EpisodeBook {
   }
 
   int written_end() const { return ring ? hw : wp; }   // one past the last row that may hold a live key
+
+  // Fork: slot b continues the episode of slot source[b] (source[b] == b: untouched). Legal iff every entry is a sample and every source is its own
+  // source -- no chains, no swaps -- so that the copy runs in place without ordering hazards: no slot is both read and written
+  bool fork_ok(const std::vector<int>& source) const {
+    if ((int)source.size() != B) return false;
+    for (int s : source)
+      if (s < 0 || s >= B || source[(size_t)s] != s) return false;
+    return true;
+  }
+
+  // the destination takes its source's age (its old episode is dropped, as in restart); everything else is batch-wide
+  void fork(const std::vector<int>& source) {
+    for (int b = 0; b < B; ++b) age[(size_t)b] = age[(size_t)source[(size_t)b]];
+  }
+
+  // At most two disjoint half-open row ranges inside [P0, written_end()) that hold every row sample b's episode has written and that is still
+  // there: the last age[b] advanced rows behind wp. Ring: where they reach back beyond P0, [P0, wp) and the rest counted back from Lmax, cut at hw
+  // (rows of a skipped tail beyond hw were never written). -> the number of ranges; their lengths sum to at most age[b]
+  int live_ranges(int b, int out[2][2]) const {
+    const int a = age[(size_t)b];
+    int n = 0;
+    auto put = [&](int lo, int hi) { if (lo < hi) { out[n][0] = lo; out[n][1] = hi; ++n; } };
+    if (a <= 0) return 0;
+    if (!ring || wp - a >= P0) { put(std::max(P0, wp - a), wp); return n; }
+    put(P0, wp);
+    put(std::max(wp, Lmax - (a - (wp - P0))), hw);
+    return n;
+  }
 
  private:
   int place(int w, int Lq, int& row) const {   // -> rows advanced

@@ -299,6 +299,27 @@ int launch_seq_kv_store(const void* in, long long ld_in, void* out, const int* l
                         hipStream_t st);
 int launch_fill_u8(uint8_t* p, long long n, uint8_t v, hipStream_t st);
 
+// ---- episode fork (episode_fork.hip): a sample's episode state copied into other batch slots, in place
+// One job = one row range [row0, row0 + nrows) of sample `src`, copied to the ndst samples dsts[dst0 ..) in EVERY layer of a cache [NL][B][L][N]:
+// the range is one contiguous span per layer, cut into chunks of kForkChunk 16-byte vectors; unit0 = the chunks of the jobs in front of it
+// (per layer), so that a flat unit number finds its job by bisection.
+struct ForkJob { int src, dst0, ndst, row0, nrows, unit0; };
+constexpr int kForkChunk = 1024;   // 16-byte vectors per work unit: 256 threads x 4
+constexpr int kForkMaxDst = 8;     // a source with more destinations is split into jobs of at most this many (more units, the source read once per job)
+struct EpisodeForkArgs {
+  void* cache = nullptr;            // [NL][B][L][N], operand type
+  const ForkJob* jobs = nullptr;    // DEVICE [n_jobs], nrows > 0, unit0 ascending
+  const int* dsts = nullptr;        // DEVICE
+  int n_jobs = 0, units = 0;        // units: chunks of all jobs in one layer
+  int NL = 0, B = 0, L = 0, N = 0;
+};
+// A workgroup loads a chunk of the source span once (dwordx4) and stores it to every destination of the job. Sources and destinations must be disjoint
+// sets (EpisodeBook::fork_ok). hipErrorInvalidValue (1) for a bad shape, 22 when N * sizeof(element) is no multiple of 16. The grid is
+// min(NL * units, 2048) workgroups, whatever B
+int launch_episode_fork(const EpisodeForkArgs& a, bool is_bf16, hipStream_t st);
+// per-sample episode state of n (destination, source) pairs (DEVICE arrays): the whole key-mask row [Lmax], the position counter and the fresh flag
+int launch_episode_fork_state(const int* dsts, const int* srcs, int n, uint8_t* mask, int* poscnt, uint8_t* fresh, int Lmax, hipStream_t st);
+
 // ---------------------------------------------------------------- attention
 // ViT: 5-token (S <= 8) multi-head attention on packed qkv T [M*S, 3*W] -> T [M*S, W]; head dim 32
 // out8 (bf16 mode): write the result as fp8 e4m3(value * inv8) [M*S, W] bytes INSTEAD of the operand-type output

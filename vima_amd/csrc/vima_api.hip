@@ -240,6 +240,7 @@ struct VimaHandle {
   int restart_batched = 1;                       // option "restart_batched": vima_decode_restart rebuilds the flagged samples' prompt K / V together (0: one sample at a time)
   std::vector<int> restart_list;                 // host copy of the flagged sample indices (source of the upload)
   std::vector<int> hist_rowmap;                  // host copy of the history's compact row -> cache row map (source of the upload)
+  std::vector<int> fork_table;                   // host copy of a fork's job table (vima_decode_fork / vima_seq_decode_fork; source of the upload)
   // hipGraph replay of the per-env-step entry points (option "graphs"): at small batch a step is ~1300 launches of
   // microsecond kernels and the HOST launch rate is the bound. The launch sequence of a call is captured the second time
   // the same (entry point, shapes, pointers, options, workspace generation) is seen and replayed afterwards.
@@ -3533,6 +3534,143 @@ int vima_op_seq_restart(VimaHandle* h, const int32_t* list, int n, int lo, int h
   Run R{h, (hipStream_t)stream};
   OTHER(R, launch_seq_restart(list, n, cache_mask, fresh, lo, hi, n_pos, R.st), "vima_op_seq_restart: seq_restart");
   return R.err;
+}
+
+// ---- episode fork (episode_fork.hip) ---------------------------------------------------------------------------------------------
+// The host side of one fork call, kept in the handle (fork_table: the source of the ONE upload): [jobs of cache 0 | jobs of cache 1 | dsts | srcs],
+// the (destination, source) pairs grouped by source, the jobs of a group split over at most kForkMaxDst destinations each.
+namespace {
+struct ForkGroup { int src, dst0, ndst; };   // destinations dsts[dst0 .. dst0 + ndst)
+struct ForkTable {
+  std::vector<ForkJob> jobs[2];
+  int units[2] = {0, 0};
+  // one range [row0, row1) of group g into cache c, whose rows hold rv 16-byte vectors
+  void add(int c, const ForkGroup& g, int row0, int row1, long long rv) {
+    if (row1 <= row0 || g.ndst <= 0) return;
+    const int chunks = (int)(((long long)(row1 - row0) * rv + kForkChunk - 1) / kForkChunk);
+    for (int d = 0; d < g.ndst; d += kForkMaxDst) {
+      jobs[c].push_back(ForkJob{g.src, g.dst0 + d, std::min(kForkMaxDst, g.ndst - d), row0, row1 - row0, units[c]});
+      units[c] += chunks;
+    }
+  }
+};
+}  // namespace
+
+// uploads the table and launches: per cache with jobs one episode_fork launch, then (mask given) the per-sample state -- at most 3 launches
+static int fork_launch(Run& R, const ForkTable& T, const std::vector<int>& dsts, const std::vector<int>& srcs, void* const cache[2], const int L[2],
+                       int NL, int B, int N, bool is_bf16, uint8_t* mask, int* poscnt, uint8_t* fresh, int Lmax) {
+  VimaHandle* h = R.h;
+  const size_t nj0 = T.jobs[0].size(), nj1 = T.jobs[1].size(), np = dsts.size(), ji = sizeof(ForkJob) / sizeof(int);
+  std::vector<int>& tab = h->fork_table;
+  tab.resize((nj0 + nj1) * ji + 2 * np);
+  if (nj0) memcpy(tab.data(), T.jobs[0].data(), nj0 * sizeof(ForkJob));
+  if (nj1) memcpy(tab.data() + nj0 * ji, T.jobs[1].data(), nj1 * sizeof(ForkJob));
+  std::copy(dsts.begin(), dsts.end(), tab.begin() + (nj0 + nj1) * ji);
+  std::copy(srcs.begin(), srcs.end(), tab.begin() + (nj0 + nj1) * ji + np);
+  int* dev = R.ws<int>(tab.size());
+  if (R.err) return R.err;
+  HIPCK(hipMemcpyAsync(dev, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, R.st));
+  const int* ddst = dev + (nj0 + nj1) * ji;
+  for (int c = 0; c < 2; ++c) {
+    if (T.jobs[c].empty()) continue;
+    EpisodeForkArgs a;
+    a.cache = cache[c]; a.jobs = reinterpret_cast<const ForkJob*>(dev + (c ? nj0 * ji : 0)); a.dsts = ddst;
+    a.n_jobs = (int)T.jobs[c].size(); a.units = T.units[c]; a.NL = NL; a.B = B; a.L = L[c]; a.N = N;
+    OTHER(R, launch_episode_fork(a, is_bf16, R.st), "episode_fork");
+  }
+  if (mask) OTHER(R, launch_episode_fork_state(ddst, ddst + np, (int)np, mask, poscnt, fresh, Lmax, R.st), "episode_fork_state");
+  return R.err;
+}
+
+// vima_decode_fork / vima_seq_decode_fork behind their policy checks
+static int fork_episode(VimaHandle* h, const char* fn, bool seq, const int32_t* source, int B, hipStream_t st) {
+  if (!source) return fail(std::string(fn) + ": null argument");
+  if (seq ? !(h->seq_live && h->ep_B == B) : !(h->ep_step >= 0 && h->ep_B == B && h->kv_valid && h->kv_B == B))
+    return fail(std::string(fn) + ": no running episode batch with this B (start one with " + (seq ? "vima_seq_prefill)" : "vima_decode_step(step = 0))"));
+  const std::vector<int> src(source, source + B);
+  if (!h->book.fork_ok(src)) {
+    for (int b = 0; b < B; ++b) {
+      const int s = src[(size_t)b];
+      if (s < 0 || s >= B) return fail(std::string(fn) + ": source[" + std::to_string(b) + "] = " + std::to_string(s) + " is not a sample of the batch [0, " + std::to_string(B) + ")", 22);
+      if (src[(size_t)s] != s)
+        return fail(std::string(fn) + ": source[" + std::to_string(b) + "] = " + std::to_string(s) + " is itself a destination (source[" + std::to_string(s) + "] = " +
+                    std::to_string(src[(size_t)s]) + "): a source must be its own source, no chains and no swaps", 22);
+    }
+  }
+  const int E = h->cfg.embed_dim, NL = h->cfg.xf_n_layers, Lmax = h->ep_Lmax, Lp = h->ep_Lp;
+  if (((size_t)2 * E * h->esz()) % 16) return fail(std::string(fn) + ": rows of 2 x embed_dim elements must be a multiple of 16 bytes", 22);
+  const long long rv = (long long)2 * E * (long long)h->esz() / 16;
+  std::vector<int> dsts, srcs;
+  ForkTable T;
+  for (int s = 0; s < B; ++s) {   // groups in increasing source order
+    ForkGroup g{s, (int)dsts.size(), 0};
+    for (int b = 0; b < B; ++b)
+      if (src[(size_t)b] == s && b != s) { dsts.push_back(b); srcs.push_back(s); ++g.ndst; }
+    if (!g.ndst) continue;
+    int rg[2][2];
+    const int nr = h->book.live_ranges(s, rg);
+    if (seq) T.add(0, g, 0, h->book.P0, rv);          // the fixed prefix [prompt | sep]
+    for (int i = 0; i < nr; ++i) T.add(0, g, rg[i][0], rg[i][1], rv);
+    if (!seq) T.add(1, g, 0, Lp, rv);                 // the sample's block of the prompt K / V cache, either layout
+  }
+  if (dsts.empty()) return 0;
+  Run R{h, st};
+  void* const cache[2] = {h->ep_kv, h->kv_cache};
+  const int L[2] = {Lmax, Lp};
+  if (fork_launch(R, T, dsts, srcs, cache, L, NL, B, 2 * E, h->bf16, h->ep_mask, h->ep_poscnt, h->ep_fresh, Lmax)) return R.err;
+  h->book.fork(src);
+  return 0;
+}
+
+int vima_decode_fork(VimaHandle* h, const int32_t* source, int B, vima_stream_t stream) {
+  if (int e = check_ready(h)) return e;
+  if (h->cfg.policy_kind != VIMA_POLICY_VIMA && h->cfg.policy_kind != VIMA_POLICY_FLAMINGO)
+    return fail("vima_decode_fork: the handle's policy has no XAttnGPT episode caches (GPT / GATO handles fork with vima_seq_decode_fork)");
+  return fork_episode(h, "vima_decode_fork", false, source, B, (hipStream_t)stream);
+}
+
+int vima_seq_decode_fork(VimaHandle* h, const int32_t* source, int B, vima_stream_t stream) {
+  if (int e = check_ready(h)) return e;
+  if (h->cfg.policy_kind != VIMA_POLICY_GPT && h->cfg.policy_kind != VIMA_POLICY_GATO)
+    return fail("vima_seq_decode_fork: decoder-only policies (GPT / GATO) only; VIMAPolicy / VIMAFlamingoPolicy handles fork with vima_decode_fork");
+  return fork_episode(h, "vima_seq_decode_fork", true, source, B, (hipStream_t)stream);
+}
+
+int vima_op_episode_fork(VimaHandle* h, void* cache, int elem_bytes, int NL, int B, int L, int N, const int32_t* group_src, const int32_t* group_ptr,
+                         const int32_t* dsts, const int32_t* range_ptr, const int32_t* ranges, int n_groups, vima_stream_t stream) {
+  const char* fn = "vima_op_episode_fork";
+  if (int e = op_begin(h, fn)) return e;
+  OP_REQ(cache && group_src && group_ptr && dsts && range_ptr && ranges, "null argument");
+  OP_REQ(elem_bytes == 2 || elem_bytes == 4, "elem_bytes must be 4 (fp32) or 2 (bf16)");
+  OP_REQ(NL > 0 && B > 0 && L > 0 && N > 0 && n_groups >= 0, "NL, B, L and N must be positive");
+  if (((long long)N * elem_bytes) % 16 || ((uintptr_t)cache & 15))
+    return fail(std::string(fn) + ": rows of N elements must be a multiple of 16 bytes and the cache 16-byte aligned", 22);
+  const long long rv = (long long)N * elem_bytes / 16;
+  std::vector<int> role((size_t)B, 0), d, s;   // 1 = source, 2 = destination
+  ForkTable T;
+  OP_REQ(group_ptr[0] == 0 && range_ptr[0] == 0, "group_ptr and range_ptr start at 0");
+  for (int g = 0; g < n_groups; ++g) {
+    const int sb = group_src[g];
+    OP_REQ(sb >= 0 && sb < B, "a source is not a sample of the cache");
+    OP_REQ(role[(size_t)sb] == 0, "a source is listed twice or is a destination");
+    OP_REQ(group_ptr[g + 1] >= group_ptr[g] && range_ptr[g + 1] >= range_ptr[g], "group_ptr and range_ptr must not decrease");
+    role[(size_t)sb] = 1;
+    ForkGroup G{sb, (int)d.size(), group_ptr[g + 1] - group_ptr[g]};
+    for (int i = group_ptr[g]; i < group_ptr[g + 1]; ++i) {
+      OP_REQ(dsts[i] >= 0 && dsts[i] < B && role[(size_t)dsts[i]] == 0, "a destination is not a sample of the cache, is listed twice or is a source");
+      role[(size_t)dsts[i]] = 2;
+      d.push_back(dsts[i]); s.push_back(sb);
+    }
+    for (int i = range_ptr[g]; i < range_ptr[g + 1]; ++i) {
+      OP_REQ(ranges[2 * i] >= 0 && ranges[2 * i] <= ranges[2 * i + 1] && ranges[2 * i + 1] <= L, "a range must be 0 <= row0 <= row1 <= L");
+      T.add(0, G, ranges[2 * i], ranges[2 * i + 1], rv);
+    }
+  }
+  if (T.jobs[0].empty()) return 0;
+  Run R{h, (hipStream_t)stream};
+  void* const caches[2] = {cache, nullptr};
+  const int Ls[2] = {L, 0};
+  return fork_launch(R, T, d, s, caches, Ls, NL, B, N, elem_bytes == 2, nullptr, nullptr, nullptr, 0);
 }
 #undef OP_REQ
 

@@ -523,6 +523,45 @@ class VIMAPolicy(nn.Module):
             _ptr(prompt_token_mask), Lp, _ptr(h_obs), _ptr(h_mask), _ptr(h_act), T, _ptr(out) if T > 0 else None, self._stream()))
         return out
 
+    def _fork_source(self, source, B):
+        src = torch.as_tensor(source).to(dtype=torch.int32, device="cpu").reshape(-1).contiguous()
+        if src.numel() != B:
+            raise AssertionError(f"source must have one entry per sample ({B}), got {src.numel()}")
+        return src, ctypes.cast(src.data_ptr(), ctypes.POINTER(ctypes.c_int32))
+
+    def fork_samples(self, source, prompt_token: torch.Tensor, prompt_token_mask: torch.Tensor):
+        """Branch rollouts inside a batch that is stepping with `forward_step`: slot b continues the episode of slot `source[b]` (a
+        length-B int sequence or tensor; `source[b] == b` leaves b untouched). Nothing is recomputed (vima_decode_fork): the source's live
+        rows of every layer's history K/V, its key mask, position counter and restart flag and its prompt K/V block are copied into the
+        destination's slot, whose old episode is dropped. Every source must be its own source (`source[source[b]] == source[b]`: no
+        chains, no swaps -- survivors of a beam keep their slots); ValueError otherwise, and nothing changes.
+
+        The destination columns `prompt_token[:, b]` and `prompt_token_mask[b]` are overwritten with the source's -- in place where the
+        tensors already live on the device, so the caller's references stay valid. Keep calling `forward_step(..., step=previous + 1)`
+        with the UPDATED prompt tensors, which are returned as (prompt_token, prompt_token_mask).
+
+        The destination's next `forward_step` consumes or ignores its row of the previous-action token exactly as the source's would
+        (right after a restart of the source: ignores it). Fed the source's inputs it returns the source's output bit for bit; the caller
+        is free to feed the branches different actions and observations, which is the point. `steps_left()` of a destination is its
+        source's."""
+        self._ready()
+        dev = self._device
+        if prompt_token.stride(-1) != 1:
+            prompt_token = prompt_token.contiguous()
+        prompt_token = prompt_token.to(dev)
+        prompt_token_mask = prompt_token_mask.to(device=dev)
+        B = prompt_token.shape[1]
+        src, src_p = self._fork_source(source, B)
+        self._kv_key = None
+        _lib.check(self._lib.vima_decode_fork(self._handle, src_p, B, self._stream()))
+        dst = torch.nonzero(src != torch.arange(B, dtype=torch.int32)).reshape(-1)
+        if dst.numel():
+            from_ = src[dst].to(device=dev, dtype=torch.long)
+            dst = dst.to(dev)
+            prompt_token[:, dst] = prompt_token[:, from_]          # sources are never destinations: the gather reads no written column
+            prompt_token_mask[dst] = prompt_token_mask[from_]
+        return prompt_token, prompt_token_mask
+
     def history_room(self) -> int:
         """The largest T `restart_samples(..., history=)` accepts now: the number of most recent batch steps whose cache rows are all still
         there (without `decode_ring`: the steps taken since step 0). Host bookkeeping only."""
