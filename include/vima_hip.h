@@ -33,7 +33,7 @@ enum { VIMA_PRECISION_FP32 = 0, VIMA_PRECISION_BF16 = 1, VIMA_PRECISION_FP8W = 2
  * the matrix products run in split-bf16: each fp32 operand is written x = hi + lo with hi = bf16(x), lo = bf16(x - hi) (round to
  * nearest even) and a.b ~ hi_a.hi_b + hi_a.lo_b + lo_a.hi_b on three v_mfma_f32_32x32x16_bf16 with fp32 accumulation (about 3 x 2^-18
  * relative error per product against 2^-8 for bf16; 3/16 of the cost of the fp32 matrix instruction). Every GEMM runs on
- * gemm_kernel<float, ..., X3> (kinds 21 / 23 of vima_prof_read_gemm_kernels); attention with impl 1 and head dim 32 / 64 on attn_x3_kernel, other
+ * gemm_kernel<float, ..., X3> (kinds 21 / 23 of vima_prof_read_gemm_kernels); attention with impl 1 and head dim 32 / 64 on attn_mfma_kernel<D, MODE, X3>, other
  * head dims on the exact generic kernel. The 5-token ViT attention is the fp32 kernel. ABI version unchanged (additive). */
 /* FP8W: bf16 activations and matrix instruction, OCP e4m3 weights (+ one fp32 scale per output channel) for the large Linear layers.
  * FP8 : FP8W plus e4m3 ACTIVATIONS into the large GEMMs of the T5 stack, the ViT and the decoder's prompt K/V projection (one static

@@ -7,7 +7,7 @@ the iid mask as a control), so that clean, partly masked and dead tiles, a dead 
 Which kernel runs (launch_attn_mfma / Run::attn; there is no per-kernel attention record in `prof`, so `_kernel_of` restates the rule and
 the case table is checked against it):
   impl 0                                        attn_generic (any precision, head dims 16 / 64 here)
-  impl 1, bf16x3 handle                         attn_x3
+  impl 1, bf16x3 handle                         attn_x3 (launch_attn_x3: attn_mfma's one-wave kernel with X3 = true, fp32 operands)
   impl 1, bf16 handle, Lq <= 32, Lk >= 64, not T5  attn_split (128-key tiles, a 32-key quarter per wave; Lk = 300: waves 2, 3 of the last tile see no key)
   impl 1, bf16 handle, Lq >= attn4_min_lq (64)  attn_mfma4 (64-key tiles); 64 queries per wave with attn_qg 2 from Lq = 256 on, not in causal mode
   impl 1, bf16 handle, otherwise                attn_mfma (32-key tiles, one wave per 32 queries)

@@ -51,7 +51,7 @@ def _usage(remarks):
             name = m.group(1)
             res[name] = {}
             continue
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
+        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
         if m and name:
             res[name][m.group(1).split(" ")[0]] = int(m.group(2))
     return res
@@ -67,13 +67,16 @@ def _body(asm, name):
 # arguments W8, X3 are false, true; X3 = false ends in ...ELb0EEEv.
 _GEMM_F32 = r"gemm_kernelIf\S*ELb[01]EEEvNS0_7GemmDevE$"
 _GEMM_X3 = r"gemm_kernelIf\S*ELb0ELb1EEEvNS0_7GemmDevE$"
+# Likewise the split attention is attn_mfma_kernel<D, MODE, X3 = true>, the single-wave flash kernel (groups: D, X3).
+_ATTN_1W = r"16attn_mfma_kernelILi(\d+)ELi\dELb([01])EEEvNS0_7AttnDevE$"
+_ATTN_X3 = r"16attn_mfma_kernelILi\d+ELi\dELb1EEEvNS0_7AttnDevE$"
 
 
 # (source, kernel (regular expression on the mangled name), expected instantiations, VGPR + AGPR budget per lane: 2 waves / SIMD
 # for the 256-thread GEMM tile (two workgroups per CU), 2 / SIMD for the single-wave attention kernel)
 @needs_hipcc
 @pytest.mark.parametrize("src,kernel,count,budget", [pytest.param("gemm.hip", _GEMM_X3, 10, 256, id="gemm.hip-gemm_kernel_X3-10-256"),
-                                                     ("attention.hip", "attn_x3_kernel", 6, 256)])
+                                                     pytest.param("attention.hip", _ATTN_X3, 6, 256, id="attention.hip-attn_mfma_kernel_X3-6-256")])
 def test_split_kernels_compile_on_the_bf16_matrix_instruction(src, kernel, count, budget):
     asm, remarks = _compile(src)
     res = {k: v for k, v in _usage(remarks).items() if re.search(kernel, k)}
@@ -84,6 +87,23 @@ def test_split_kernels_compile_on_the_bf16_matrix_instruction(src, kernel, count
         body = _body(asm, name)
         assert "v_mfma_f32_32x32x16_bf16" in body, name
         assert "v_mfma_f32_32x32x2_f32" not in body, name
+
+
+@needs_hipcc
+def test_single_wave_attention_lds_is_one_plane_for_bf16_two_for_x3():
+    """X3 is a flag of the one single-wave attention body; its second V^T plane (lo_plane) must exist in the X3 instantiations only.
+    Static LDS = D rows of VT_STRIDE = 36 bf16 per plane: 2304 / 4608 bytes for D = 32 / 64, twice that with X3."""
+    _, remarks = _compile("attention.hip")
+    found = {False: [], True: []}
+    for name, v in _usage(remarks).items():
+        m = re.search(_ATTN_1W, name)
+        if not m:
+            continue
+        d, x3 = int(m.group(1)), m.group(2) == "1"
+        found[x3].append(name)
+        assert v.get("ScratchSize") == 0, (name, v)
+        assert v.get("LDS") == d * 36 * 2 * (2 if x3 else 1), (name, v)
+    assert len(found[False]) == 6 and len(found[True]) == 6, found
 
 
 @needs_hipcc

@@ -138,7 +138,7 @@ _ATTN_SHAPES = [(1, 77), (31, 31), (200, 200), (512, 512), (31, 512)]
 @pytest.mark.parametrize("D", [32, 64])
 @pytest.mark.parametrize("mode,Lq,Lk", [(m, *s) for m in (0, 1, 2) for s in _ATTN_SHAPES if m != 2 or s[0] == s[1]])   # causal: Lq == Lk
 def test_attention_split_bf16_against_fp64(D, mode, Lq, Lk):
-    """impl 1 on a bf16x3 handle (attn_x3_kernel): O(1) inputs, a key mask with one fully masked sample row; within 2e-5
+    """impl 1 on a bf16x3 handle (attn_mfma_kernel<D, MODE, X3 = true>): O(1) inputs, a key mask with one fully masked sample row; within 2e-5
     absolute of fp64 and of the exact generic kernel (impl 0) on the same handle."""
     pol = bare_policy(X3)
     B, H = 2, 3

@@ -12,7 +12,8 @@
 //       ATTN_CAUSAL Attention._attn (components.py:51-80): /sqrt(d); w*b + -1e4*(1-b) causal fill; + key mask
 //     Masked keys carry the score finfo(fp32).min exactly like the reference (so an all-masked row degenerates to the
 //     same uniform distribution); the -1e4 causal fill is kept literally (no causal tile skipping).
-//  * attn_x3       : precision "bf16x3": attn_mfma's single-wave kernel on fp32 operands with split-bf16 products (3 bf16 MFMAs each).
+//     Precision "bf16x3" runs attn_mfma_kernel<D, MODE, X3 = true>: the same single-wave body on fp32 operands with split-bf16
+//     products (3 bf16 MFMAs each); it has no 4-wave or split-key form.
 #include "kernels.h"
 #include <float.h>
 #include <type_traits>
@@ -280,171 +281,65 @@ __global__ __launch_bounds__(64) void attn_generic_kernel(const AttnDev p) {
 // so that a lane owns one query column: row max / sum are in-lane reductions plus one exchange with lane^32, and the
 // exponentiated scores are ALREADY laid out as the B-operand (P^T) of O^T += V^T.P^T -- no cross-lane shuffle of P.
 // V^T comes from a transposed LDS image of the V tile (rows padded to 72 B: conflict-free ds_read_b64).
+// The score fix-up restates the reference literally: key mask -FLT_MAX after scaling, causal fill -1e4 (q_off / win_end), T5 relative
+// bias without 1/sqrt(d); the running max starts at -inf, never at a finite sentinel.
+// X3 = precision "bf16x3": the same body on fp32 Q / K / V / out, every product in split-bf16 (split_bf16x8: x = hi + lo,
+// a.b ~ hi_a.hi_b + hi_a.lo_b + lo_a.hi_b, three v_mfma_f32_32x32x16_bf16, correction terms first). Q is split once per wave,
+// K once per tile; V^T is staged in LDS as a hi and a lo bf16 plane. The probabilities stay fp32 for the running sum and are
+// split for the PV product (the bf16 form rounds them first and sums the rounded weights).
 constexpr int VT_STRIDE = 36;  // bf16 elements per Vt row (32 keys + 4 pad)
 
 __device__ __forceinline__ uint32_t pack_bf16(float a, float b) { return pack2_bf16(a, b); }
 
-template <int D, int MODE>
-__global__ __launch_bounds__(64) void attn_mfma_kernel(const AttnDev p) {
-  __shared__ __attribute__((aligned(16))) bf16_t vt[D * VT_STRIDE];
-  constexpr int KD = D / 16;   // MFMA k-steps over the head dim
-  constexpr int OT = D / 32;   // 32-row tiles of O^T
-  const int lane = threadIdx.x;
-  const int hi = lane >> 5, l31 = lane & 31;
-  const int q0 = blockIdx.x * 32, h = blockIdx.y, b = blockIdx.z;
-  const bf16_t* Q = reinterpret_cast<const bf16_t*>(p.q);
-  const bf16_t* K = reinterpret_cast<const bf16_t*>(p.k);
-  const bf16_t* V = reinterpret_cast<const bf16_t*>(p.v);
-
-  const int qi = q0 + l31;
-  const int qrow = qi < p.Lq ? qi : p.Lq - 1;
-  bf16x8_t qf[KD];
-#pragma unroll
-  for (int dd = 0; dd < KD; ++dd) {
-    const uint4 u = *reinterpret_cast<const uint4*>(Q + ((long long)b * p.Lq + qrow) * p.ldq + h * D + dd * 16 + hi * 8);
-    qf[dd] = __builtin_bit_cast(bf16x8_t, u);
-  }
-  f32x16_t ot[OT];
-#pragma unroll
-  for (int it = 0; it < OT; ++it)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) ot[it][r] = 0.f;
-  float m_run = -INFINITY, l_run = 0.f;
-  const float* rb = (MODE == ATTN_T5) ? p.relbias + (long long)h * (2 * p.Lk - 1) + (p.Lk - 1) - qi : nullptr;
-  const uint8_t* km = p.kmask ? p.kmask + (long long)b * p.Lkr : nullptr;
-
-  for (int k0 = 0; k0 < p.Lk; k0 += 32) {
-    // ---- S^T tile: rows = 32 keys, cols = 32 queries
-    f32x16_t s;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) s[r] = 0.f;
-    {
-      const int krow = (k0 + l31) < p.Lk ? (k0 + l31) : p.Lk - 1;
-      const bf16_t* kp = K + b * p.k_bs + (long long)krow * p.ldk + h * p.k_hs + hi * 8;
-#pragma unroll
-      for (int dd = 0; dd < KD; ++dd) {
-        const uint4 u = *reinterpret_cast<const uint4*>(kp + dd * 16);
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, u), qf[dd], s, 0, 0, 0);
-      }
-    }
-    // ---- stage V^T of this key tile (previous tile's readers are done: single wave + barrier)
-    __syncthreads();
-#pragma unroll
-    for (int c0 = 0; c0 < (32 * D / 8) / 64; ++c0) {
-      const int c = lane + c0 * 64;
-      const int key = c / (D / 8), dc = c % (D / 8);
-      const int vrow = (k0 + key) < p.Lk ? (k0 + key) : p.Lk - 1;
-      const uint4 u = *reinterpret_cast<const uint4*>(V + b * p.v_bs + (long long)vrow * p.ldv + h * p.v_hs + dc * 8);
-      const uint32_t wds[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        vt[(dc * 8 + 2 * e) * VT_STRIDE + key] = (bf16_t)(wds[e] & 0xffffu);
-        vt[(dc * 8 + 2 * e + 1) * VT_STRIDE + key] = (bf16_t)(wds[e] >> 16);
-      }
-    }
-    // ---- scores -> probabilities (fp32), online softmax
-    float x[16];
-    float mt = -INFINITY;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-      float v;
-      if (key < p.Lk) {
-        const float madd = (km && !km[key]) ? -FLT_MAX : 0.0f;
-        if (MODE == ATTN_T5) {
-          v = s[r] + ((qi < p.Lq ? rb[key] : 0.f) + madd);
-        } else if (MODE == ATTN_CROSS) {
-          v = s[r] * p.scale + madd;
-        } else {
-          v = s[r] * p.scale;
-          if (key > qi + p.q_off && key < p.win_end) v = -1e4f;
-          v = v + madd;
-        }
-      } else {
-        v = -INFINITY;
-      }
-      x[r] = v;
-      mt = fmaxf(mt, v);
-    }
-    mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-    const float m_new = fmaxf(m_run, mt);
-    const float alpha = __expf(m_run - m_new);
-    uint32_t pk[8];
-    float rs = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; r += 2) {
-      const float p0 = __expf(x[r] - m_new), p1 = __expf(x[r + 1] - m_new);
-      const uint32_t u = pack_bf16(p0, p1);
-      pk[r >> 1] = u;
-      rs += __uint_as_float(u << 16) + __uint_as_float(u & 0xffff0000u);   // sum the ROUNDED weights actually used
-    }
-    rs += __shfl_xor(rs, 32, 64);
-    l_run = l_run * alpha + rs;
-    m_run = m_new;
-#pragma unroll
-    for (int it = 0; it < OT; ++it)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) ot[it][r] *= alpha;
-    __syncthreads();
-    // ---- O^T += V^T . P^T   (two K=16 MFMAs per 32-row tile of O^T)
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-      uint4 pu;
-      pu.x = pk[half * 4 + 0]; pu.y = pk[half * 4 + 1]; pu.z = pk[half * 4 + 2]; pu.w = pk[half * 4 + 3];
-      const bf16x8_t pf = __builtin_bit_cast(bf16x8_t, pu);
-#pragma unroll
-      for (int it = 0; it < OT; ++it) {
-        const bf16_t* vr = vt + (it * 32 + l31) * VT_STRIDE + 16 * half + 4 * hi;
-        const uint2 a0 = *reinterpret_cast<const uint2*>(vr);
-        const uint2 a1 = *reinterpret_cast<const uint2*>(vr + 8);
-        uint4 vu;
-        vu.x = a0.x; vu.y = a0.y; vu.z = a1.x; vu.w = a1.y;
-        ot[it] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, vu), pf, ot[it], 0, 0, 0);
-      }
-    }
-  }
-  if (qi < p.Lq) {
-    const float inv = 1.0f / l_run;
-    bf16_t* op = reinterpret_cast<bf16_t*>(p.out) + ((long long)b * p.Lq + qi) * p.ldo + h * D;
-#pragma unroll
-    for (int it = 0; it < OT; ++it)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d = it * 32 + 8 * g + 4 * hi;
-        store4(op + d, make_float4(ot[it][4 * g] * inv, ot[it][4 * g + 1] * inv, ot[it][4 * g + 2] * inv,
-                                   ot[it][4 * g + 3] * inv));
-      }
-  }
+// One 32x16 MFMA operand of a lane (8 consecutive k): as it is (bf16), or as its hi / lo split (fp32 operands, X3).
+struct AttnFrag { bf16x8_t v; };
+struct AttnFragX3 { bf16x8_t h, l; };
+__device__ __forceinline__ AttnFrag load_frag(const bf16_t* p) { return {__builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(p))}; }
+__device__ __forceinline__ AttnFragX3 load_frag(const float* p) {
+  AttnFragX3 f;
+  split_bf16x8(load4(p), load4(p + 4), f.h, f.l);
+  return f;
+}
+// a: key or V^T operand, b: Q or P operand
+__device__ __forceinline__ f32x16_t mma(const AttnFrag& a, const AttnFrag& b, f32x16_t c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.v, b.v, c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x16_t mma(const AttnFragX3& a, const AttnFragX3& b, f32x16_t c) {
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.l, b.h, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.l, c, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.h, c, 0, 0, 0);
+}
+// 8 keys of one V^T row: two ds_read_b64, 8 elements apart
+__device__ __forceinline__ bf16x8_t vt_frag(const bf16_t* vr) {
+  const uint2 a0 = *reinterpret_cast<const uint2*>(vr), a1 = *reinterpret_cast<const uint2*>(vr + 8);
+  return __builtin_bit_cast(bf16x8_t, make_uint4(a0.x, a0.y, a1.x, a1.y));
+}
+// X3: the lo plane of V^T. Function-local and called under `if constexpr (X3)` only, so that the bf16 instantiations own no second array.
+template <int D>
+__device__ __forceinline__ bf16_t* lo_plane() {
+  __shared__ __attribute__((aligned(16))) bf16_t vtl[D * VT_STRIDE];
+  return vtl;
 }
 
-// =============================================================================================== split-bf16 attention
-// precision "bf16x3": attn_mfma_kernel's single-wave formulation (S^T = K.Q^T with the key tile as the A operand, so that a
-// lane owns one query column; O^T += V^T.P^T) on fp32 Q / K / V / out, every product in split-bf16 (split_bf16x8: x = hi + lo,
-// a.b ~ hi_a.hi_b + hi_a.lo_b + lo_a.hi_b, three v_mfma_f32_32x32x16_bf16, correction terms first). Q is split once per wave,
-// K once per tile; V^T is staged in LDS as a hi and a lo bf16 plane. The probabilities stay fp32 for the running sum and are
-// split for the PV product. Score fix-up and mask semantics are attn_mfma_kernel's (key mask -FLT_MAX after scaling, causal
-// fill -1e4, T5 relative bias without 1/sqrt(d)); the running max starts at -inf, never at a finite sentinel.
-template <int D, int MODE>
-__global__ __launch_bounds__(64) void attn_x3_kernel(const AttnDev p) {
-  __shared__ __attribute__((aligned(16))) bf16_t vth[D * VT_STRIDE];
-  __shared__ __attribute__((aligned(16))) bf16_t vtl[D * VT_STRIDE];
+template <int D, int MODE, bool X3 = false>
+__global__ __launch_bounds__(64) void attn_mfma_kernel(const AttnDev p) {
+  using T = std::conditional_t<X3, float, bf16_t>;
+  using Frag = std::conditional_t<X3, AttnFragX3, AttnFrag>;
+  __shared__ __attribute__((aligned(16))) bf16_t vt[D * VT_STRIDE];   // X3: the hi plane
   constexpr int KD = D / 16;   // MFMA k-steps over the head dim
   constexpr int OT = D / 32;   // 32-row tiles of O^T
   const int lane = threadIdx.x;
   const int hi = lane >> 5, l31 = lane & 31;
   const int q0 = blockIdx.x * 32, h = blockIdx.y, b = blockIdx.z;
-  const float* Q = reinterpret_cast<const float*>(p.q);
-  const float* K = reinterpret_cast<const float*>(p.k);
-  const float* V = reinterpret_cast<const float*>(p.v);
+  const T* Q = reinterpret_cast<const T*>(p.q);
+  const T* K = reinterpret_cast<const T*>(p.k);
+  const T* V = reinterpret_cast<const T*>(p.v);
 
   const int qi = q0 + l31;
   const int qrow = qi < p.Lq ? qi : p.Lq - 1;
-  bf16x8_t qh[KD], ql[KD];
+  Frag qf[KD];
 #pragma unroll
-  for (int dd = 0; dd < KD; ++dd) {
-    const float* qp = Q + ((long long)b * p.Lq + qrow) * p.ldq + h * D + dd * 16 + hi * 8;
-    split_bf16x8(load4(qp), load4(qp + 4), qh[dd], ql[dd]);
-  }
+  for (int dd = 0; dd < KD; ++dd) qf[dd] = load_frag(Q + ((long long)b * p.Lq + qrow) * p.ldq + h * D + dd * 16 + hi * 8);
   f32x16_t ot[OT];
 #pragma unroll
   for (int it = 0; it < OT; ++it)
@@ -461,30 +356,36 @@ __global__ __launch_bounds__(64) void attn_x3_kernel(const AttnDev p) {
     for (int r = 0; r < 16; ++r) s[r] = 0.f;
     {
       const int krow = (k0 + l31) < p.Lk ? (k0 + l31) : p.Lk - 1;
-      const float* kp = K + b * p.k_bs + (long long)krow * p.ldk + h * p.k_hs + hi * 8;
+      const T* kp = K + b * p.k_bs + (long long)krow * p.ldk + h * p.k_hs + hi * 8;
 #pragma unroll
-      for (int dd = 0; dd < KD; ++dd) {
-        bf16x8_t kh, kl;
-        split_bf16x8(load4(kp + dd * 16), load4(kp + dd * 16 + 4), kh, kl);
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kl, qh[dd], s, 0, 0, 0);
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kh, ql[dd], s, 0, 0, 0);
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kh, qh[dd], s, 0, 0, 0);
-      }
+      for (int dd = 0; dd < KD; ++dd) s = mma(load_frag(kp + dd * 16), qf[dd], s);
     }
-    // ---- stage the hi / lo planes of V^T of this key tile (previous tile's readers are done: single wave + barrier)
+    // ---- stage V^T of this key tile (previous tile's readers are done: single wave + barrier); 16-byte loads = 8 bf16 or 4 fp32 (X3: hi / lo planes)
     __syncthreads();
+    constexpr int VE = 16 / sizeof(T);
 #pragma unroll
-    for (int c0 = 0; c0 < (32 * D / 4) / 64; ++c0) {
+    for (int c0 = 0; c0 < (32 * D / VE) / 64; ++c0) {
       const int c = lane + c0 * 64;
-      const int key = c / (D / 4), dc = c % (D / 4);
+      const int key = c / (D / VE), dc = c % (D / VE);
       const int vrow = (k0 + key) < p.Lk ? (k0 + key) : p.Lk - 1;
-      const float4 u = load4(V + b * p.v_bs + (long long)vrow * p.ldv + h * p.v_hs + dc * 4);
-      const float x4[4] = {u.x, u.y, u.z, u.w};
+      const T* vp = V + b * p.v_bs + (long long)vrow * p.ldv + h * p.v_hs + dc * VE;
+      if constexpr (X3) {
+        const float4 u = load4(vp);
+        const float x4[4] = {u.x, u.y, u.z, u.w};
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const bf16_t vh = f32_to_bf16(x4[e]);
-        vth[(dc * 4 + e) * VT_STRIDE + key] = vh;
-        vtl[(dc * 4 + e) * VT_STRIDE + key] = f32_to_bf16(x4[e] - bf16_to_f32(vh));
+        for (int e = 0; e < 4; ++e) {
+          const bf16_t vh = f32_to_bf16(x4[e]);
+          vt[(dc * 4 + e) * VT_STRIDE + key] = vh;
+          lo_plane<D>()[(dc * 4 + e) * VT_STRIDE + key] = f32_to_bf16(x4[e] - bf16_to_f32(vh));
+        }
+      } else {
+        const uint4 u = *reinterpret_cast<const uint4*>(vp);
+        const uint32_t wds[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          vt[(dc * 8 + 2 * e) * VT_STRIDE + key] = (bf16_t)(wds[e] & 0xffffu);
+          vt[(dc * 8 + 2 * e + 1) * VT_STRIDE + key] = (bf16_t)(wds[e] >> 16);
+        }
       }
     }
     // ---- scores -> probabilities (fp32), online softmax
@@ -514,12 +415,22 @@ __global__ __launch_bounds__(64) void attn_x3_kernel(const AttnDev p) {
     mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
     const float m_new = fmaxf(m_run, mt);   // finite: key k0 < Lk is in this tile
     const float alpha = __expf(m_run - m_new);
-    float pr[16];
+    std::conditional_t<X3, float[16], uint32_t[8]> pr;   // X3: fp32 probabilities; bf16: rounded pairs
     float rs = 0.f;
+    if constexpr (X3) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      pr[r] = __expf(x[r] - m_new);
-      rs += pr[r];
+      for (int r = 0; r < 16; ++r) {
+        pr[r] = __expf(x[r] - m_new);
+        rs += pr[r];
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 16; r += 2) {
+        const float p0 = __expf(x[r] - m_new), p1 = __expf(x[r + 1] - m_new);
+        const uint32_t u = pack_bf16(p0, p1);
+        pr[r >> 1] = u;
+        rs += __uint_as_float(u << 16) + __uint_as_float(u & 0xffff0000u);   // sum the ROUNDED weights actually used
+      }
     }
     rs += __shfl_xor(rs, 32, 64);
     l_run = l_run * alpha + rs;
@@ -529,28 +440,27 @@ __global__ __launch_bounds__(64) void attn_x3_kernel(const AttnDev p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) ot[it][r] *= alpha;
     __syncthreads();
-    // ---- O^T += V^T . P^T   (two K=16 steps per 32-row tile of O^T, three MFMAs each)
+    // ---- O^T += V^T . P^T   (two K=16 steps per 32-row tile of O^T)
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
-      bf16x8_t ph, pl;
-      split_bf16x8(make_float4(pr[half * 8 + 0], pr[half * 8 + 1], pr[half * 8 + 2], pr[half * 8 + 3]),
-                   make_float4(pr[half * 8 + 4], pr[half * 8 + 5], pr[half * 8 + 6], pr[half * 8 + 7]), ph, pl);
+      Frag pf;
+      if constexpr (X3)
+        split_bf16x8(make_float4(pr[half * 8 + 0], pr[half * 8 + 1], pr[half * 8 + 2], pr[half * 8 + 3]),
+                     make_float4(pr[half * 8 + 4], pr[half * 8 + 5], pr[half * 8 + 6], pr[half * 8 + 7]), pf.h, pf.l);
+      else
+        pf.v = __builtin_bit_cast(bf16x8_t, make_uint4(pr[half * 4 + 0], pr[half * 4 + 1], pr[half * 4 + 2], pr[half * 4 + 3]));
 #pragma unroll
       for (int it = 0; it < OT; ++it) {
         const int o = (it * 32 + l31) * VT_STRIDE + 16 * half + 4 * hi;
-        const uint2 h0 = *reinterpret_cast<const uint2*>(vth + o), h1 = *reinterpret_cast<const uint2*>(vth + o + 8);
-        const uint2 g0 = *reinterpret_cast<const uint2*>(vtl + o), g1 = *reinterpret_cast<const uint2*>(vtl + o + 8);
-        const bf16x8_t vh = __builtin_bit_cast(bf16x8_t, make_uint4(h0.x, h0.y, h1.x, h1.y));
-        const bf16x8_t vl = __builtin_bit_cast(bf16x8_t, make_uint4(g0.x, g0.y, g1.x, g1.y));
-        ot[it] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vl, ph, ot[it], 0, 0, 0);
-        ot[it] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh, pl, ot[it], 0, 0, 0);
-        ot[it] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh, ph, ot[it], 0, 0, 0);
+        Frag vf{vt_frag(vt + o)};
+        if constexpr (X3) vf.l = vt_frag(lo_plane<D>() + o);
+        ot[it] = mma(vf, pf, ot[it]);
       }
     }
   }
   if (qi < p.Lq) {
     const float inv = 1.0f / l_run;
-    float* op = reinterpret_cast<float*>(p.out) + ((long long)b * p.Lq + qi) * p.ldo + h * D;
+    T* op = reinterpret_cast<T*>(p.out) + ((long long)b * p.Lq + qi) * p.ldo + h * D;
 #pragma unroll
     for (int it = 0; it < OT; ++it)
 #pragma unroll
@@ -1401,6 +1311,24 @@ static int launch_split(const AttnDev& d, const AttnArgs& a, hipStream_t st) {
   return launch_dyn_lds<attn_split_kernel<D, MODE>>(dim3((unsigned)(((a.B * a.H + 15) / 16) * 16)), dim3(256), 160 * 1024, sh, st, d);
 }
 
+template <int D, int MODE, bool X3>
+static int launch_one_wave(const AttnDev& d, const AttnArgs& a, hipStream_t st) {
+  dim3 grid((unsigned)((a.Lq + 31) / 32), (unsigned)a.H, (unsigned)a.B);
+  hipLaunchKernelGGL((attn_mfma_kernel<D, MODE, X3>), grid, dim3(64), 0, st, d);
+  return (int)hipGetLastError();
+}
+
+// f(std::integral_constant<int, D>{}, std::integral_constant<int, MODE>{}) for head dim 32 or 64 (checked by the callers) and the three flavours
+template <typename F>
+static int dispatch_d_mode(const AttnArgs& a, F&& f) {
+  auto by_mode = [&](auto D) {
+    if (a.mode == ATTN_T5) return f(D, std::integral_constant<int, ATTN_T5>{});
+    if (a.mode == ATTN_CROSS) return f(D, std::integral_constant<int, ATTN_CROSS>{});
+    return f(D, std::integral_constant<int, ATTN_CAUSAL>{});
+  };
+  return a.D == 32 ? by_mode(std::integral_constant<int, 32>{}) : by_mode(std::integral_constant<int, 64>{});
+}
+
 int launch_attn_mfma(const AttnArgs& a, hipStream_t st) {
   if (a.B <= 0 || a.Lq <= 0 || a.Lk <= 0) return 0;
   if (a.D != 32 && a.D != 64) return (int)hipErrorInvalidValue;
@@ -1414,31 +1342,10 @@ int launch_attn_mfma(const AttnArgs& a, hipStream_t st) {
     if (a.D == 32) return a.mode == ATTN_CROSS ? launch_split<32, ATTN_CROSS>(d, a, st) : launch_split<32, ATTN_CAUSAL>(d, a, st);
     return a.mode == ATTN_CROSS ? launch_split<64, ATTN_CROSS>(d, a, st) : launch_split<64, ATTN_CAUSAL>(d, a, st);
   }
-  if (a.Lq >= min_lq4) {
-    if (a.D == 32) {
-      if (a.mode == ATTN_T5) return launch_mfma4<32, ATTN_T5>(d, a, st);
-      if (a.mode == ATTN_CROSS) return launch_mfma4<32, ATTN_CROSS>(d, a, st);
-      return launch_mfma4<32, ATTN_CAUSAL>(d, a, st);
-    }
-    if (a.mode == ATTN_T5) return launch_mfma4<64, ATTN_T5>(d, a, st);
-    if (a.mode == ATTN_CROSS) return launch_mfma4<64, ATTN_CROSS>(d, a, st);
-    return launch_mfma4<64, ATTN_CAUSAL>(d, a, st);
-  }
-  dim3 grid((unsigned)((a.Lq + 31) / 32), (unsigned)a.H, (unsigned)a.B);
-#define VIMA_ATTN(D_, M_) hipLaunchKernelGGL((attn_mfma_kernel<D_, M_>), grid, dim3(64), 0, st, d)
-  if (a.D == 32) {
-    if (a.mode == ATTN_T5) VIMA_ATTN(32, ATTN_T5);
-    else if (a.mode == ATTN_CROSS) VIMA_ATTN(32, ATTN_CROSS);
-    else VIMA_ATTN(32, ATTN_CAUSAL);
-  } else {
-    if (a.mode == ATTN_T5) VIMA_ATTN(64, ATTN_T5);
-    else if (a.mode == ATTN_CROSS) VIMA_ATTN(64, ATTN_CROSS);
-    else VIMA_ATTN(64, ATTN_CAUSAL);
-  }
-#undef VIMA_ATTN
-  return (int)hipGetLastError();
+  if (a.Lq >= min_lq4)
+    return dispatch_d_mode(a, [&](auto D, auto mode) { return launch_mfma4<decltype(D)::value, decltype(mode)::value>(d, a, st); });
+  return dispatch_d_mode(a, [&](auto D, auto mode) { return launch_one_wave<decltype(D)::value, decltype(mode)::value, false>(d, a, st); });
 }
-
 
 int launch_attn_x3(const AttnArgs& a, hipStream_t st) {
   if (a.B <= 0 || a.Lq <= 0 || a.Lk <= 0) return 0;
@@ -1447,20 +1354,8 @@ int launch_attn_x3(const AttnArgs& a, hipStream_t st) {
   // 16-byte fp32 loads / stores: rows, head offsets and batch strides must be 16-B aligned
   if ((a.ldq % 4) || (a.ldk % 4) || (a.ldv % 4) || (a.ldo % 4) || (a.k_bs % 4) || (a.v_bs % 4) || (a.k_hs % 4) || (a.v_hs % 4))
     return (int)hipErrorInvalidValue;
-  const AttnDev d = to_dev(a);
-  dim3 grid((unsigned)((a.Lq + 31) / 32), (unsigned)a.H, (unsigned)a.B);
-#define VIMA_ATTN(D_, M_) hipLaunchKernelGGL((attn_x3_kernel<D_, M_>), grid, dim3(64), 0, st, d)
-  if (a.D == 32) {
-    if (a.mode == ATTN_T5) VIMA_ATTN(32, ATTN_T5);
-    else if (a.mode == ATTN_CROSS) VIMA_ATTN(32, ATTN_CROSS);
-    else VIMA_ATTN(32, ATTN_CAUSAL);
-  } else {
-    if (a.mode == ATTN_T5) VIMA_ATTN(64, ATTN_T5);
-    else if (a.mode == ATTN_CROSS) VIMA_ATTN(64, ATTN_CROSS);
-    else VIMA_ATTN(64, ATTN_CAUSAL);
-  }
-#undef VIMA_ATTN
-  return (int)hipGetLastError();
+  const AttnDev d = to_dev(a);   // always the one-wave kernel: there is no split-key or 4-wave form on fp32 operands
+  return dispatch_d_mode(a, [&](auto D, auto mode) { return launch_one_wave<decltype(D)::value, decltype(mode)::value, true>(d, a, st); });
 }
 
 }  // namespace vima

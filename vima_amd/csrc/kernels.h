@@ -362,7 +362,7 @@ struct AttnArgs {
 // generic exact kernel (any T); the MFMA flash kernel (bf16, D in {32,64})
 int launch_attn_generic(const AttnArgs& a, bool is_bf16, hipStream_t st);
 int launch_attn_mfma(const AttnArgs& a, hipStream_t st);
-// precision "bf16x3": fp32 operands, split-bf16 products on the matrix cores (D in {32,64}; attn_x3_kernel)
+// precision "bf16x3": fp32 operands, split-bf16 products on the matrix cores (D in {32,64}; attn_mfma_kernel<D, MODE, X3 = true>, always the one-wave kernel)
 int launch_attn_x3(const AttnArgs& a, hipStream_t st);
 
 }  // namespace vima
