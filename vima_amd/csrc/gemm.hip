@@ -28,6 +28,7 @@
 //  * blockIdx -> tile mapping is XCD-aware: consecutive workgroups on one XCD (blockIdx % 8) walk the n-tiles of
 //    the same A row panel, so the panel is fetched from HBM once per XCD L2.
 #include "kernels.h"
+#include "gemm_route.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -1892,44 +1893,7 @@ __global__ __launch_bounds__(TileW::THREADS, 2) void gemm_wide_kernel(const Gemm
 #include "gemm_skinny.inc"  // gemm_skinny_kernel: M <= 32 (one env step at batch <= 3), K split over the waves of a workgroup, operands straight from global memory
 #endif
 
-// Knob resolution: the handle's Tuning value when set (>= 0), otherwise the process default from the environment
-// (read once; never written afterwards, so it is safe to share between handles).
-inline int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return (e && e[0]) ? atoi(e) : dflt;
-}
-inline int env_cached(const char* name, int& cache, int dflt) {
-  if (cache < 0) cache = env_int(name, dflt);
-  return cache;
-}
-int g_env_variant = -1, g_env_tile = -1, g_env_raster = -1, g_env_epi = -1, g_env_persist = -1, g_env_small = -1, g_env_splitk = -1;
-#define VIMA_KNOB(fn, field, env, cache, dflt)                                   \
-  inline int fn(const Tuning* t) { return (t && t->field >= 0) ? t->field : env_cached(env, cache, dflt); }
-VIMA_KNOB(gemm_variant, gemm_variant, "VIMA_GEMM_VARIANT", g_env_variant, 1)
-VIMA_KNOB(gemm_tile, gemm_tile, "VIMA_GEMM_TILE", g_env_tile, 0)
-VIMA_KNOB(gemm_raster, gemm_raster, "VIMA_GEMM_RASTER", g_env_raster, 0)
-VIMA_KNOB(gemm_epi, gemm_epi, "VIMA_GEMM_EPI", g_env_epi, 1)
-VIMA_KNOB(gemm_persist, gemm_persist, "VIMA_GEMM_PERSIST", g_env_persist, 1)
-VIMA_KNOB(gemm_small, gemm_small, "VIMA_GEMM_SMALL", g_env_small, 1)
-VIMA_KNOB(gemm_splitk, gemm_splitk, "VIMA_GEMM_SPLITK", g_env_splitk, 0)
-int g_env_wide = -1;
-VIMA_KNOB(gemm_wide, gemm_wide, "VIMA_GEMM_WIDE", g_env_wide, 0)
-int g_env_pp = -1;
-VIMA_KNOB(gemm_pp, gemm_pp, "VIMA_GEMM_PP", g_env_pp, 1)
-int g_env_q4 = -1;
-VIMA_KNOB(gemm_q4, gemm_q4, "VIMA_GEMM_Q4", g_env_q4, 6)
-int g_env_resident = -1, g_env_res_maxwg = -1;
-VIMA_KNOB(gemm_resident, gemm_resident, "VIMA_GEMM_RESIDENT", g_env_resident, 1)
-VIMA_KNOB(gemm_res_maxwg, gemm_res_maxwg, "VIMA_GEMM_RES_MAXWG", g_env_res_maxwg, 256)
-int g_env_res_nch = -1;
-VIMA_KNOB(gemm_res_nch, gemm_res_nch, "VIMA_GEMM_RES_NCH", g_env_res_nch, 0)
-int g_env_skinny = -1;
-VIMA_KNOB(gemm_skinny, gemm_skinny, "VIMA_GEMM_SKINNY", g_env_skinny, 1)
-int g_env_flat = -1;
-VIMA_KNOB(gemm_flat, gemm_flat, "VIMA_GEMM_FLAT", g_env_flat, 1)
-#undef VIMA_KNOB
-
-inline bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
+static_assert(kGemmInvalid == (int)hipErrorInvalidValue, "gemm_route.h refuses with hipErrorInvalidValue");
 
 // f(std::integral_constant<int, ACT>{}) for the activation `act`: the launchers whose kernels exist for all four of them
 template <typename F>
@@ -1972,22 +1936,12 @@ int launch_tile(GemmDev d, const GemmArgs& a, bool vec, hipStream_t st) {
     }
   }
   if constexpr (sizeof(T) == 2) {
-    if (a.w8)   // fp8 weights: always the asm LDS-DMA pipeline and the vector epilogue (checked by launch_t)
+    if (a.w8)   // fp8 weights: always the asm LDS-DMA pipeline and the vector epilogue (gemm_route refuses fp8 weights without it)
       return dispatch_act(a.act, [&](auto act) { return launch_inst<T, TL, decltype(act)::value, true, true, true>(d, grid, st); });
   }
   if (!vec) return launch_inst<T, TL, -1, false, ASMLDS>(d, grid, st);
 #endif
   return dispatch_act(a.act, [&](auto act) { return launch_inst<T, TL, decltype(act)::value, true, ASMLDS>(d, grid, st); });
-}
-
-// 256x256 persistent kernels: the specialised epilogue for the combinations the policy uses (0 = none of them)
-inline int persistent_epi(const GemmArgs& a, const GemmDev& d) {
-  if (a.rb != 0) return 0;
-  if (d.wide8 && !a.mul && !a.res && !a.resT && !a.ssq_out) return 1;
-  if (d.wide8 && a.mul && a.outT && !a.out8 && !a.res && !a.resT && !a.rs_ssq && !a.ssq_out) return 2;
-  if (!d.wide8 && a.out32 && !a.mul && !a.rs_ssq && !a.resT) return 3;   // fp32 (+ operand-type) output, with or without a residual
-  if (d.wide8 && a.resT && !a.mul && !a.res && !a.rs_ssq) return 4;
-  return 0;
 }
 
 // n-tiles per n-group of a persistent raster: W panels (BN rows of K elements) of one group <= `VIMA_GEMM_NGROUP_KB` (default 2560 KiB)
@@ -2011,36 +1965,29 @@ int launch_persistent_w(const GemmDev& d, int grid, hipStream_t st) {
 }
 template <int ACT, int EPI>
 int launch_persistent_inst(const GemmDev& d, int grid, hipStream_t st) {
-#ifdef VIMA_GEMM_LAB
+#ifdef VIMA_GEMM_LAB   // (the route of the lab build refuses fp8 weights here)
   return launch_persistent_w<ACT, EPI, false>(d, grid, st);
 #else
   return d.wscale ? launch_persistent_w<ACT, EPI, true>(d, grid, st) : launch_persistent_w<ACT, EPI, false>(d, grid, st);
 #endif
 }
 
-int launch_persistent(GemmDev d, const GemmArgs& a, hipStream_t st) {
-  if (a.split_n) return -1;   // (the column-split output is not part of the 256x256 epilogues)
+int launch_persistent(GemmDev d, const GemmArgs& a, int epi, hipStream_t st) {
   d.mtiles = (d.M + TileL::BM - 1) / TileL::BM;
   d.ntiles = (d.N + TileL::BN - 1) / TileL::BN;
   d.vtotal = (d.mtiles + 7) / 8 * 8 * d.ntiles;
   d.raster = 0; d.ngroup = 1; d.epi_lds = 1;
   d.dbg = a.tune ? a.tune->gemm_dbg : nullptr;
   const int grid = d.vtotal < num_cu() ? d.vtotal : num_cu();
-  // specialised epilogues for the combinations the policy uses; everything else takes the generic instantiation
-  const int epi = persistent_epi(a, d);
-  if (a.resT && epi != 4) return -1;   // one-tile-per-workgroup kernel
-  if (a.hm_D) {   // head-major output: its own instantiation (as a run-time branch of EPI 1 it cost every row-major launch ~9 %)
-    if (epi != 1 || a.act != ACT_NONE) return (int)hipErrorInvalidValue;
-    return launch_persistent_inst<ACT_NONE, 5>(d, grid, st);
-  }
   switch (a.act * 8 + epi) {
     case ACT_NONE * 8 + 1: return launch_persistent_inst<ACT_NONE, 1>(d, grid, st);
     case ACT_NONE * 8 + 3: return launch_persistent_inst<ACT_NONE, 3>(d, grid, st);
     case ACT_NONE * 8 + 4: return launch_persistent_inst<ACT_NONE, 4>(d, grid, st);
+    case ACT_NONE * 8 + 5: return launch_persistent_inst<ACT_NONE, 5>(d, grid, st);
     case ACT_RELU * 8 + 1: return launch_persistent_inst<ACT_RELU, 1>(d, grid, st);
     case ACT_GELU * 8 + 2: return launch_persistent_inst<ACT_GELU, 2>(d, grid, st);
     case ACT_QUICKGELU * 8 + 1: return launch_persistent_inst<ACT_QUICKGELU, 1>(d, grid, st);
-    default: return -1;   // no specialised instantiation (the all-runtime form spills): one-tile-per-workgroup kernel
+    default: return (int)hipErrorInvalidValue;
   }
 }
 
@@ -2059,12 +2006,8 @@ int launch_pp_inst(const GemmDev& d, int grid, hipStream_t st) {
   return launch_pp_inst2<ACT, EPI, false>(d, grid, st);
 }
 
-// ping-pong persistent kernel (option gemm_pp): same eligibility as launch_persistent plus an even number of K-tiles and
-// bf16 weights; returns -1 when the problem does not fit it (caller falls back)
-int launch_pp(GemmDev d, const GemmArgs& a, hipStream_t st) {
-  if (a.split_n) return -1;
-  if (a.a8) { if (!a.w8 || a.K % 256 != 0) return -1; }
-  else if (a.w8 || (a.K / 64) % 2 != 0 || a.out8) return -1;   // (an fp8 copy of a bf16-operand GEMM's output: launch_persistent)
+// ping-pong persistent kernel (option gemm_pp)
+int launch_pp(GemmDev d, const GemmArgs& a, int epi, hipStream_t st) {
   d.mtiles = (d.M + TileL::BM - 1) / TileL::BM;
   d.ntiles = (d.N + TileL::BN - 1) / TileL::BN;
   d.vtotal = (d.mtiles + 7) / 8 * 8 * d.ntiles;
@@ -2084,24 +2027,16 @@ int launch_pp(GemmDev d, const GemmArgs& a, hipStream_t st) {
     if (tiles <= 2LL * ncu && rounds_flat < rounds_raster && gemm_flat(a.tune)) { d.flat = 1; d.vtotal = (int)tiles; }
   }
   const int grid = d.vtotal < ncu ? d.vtotal : ncu;
-  const int epi = persistent_epi(a, d);
-  if (a.resT && epi != 4) return -1;
-  if (a.pair32) {   // GEGLU pair over block-interleaved weights (launch_t has validated the form): its own epilogue
-    if (a.a8 || a.act != ACT_GELU) return -1;
-    return launch_pp_inst<ACT_GELU, 6>(d, grid, st);
-  }
-  if (a.hm_D) {   // head-major output: its own instantiation (see launch_persistent)
-    if (epi != 1 || a.act != ACT_NONE) return (int)hipErrorInvalidValue;
-    return launch_pp_inst<ACT_NONE, 5>(d, grid, st);
-  }
   switch (a.act * 8 + epi) {
     case ACT_NONE * 8 + 1: return launch_pp_inst<ACT_NONE, 1>(d, grid, st);
     case ACT_NONE * 8 + 3: return launch_pp_inst<ACT_NONE, 3>(d, grid, st);
     case ACT_NONE * 8 + 4: return launch_pp_inst<ACT_NONE, 4>(d, grid, st);
+    case ACT_NONE * 8 + 5: return launch_pp_inst<ACT_NONE, 5>(d, grid, st);
     case ACT_RELU * 8 + 1: return launch_pp_inst<ACT_RELU, 1>(d, grid, st);
     case ACT_GELU * 8 + 2: return launch_pp_inst<ACT_GELU, 2>(d, grid, st);
+    case ACT_GELU * 8 + 6: return launch_pp_inst<ACT_GELU, 6>(d, grid, st);   // GEGLU pair over block-interleaved weights
     case ACT_QUICKGELU * 8 + 1: return launch_pp_inst<ACT_QUICKGELU, 1>(d, grid, st);
-    default: return -1;
+    default: return (int)hipErrorInvalidValue;
   }
 }
 
@@ -2110,18 +2045,10 @@ int launch_wide_inst(const GemmDev& d, int grid, hipStream_t st) {
   return launch_dyn_lds<gemm_wide_kernel<ACT, EPI>>(dim3((unsigned)grid), dim3(TileW::THREADS), TileW::SMEM_BYTES, TileW::SMEM_BYTES, st, d);
 }
 
-// 256 x 384 persistent kernel (option gemm_wide): returns -1 when the problem does not fit it (caller falls back)
-int launch_wide(GemmDev d, const GemmArgs& a, hipStream_t st) {
-  if (a.w8 || a.rb != 0 || a.batch > 1 || a.M % TileW::BM || a.N % TileW::BN || a.K < 2 * 64 || a.K % 64 || !d.wide8) return -1;
-  if ((long long)a.M * a.lda * 2 >= (1LL << 32) || (long long)a.N * a.ldw * 2 >= (1LL << 32)) return -1;
-  if (a.mul || a.res || a.out32 || a.hm_D || a.split_n) return -1;
-  int epi = 0;
-  if (!a.resT && !a.ssq_out) epi = 1;
-  else if (a.resT && !a.rs_ssq && a.act == ACT_NONE) epi = 4;
-  if (!epi) return -1;
+// 256 x 384 persistent kernel (option gemm_wide)
+int launch_wide(GemmDev d, const GemmArgs& a, int epi, hipStream_t st) {
   d.mtiles = d.M / TileW::BM;
   d.ntiles = d.N / TileW::BN;
-  if ((long long)d.mtiles * d.ntiles < 128) return -1;
   d.vtotal = (d.mtiles + 7) / 8 * 8 * d.ntiles;
   d.raster = 0; d.ngroup = 1; d.epi_lds = 1;
   d.dbg = a.tune ? a.tune->gemm_dbg : nullptr;
@@ -2131,7 +2058,7 @@ int launch_wide(GemmDev d, const GemmArgs& a, hipStream_t st) {
     case ACT_RELU * 8 + 1: return launch_wide_inst<ACT_RELU, 1>(d, grid, st);
     case ACT_QUICKGELU * 8 + 1: return launch_wide_inst<ACT_QUICKGELU, 1>(d, grid, st);
     case ACT_NONE * 8 + 4: return launch_wide_inst<ACT_NONE, 4>(d, grid, st);
-    default: return -1;
+    default: return (int)hipErrorInvalidValue;
   }
 }
 
@@ -2140,34 +2067,24 @@ int launch_q4_inst(const GemmDev& d, int grid, hipStream_t st) {
   return launch_dyn_lds<gemm_q4_kernel<ACT, EPI, MIH>>(dim3((unsigned)grid), dim3(Q4::THREADS), Q4T<MIH>::SMEM_BYTES, Q4T<MIH>::SMEM_BYTES, st, d);
 }
 
-// four-wave kernel (option gemm_q4: 1 = 256 x 384 tile, 2 = 128 x 384 tile): returns -1 when the problem does not fit it (caller falls back to the 256x256 kernels)
+// four-wave kernel (option gemm_q4): MIH 2 = its 256 x 384 tile, 1 = its 128 x 384 tile
 template <int MIH>
-int launch_q4(GemmDev d, const GemmArgs& a, hipStream_t st) {
+int launch_q4(GemmDev d, const GemmArgs& a, int epi, hipStream_t st) {
   using QC = Q4T<MIH>;
-  if (a.w8 || a.a8 || a.rb != 0 || a.batch > 1 || a.M % QC::BM || a.N % QC::BN || a.K < 128 || a.K % 128 || !d.wide8) return -1;
-  if ((long long)a.M * a.lda * 2 >= (1LL << 32) || (long long)a.N * a.ldw * 2 >= (1LL << 32)) return -1;
-  if (a.mul || a.res || a.out32 || a.out8 || a.split_n || a.pair32 || a.sum_out || a.rs_sum) return -1;
-  if (a.rs_ssq && (MIH != 1 || a.rs_parts != 24 || a.resT)) return -1;   // fused-RMSNorm consumer: the 128 x 384 tile only (E = 768: 24 partials per row), bf16-output epilogues
-  int epi = 0;
-  if (!a.resT && !a.ssq_out) epi = a.hm_D ? 5 : 1;
-  else if (a.resT && a.act == ACT_NONE && !a.hm_D) epi = 4;
-  if (!epi) return -1;
-  if (epi == 5 && (a.act != ACT_NONE || a.hm_L % QC::BM != 0)) return -1;
   d.mtiles = d.M / QC::BM;
   d.ntiles = d.N / QC::BN;
-  if ((long long)d.mtiles * d.ntiles < 128) return -1;
   d.vtotal = (d.mtiles + 7) / 8 * 8 * d.ntiles;
   d.raster = 0; d.epi_lds = 1; d.flat = 0;
   d.ngroup = ngroup_for(QC::BN, a.K, 2, d.ntiles);   // n-groups whose W panels stay in an XCD's L2
   d.dbg = a.tune ? a.tune->gemm_dbg : nullptr;
   const int grid = d.vtotal < num_cu() ? d.vtotal : num_cu();
-  if (epi == 5) return launch_q4_inst<ACT_NONE, 5, MIH>(d, grid, st);
   switch (a.act * 8 + epi) {
     case ACT_NONE * 8 + 1: return launch_q4_inst<ACT_NONE, 1, MIH>(d, grid, st);
     case ACT_RELU * 8 + 1: return launch_q4_inst<ACT_RELU, 1, MIH>(d, grid, st);
     case ACT_QUICKGELU * 8 + 1: return launch_q4_inst<ACT_QUICKGELU, 1, MIH>(d, grid, st);
     case ACT_NONE * 8 + 4: return launch_q4_inst<ACT_NONE, 4, MIH>(d, grid, st);
-    default: return -1;
+    case ACT_NONE * 8 + 5: return launch_q4_inst<ACT_NONE, 5, MIH>(d, grid, st);
+    default: return (int)hipErrorInvalidValue;
   }
 }
 
@@ -2204,35 +2121,14 @@ dim3 resident_geometry(GemmDev& d, const GemmArgs& a) {
   d.dbg = a.tune ? a.tune->gemm_dbg : nullptr;
   return dim3((unsigned)(d.mtiles * d.ntiles), (unsigned)(a.batch > 0 ? a.batch : 1), 1);
 }
-// bf16 problems with a vector-aligned epilogue and no fp8 operands; < 0 = not taken. Tile (`force`: gemm_tile 10 / 11 / 12 = 32x32 /
-// 64x32 / 64x64 whatever the grid): the smallest one whose grid still fits the chip once (`gemm_res_maxwg`, default 256 = one
-// workgroup per CU; M <= 32 always takes 32x32) -- a lone 32x32 accumulator per wave is a dependent MFMA chain, so what counts is
-// how many of them run side by side, not the operand bytes per FLOP (measured, profiles/r03_small_m.txt).
-int launch_resident(const GemmDev& d, const GemmArgs& a, int force, hipStream_t st) {
-  if (a.w8 || a.a8 || a.out8 || a.K % 64 != 0 || (a.N % 4 != 0 && !a.grp_col)) return -1;
-  if (a.ssq_out && a.act != ACT_NONE) return -1;
-  if (a.resT && a.act != ACT_NONE) return -1;   // the kernel applies the bf16 residual only without an activation (launch_t refuses the pair anyway)
-  const long long nb = a.batch > 0 ? a.batch : 1;
-  const long long maxwg = gemm_res_maxwg(a.tune);
-  const long long m32 = (a.M + 31) / 32, m64 = (a.M + 63) / 64, n32 = (a.N + 31) / 32, n64 = (a.N + 63) / 64;
-  int tile = 0;
-  if (a.W2) {   // GEGLU pair: 32x32 for M <= 32, else 64x64 while its grid fits the chip once (the caller asks gemm_dual_ok() first)
-    tile = a.M <= 32 ? 15 : (m64 * n64 <= maxwg ? 16 : 0);
-    if (!tile || a.act != ACT_GELU) return -1;
-    if (a.kernel_id) *a.kernel_id = tile * 1000 + (a.act + 1) * 10;
-    return tile == 15 ? launch_resident_act<RT32D, ACT_GELU>(d, a, st) : launch_resident_act<RT64D, ACT_GELU>(d, a, st);
-  }
-  if (force) tile = force;
-  else if (a.M <= 32) tile = (n32 * nb <= 4 * maxwg || a.grp_col) ? 10 : 0;
-  else if (m32 * n32 * nb <= maxwg) tile = 10;
-  else if (m64 * n32 * nb <= maxwg) tile = 11;
-  else if (m64 * n64 * nb <= maxwg || a.grp_col) tile = 12;
-  if (!tile) return -1;
-  if (a.kernel_id) *a.kernel_id = tile * 1000 + (a.act + 1) * 10;
+int launch_resident(const GemmDev& d, const GemmArgs& a, GemmFamily tile, hipStream_t st) {
   switch (tile) {
-    case 10: return launch_resident_tile<RT32>(d, a, st);
-    case 11: return launch_resident_tile<RT64x32>(d, a, st);
-    default: return launch_resident_tile<RT64>(d, a, st);
+    case GF_RT32_DUAL: return launch_resident_act<RT32D, ACT_GELU>(d, a, st);
+    case GF_RT64_DUAL: return launch_resident_act<RT64D, ACT_GELU>(d, a, st);
+    case GF_RT32: return launch_resident_tile<RT32>(d, a, st);
+    case GF_RT64x32: return launch_resident_tile<RT64x32>(d, a, st);
+    case GF_RT64: return launch_resident_tile<RT64>(d, a, st);
+    default: return (int)hipErrorInvalidValue;
   }
 }
 #endif
@@ -2248,14 +2144,8 @@ template <typename ST>
 int launch_skinny_act(const GemmDev& d, const GemmArgs& a, dim3 grid, hipStream_t st) {
   return dispatch_act(a.act, [&](auto act) { return launch_skinny_inst<ST, decltype(act)::value>(d, grid, st); });
 }
-// bf16 problems of at most 32 rows with a vector-aligned epilogue and no fp8 operands; < 0 = not taken. The number of waves (= the K split)
-// depends on K only.
+// The number of waves (= the K split) depends on K only.
 int launch_skinny(GemmDev d, const GemmArgs& a, hipStream_t st) {
-  if (a.M > 32 || a.w8 || a.a8 || a.out8 || a.K % 64 != 0 || a.N % 4 != 0 || a.grp_col || a.hm_D || a.pair32) return -1;
-  if ((a.ssq_out || a.resT) && a.act != ACT_NONE) return -1;
-  if (a.W2 && (a.act != ACT_GELU || a.K > 2048)) return -1;
-  if ((long long)a.M * a.lda * 2 >= (1LL << 31) || (long long)a.N * a.ldw * 2 >= (1LL << 31)) return -1;   // buffer descriptors with 31-bit byte ranges
-  if (a.W2 && ((long long)a.M * a.lda2 * 2 >= (1LL << 31) || (long long)a.N * a.ldw2 * 2 >= (1LL << 31))) return -1;
   // columns per workgroup: the narrowest of 32 / 16 / 8 that still leaves whole tiles and at most ~256 workgroups -- what bounds a launch is the
   // bytes ONE workgroup pulls (a CU streams ~24 GB/s), so N is spread over as many CUs as there are; partial sums for a downstream fused norm are
   // per 32 columns and need the full-width tile
@@ -2271,7 +2161,6 @@ int launch_skinny(GemmDev d, const GemmArgs& a, hipStream_t st) {
   d.dbg = a.tune ? a.tune->gemm_dbg : nullptr;
   const dim3 grid((unsigned)((a.N + cols - 1) / cols), (unsigned)nb, 1);
   const int ks = a.K / 16;
-  if (a.kernel_id) *a.kernel_id = (a.W2 ? 18 : 17) * 1000 + (a.act + 1) * 10;
   if (a.W2) return ks <= 64 ? launch_skinny_inst<SkTile<4, 12, true>, ACT_GELU>(d, grid, st) : launch_skinny_inst<SkTile<8, 8, true>, ACT_GELU>(d, grid, st);
   if (ks <= 64) return launch_skinny_act<SkTile<4, 12, false>>(d, a, grid, st);
   if (ks <= 128) return launch_skinny_act<SkTile<8, 12, false>>(d, a, grid, st);
@@ -2279,33 +2168,7 @@ int launch_skinny(GemmDev d, const GemmArgs& a, hipStream_t st) {
 }
 #endif
 
-// ------------------------------------------------------------------------------------------------ split-K
-// With M = 8 .. 512 rows (batch 1 .. 32 decoder / prompt GEMMs) a 128x128 grid has 6 .. 100 workgroups, each walking
-// its K dimension serially at the per-CU operand-path rate (~23 B/clk): 8 us at K = 768, 30 us at K = 3072, most CUs
-// idle. Such problems are split along K into S ranges (pass 1: the same kernel, batched over the ranges, raw fp32
-// partials) and finished by an elementwise pass that sums the partials in split order -- deterministic -- and applies
-// the whole epilogue. The summation order differs from the single-pass kernels, i.e. results would depend (at fp32
-// rounding level) on whether a problem was small enough to be split -- batch-composition and chunking invariance would
-// only hold to bf16 tolerance. Measured gain: 35 -> 25 us at M = 8, K = 3072; nothing at K = 768 (a second launch costs
-// as much as the saved slices); batch-1 step 6.2 -> 5.5 ms. It is therefore OPT-IN (option gemm_splitk / VIMA_GEMM_SPLITK).
-struct SplitPlan { int S; int Ks; };
-inline SplitPlan splitk_plan(const GemmArgs& a, bool is_bf16) {
-  SplitPlan p{1, a.K};
-  if (!gemm_splitk(a.tune) || a.w8) return p;
-  const int bk = is_bf16 ? 64 : 32;
-  if (a.batch > 1 || a.M <= 0 || a.N <= 0 || a.K % bk || a.N % 4 || a.ssq_out || a.rb > 0 || a.resT) return p;
-  if (a.pair32 || a.hm_D || a.W2 || a.grp_col || a.rs_sum || a.sum_out) return p;   // forms whose epilogue the reduce pass does not have
-  const long long tiles = (long long)((a.M + 127) / 128) * ((a.N + 127) / 128);
-  const int slices = a.K / bk;
-  if (tiles >= 128 || slices < 24) return p;   // measured: the second pass only pays from K = 1536 (bf16) on
-  const int want = (int)((256 + tiles - 1) / tiles);
-  int best = 1;
-  for (int s = 2; s <= want && s * 2 <= slices; ++s)
-    if (slices % s == 0) best = s;
-  if (best > 1) { p.S = best; p.Ks = slices / best * bk; }
-  return p;
-}
-
+// ------------------------------------------------------------------------------------------------ split-K (the plan: gemm_route.h)
 template <typename T>
 __global__ __launch_bounds__(256) void gemm_reduce_kernel(const float* __restrict__ part, int S, long long MN, int M, int N,
                                                           const float* bias, int act, const T* mul, int ldmul,
@@ -2334,46 +2197,25 @@ __global__ __launch_bounds__(256) void gemm_reduce_kernel(const float* __restric
 }
 
 template <typename T>
-int launch_t(const GemmArgs& a, hipStream_t st) {
-  constexpr int BK = 128 / (int)sizeof(T);   // K granularity of the widest K-slice (TileS / TileL)
-  if (a.M <= 0 || a.N <= 0) return 0;
-  if (a.K <= 0 || a.K % BK != 0) return (int)hipErrorInvalidValue;
-  if (a.x3 && sizeof(T) != 4) return (int)hipErrorInvalidValue;   // split-bf16 splits fp32 operands
-  // LDS-DMA reads 16-B chunks: rows must start 16-B aligned
-  const size_t es = sizeof(T);
-  const size_t esw = a.w8 ? 1 : es;   // fp8 weights: ldw / bsW count bytes
-  if (a.w8 && (sizeof(T) != 2 || !a.wscale || a.N % 4 != 0 || a.K % 64 != 0 || a.batch > 1 || !aligned_to(a.wscale, 16)))
-    return (int)hipErrorInvalidValue;
-  if (!aligned_to(a.A, 16) || !aligned_to(a.W, 16) || (a.lda * es) % 16 || (a.ldw * esw) % 16 ||
-      (a.bsA * es) % 16 || (a.bsW * esw) % 16)
-    return (int)hipErrorInvalidValue;
-  if (a.splitk_ws) {   // underfilled grid: two deterministic passes (see splitk_plan)
-    const SplitPlan sp = splitk_plan(a, sizeof(T) == 2);
-    const long long MN = (long long)a.M * a.N;
-    const bool ok4 = (!a.bias || aligned_to(a.bias, 16)) && (!a.mul || (aligned_to(a.mul, 4 * es) && a.ldmul % 4 == 0)) &&
-                     (!a.res || (aligned_to(a.res, 16) && a.ldres % 4 == 0)) && (!a.out32 || (aligned_to(a.out32, 16) && a.ld32 % 4 == 0)) &&
-                     (!a.outT || (aligned_to(a.outT, 4 * es) && a.ldT % 4 == 0));
-    if (sp.S > 1 && ok4 && a.splitk_ws_bytes >= (size_t)sp.S * MN * sizeof(float) && aligned_to(a.splitk_ws, 16)) {
-      GemmArgs p1;
-      p1.A = a.A; p1.lda = a.lda; p1.W = a.W; p1.ldw = a.ldw; p1.M = a.M; p1.N = a.N; p1.K = sp.Ks;
-      if (a.kernel_id) *a.kernel_id = (a.x3 ? 23000 : 8000) + (a.act + 1) * 10;
-      p1.x3 = a.x3;   // the partial pass multiplies like the single pass
-      p1.tune = a.tune; p1.batch = sp.S; p1.bsA = sp.Ks; p1.bsW = sp.Ks; p1.out32 = a.splitk_ws; p1.ld32 = a.N; p1.bs32 = MN;
-      if (int e = launch_t<T>(p1, st)) return e;
-      const long long work = (long long)a.M * (a.N / 4);
-      hipLaunchKernelGGL(gemm_reduce_kernel<T>, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, a.splitk_ws, sp.S, MN, a.M,
-                         a.N, a.bias, a.act, reinterpret_cast<const T*>(a.mul), a.ldmul, a.res, a.ldres, a.out32, a.ld32,
-                         reinterpret_cast<T*>(a.outT), a.ldT, a.rs_ssq, a.rs_parts, a.rs_invk, a.rs_eps);
-      return (int)hipGetLastError();
-    }
-  }
-  if (a.grp_col && (sizeof(T) != 2 || a.w8 || a.a8 || a.act != ACT_NONE || a.mul || a.res || a.resT || a.outT || a.out8 || a.ssq_out || a.rs_ssq ||
-                    a.rb > 0 || !a.out32 || a.K % 64 != 0 || !gemm_grouped_ok(a.tune)))
-    return (int)hipErrorInvalidValue;
-  if (a.W2 && (sizeof(T) != 2 || a.w8 || a.a8 || a.mul || a.res || a.resT || a.out32 || a.out8 || a.ssq_out || (a.rs_ssq && !a.rs_sum) || a.rb > 0 || a.batch > 1 ||
-               a.grp_col || !a.outT || !a.A2 || a.K % 64 != 0 || a.N % 4 != 0 || !aligned_to(a.A2, 16) || !aligned_to(a.W2, 16) || (a.lda2 * es) % 16 ||
-               (a.ldw2 * es) % 16 || !gemm_dual_ok(a.tune, a.M, a.N)))
-    return (int)hipErrorInvalidValue;
+int launch_t(const GemmArgs& a, hipStream_t st);
+
+// underfilled grid: two deterministic passes (gemm_route.h: splitk_plan). The partial problem takes its own route.
+template <typename T>
+int launch_splitk(const GemmArgs& a, const SplitPlan& sp, hipStream_t st) {
+  const long long MN = (long long)a.M * a.N;
+  GemmArgs p1;
+  p1.A = a.A; p1.lda = a.lda; p1.W = a.W; p1.ldw = a.ldw; p1.M = a.M; p1.N = a.N; p1.K = sp.Ks;
+  p1.x3 = a.x3;   // the partial pass multiplies like the single pass
+  p1.tune = a.tune; p1.batch = sp.S; p1.bsA = sp.Ks; p1.bsW = sp.Ks; p1.out32 = a.splitk_ws; p1.ld32 = a.N; p1.bs32 = MN;
+  if (int e = launch_t<T>(p1, st)) return e;
+  const long long work = (long long)a.M * (a.N / 4);
+  hipLaunchKernelGGL(gemm_reduce_kernel<T>, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, a.splitk_ws, sp.S, MN, a.M,
+                     a.N, a.bias, a.act, reinterpret_cast<const T*>(a.mul), a.ldmul, a.res, a.ldres, a.out32, a.ld32,
+                     reinterpret_cast<T*>(a.outT), a.ldT, a.rs_ssq, a.rs_parts, a.rs_invk, a.rs_eps);
+  return (int)hipGetLastError();
+}
+
+GemmDev gemm_dev(const GemmArgs& a, const GemmRoute& r) {
   GemmDev d;
   d.grp_col = a.grp_col;
   d.A2 = a.A2; d.W2 = a.W2; d.lda2 = a.lda2; d.ldw2 = a.ldw2;
@@ -2381,168 +2223,51 @@ int launch_t(const GemmArgs& a, hipStream_t st) {
   d.bsA = a.bsA; d.bsW = a.bsW; d.bsBias = a.bsBias; d.bsMul = a.bsMul; d.bsRes = a.bsRes; d.bs32 = a.bs32; d.bsT = a.bsT;
   d.bias = a.bias; d.act = a.act; d.mul = a.mul; d.ldmul = a.ldmul; d.res = a.res; d.ldres = a.ldres;
   d.resT = a.resT; d.ldresT = a.ldresT;
-  if (a.resT && (a.res || a.batch > 1 || a.act != ACT_NONE)) return (int)hipErrorInvalidValue;
   d.out32 = a.out32; d.ld32 = a.ld32; d.outT = a.outT; d.ldT = a.ldT;
   d.rb = a.rb; d.s_hi = a.s_hi; d.s_lo = a.s_lo; d.ro = a.ro;
   d.hm_D = a.hm_D; d.hm_L = a.hm_L;
   d.outT_lo = a.outT_lo; d.ldT_lo = a.ldT_lo; d.split_n = a.split_n;
-  if (a.hm_D && (sizeof(T) != 2 || !a.outT || a.out32 || a.mul || a.res || a.resT || a.out8 || a.ssq_out || a.rb > 0 || a.batch > 1 || a.grp_col || a.W2 ||
-                 !gemm_headmajor_ok(a.tune, a.M, a.N, a.K, a.lda, a.ldw, a.hm_D, a.hm_L, a.a8)))
-    return (int)hipErrorInvalidValue;
   d.ssq_out = a.ssq_out; d.rs_ssq = a.rs_ssq; d.rs_parts = a.rs_parts; d.rs_invk = a.rs_invk; d.rs_eps = a.rs_eps;
   d.sum_out = a.sum_out; d.rs_sum = a.rs_sum; d.rs_c = a.rs_c;
-  // fused LayerNorm: partial sums ride with the partial sums of squares of an fp32-output producer; the consumers are the two GEGLU-pair forms
-  if (a.sum_out && (sizeof(T) != 2 || !a.ssq_out || !a.out32 || !gemm_lnfold_producer_ok(a.tune, a.M, a.N))) return (int)hipErrorInvalidValue;
-  if (a.rs_sum && (sizeof(T) != 2 || !a.rs_ssq || !a.rs_c || !(a.pair32 || a.W2) || !aligned_to(a.rs_c, 16))) return (int)hipErrorInvalidValue;
   d.wscale = a.w8 ? a.wscale : nullptr;
   d.ascale = a.a8 ? a.ascale : 1.0f;
   d.out8 = a.out8; d.ld8 = a.ld8; d.out8_inv = a.out8_inv;
-  if (a.ssq_out && ((!a.out32 && !a.outT) || a.batch > 1 || a.N % 32 != 0)) return (int)hipErrorInvalidValue;
-  if (a.rs_ssq && a.rs_parts <= 0) return (int)hipErrorInvalidValue;
   d.mtiles = d.ntiles = 0;
-  bool v = (a.N % 4 == 0);
-  if (a.bias) v = v && aligned_to(a.bias, 16) && (a.bsBias % 4 == 0);
-  if (a.mul) v = v && aligned_to(a.mul, 4 * es) && (a.ldmul % 4 == 0) && (a.bsMul % 4 == 0);
-  if (a.res) v = v && aligned_to(a.res, 16) && (a.ldres % 4 == 0) && (a.bsRes % 4 == 0);
-  if (a.resT) v = v && aligned_to(a.resT, 4 * es) && (a.ldresT % 4 == 0);
-  if (a.out32) v = v && aligned_to(a.out32, 16) && (a.ld32 % 4 == 0) && (a.bs32 % 4 == 0);
-  if (a.outT) v = v && aligned_to(a.outT, 4 * es) && (a.ldT % 4 == 0) && (a.bsT % 4 == 0);
-  if (a.w8 && !v) return (int)hipErrorInvalidValue;   // fp8 weights need the vector epilogue (16-byte aligned outputs)
-  // column-split output: the VECTOR epilogues of the one-tile-per-workgroup / resident / skinny kernels only (the scalar epilogue and the persistent
-  // kernels' epilogues do not know split_n: a launch that could reach them is refused, never mis-stored)
-  if (a.split_n && (sizeof(T) != 2 || !v || !a.outT || !a.outT_lo || a.out32 || a.out8 || a.mul || a.res || a.resT || a.ssq_out || a.hm_D || a.pair32 || a.W2 || a.grp_col ||
-                    a.batch > 1 || a.split_n <= 0 || a.split_n >= a.N || a.split_n % 128 != 0 || a.N % 8 != 0 || a.ldT_lo % 8 != 0 || !aligned_to(a.outT_lo, 16) ||
-                    a.w8 || a.a8 || gemm_splitk(a.tune)))
-    return (int)hipErrorInvalidValue;
-  d.wide8 = 0;
+  d.wide8 = r.wide8 ? 1 : 0;
+  return d;
+}
+
+// route (gemm_route.h), fill GemmDev, launch. A route that names an instantiation which does not exist is a bug: hipErrorInvalidValue.
+template <typename T>
+int launch_t(const GemmArgs& a, hipStream_t st) {
+  const GemmRoute r = gemm_route(a, sizeof(T) == 2, num_cu());
+  if (a.kernel_id && r.kernel_id) *a.kernel_id = r.kernel_id;
+  if (r.err || r.family == GF_NONE) return r.err;
+  if (r.family == GF_SPLITK) return launch_splitk<T>(a, r.split, st);
+  const GemmDev d = gemm_dev(a, r);
   if constexpr (sizeof(T) == 2) {
-    d.wide8 = (v && (a.outT || a.out8) && !a.out32 && a.N % 8 == 0 && a.ldT % 8 == 0 && a.bsT % 8 == 0 && aligned_to(a.outT, 16) &&
-               (!a.out8 || (a.ld8 % 8 == 0 && aligned_to(a.out8, 8))) &&
-               (!a.mul || (a.ldmul % 8 == 0 && a.bsMul % 8 == 0 && aligned_to(a.mul, 16))) &&
-               (!a.resT || (a.ldresT % 8 == 0 && aligned_to(a.resT, 16)))) ? 1 : 0;
-    // RMS partials without the fp32 stream exist only in the 8-column layout (statistics of the stored bf16 values)
-    if (a.ssq_out && !a.out32 && !d.wide8) return (int)hipErrorInvalidValue;
+    switch (r.family) {
+      case GF_PP: case GF_PP_F8: return launch_pp(d, a, r.epi, st);
+      case GF_PERSISTENT: return launch_persistent(d, a, r.epi, st);
+      case GF_WIDE: return launch_wide(d, a, r.epi, st);
+      case GF_Q4_256: return launch_q4<2>(d, a, r.epi, st);
+      case GF_Q4_128: return launch_q4<1>(d, a, r.epi, st);
+      case GF_TILE_L: return launch_tile<T, TileL, true>(d, a, r.vec, st);
+#ifndef VIMA_GEMM_LAB
+      case GF_SKINNY: case GF_SKINNY_DUAL: return launch_skinny(d, a, st);
+      case GF_RT32: case GF_RT64x32: case GF_RT64: case GF_RT32_DUAL: case GF_RT64_DUAL: return launch_resident(d, a, r.family, st);
+      case GF_TILE_XS: return launch_tile<T, TileXS, true>(d, a, r.vec, st);
+      case GF_TILE_64: return launch_tile<T, Tile64, true>(d, a, r.vec, st);
+      case GF_TILE_64x128: return launch_tile<T, Tile64x128, true>(d, a, r.vec, st);
+      case GF_TILE_128x64: return launch_tile<T, Tile128x64, true>(d, a, r.vec, st);
+#endif
+      default: break;
+    }
   }
 #ifndef VIMA_GEMM_LAB
-  if constexpr (sizeof(T) == 2) {
-    if (a.grp_col || a.W2) {
-      if (a.W2 && !v) return (int)hipErrorInvalidValue;
-      if (a.W2 && a.M <= 32 && gemm_skinny(a.tune)) {
-        const int e = launch_skinny(d, a, st);
-        if (e >= 0) return e;
-      }
-      const int e = launch_resident(d, a, 0, st);
-      return e >= 0 ? e : (int)hipErrorInvalidValue;
-    }
-    if (a.pair32) {   // GEGLU pair over block-interleaved weights: the 128x128 ring tile's pair epilogue (the caller asks gemm_pair_ok() first)
-      if (!v || a.w8 || a.a8 || a.act != ACT_GELU || a.mul || a.res || a.resT || a.out32 || a.out8 || a.ssq_out || (a.rs_ssq && !a.rs_sum) || a.rb > 0 ||
-          a.batch > 1 || a.hm_D || !a.outT || a.N % TileS::BN != 0 || a.K % 64 != 0 || a.ldT % 8 != 0 || !aligned_to(a.outT, 16) ||
-          !gemm_pair_ok(a.tune, a.M, a.N / 2, a.K))
-        return (int)hipErrorInvalidValue;
-      if (gemm_pair_large(a.tune, a.M, a.N / 2, a.K) && (long long)a.M * a.lda * 2 < (1LL << 32) && (long long)a.N * a.ldw * 2 < (1LL << 32)) {
-        d.wide8 = 1;
-        const int e = launch_pp(d, a, st);   // >= 160 full 256x256 tiles of the interleaved [M, 2 Nout] problem: the persistent kernel's pair epilogue
-        if (e >= 0) { if (a.kernel_id) *a.kernel_id = 1000 + (a.act + 1) * 10 + 6; return e; }
-      }
-      if (a.kernel_id) *a.kernel_id = 5000 + (a.act + 1) * 10;
-      return launch_tile<T, TileS, true>(d, a, v, st);
-    }
-  }
+  if (r.family == GF_TILE_S) return r.asm_lds ? launch_tile<T, TileS, true>(d, a, r.vec, st) : launch_tile<T, TileS, false>(d, a, r.vec, st);
 #endif
-  if (a.pair32) return (int)hipErrorInvalidValue;
-  if constexpr (sizeof(T) == 2) {
-    // TileL when the 256x256 grid still fills the chip (>= ~1 workgroup per CU) and padding waste is small
-    const long long mt = (a.M + 255) / 256, nt = (a.N + 255) / 256;
-    const double waste = (double)(mt * 256) * (double)(nt * 256) / ((double)a.M * (double)a.N);
-    bool large = v && (mt * nt * (a.batch > 0 ? a.batch : 1) >= 160) && waste < 1.15;   // measured: 192 tiles of 256x256 beat 768 of 128x128 by 10-28 %
-    if (gemm_tile(a.tune) == 1) large = false;
-    if (gemm_tile(a.tune) >= 2 && gemm_tile(a.tune) < 7) large = v;
-    if (gemm_tile(a.tune) >= 7) large = false;
-    if (a.split_n) large = false;   // after every override: the column-split output exists in the one-tile-per-workgroup / resident / skinny epilogues only
-    if (large && gemm_q4(a.tune) && gemm_tile(a.tune) == 0 && gemm_persist(a.tune) && gemm_raster(a.tune) == 0 && gemm_epi(a.tune)) {
-      // gemm_q4: 1 = the 256 x 384 tile wherever it fits, 2 = the 128 x 384 tile wherever it fits, 3 = the 128 x 384 tile where it needs fewer ROUNDS of the chip than
-      // the 256 x 256 tiling. A round of 128 x 384 tiles is 0.75 of a round of 256 x 256 tiles in FLOPs and measures ~0.8 of it in time (12 MFMAs per phase and barrier
-      // instead of 24); the margin keeps the choice away from ties. M = 16 384 (batch 32): N = 768 one round instead of one of 192 tiles, N = 1536 / 2304 2 / 3 rounds
-      // instead of 2 / 3 larger ones; the batch-256 shapes (M = 131 072, 81 920) never qualify. The choice depends on the SHAPE only, and the tile is bit-identical anyway.
-      int mode = gemm_q4(a.tune);
-      // 6 (the default since the end of round 6) = the 256 x 384 tile for GEMMs of at least 32 768 rows. Kernel for kernel the two tilings take the same time
-      // (power-bound: DESIGN.md 4.2c) -- but with the model's TWO streams the four-wave kernel's 7 % fewer busy cycles are left to whatever runs beside it:
-      // wall clock of the headline step 53.63 -> 52.89 ms, 1024-token prompt 109.8 -> 108.2, T = 8 65.6 -> 65.0, batch 128 27.85 -> 27.58 (alternating, same box:
-      // profiles/r06_q4_wall_clock.txt); below that size it loses (batch 32 +5 %, the env steps +1 %, VIMA-20M batch 32 +3 %), hence the row threshold.
-      if (mode == 6) mode = a.M >= 32768 ? 1 : 0;
-      if (mode == 4) mode = a.N >= 1536 ? 1 : 0;   // 4 / 5 (lab): the 256 x 384 tile for the wide-N GEMMs only / for N = 768 only
-      if (mode == 5) mode = a.N == 768 ? 1 : 0;
-      if (mode == 3) {
-        mode = 0;
-        if (a.M % 128 == 0 && a.N % 384 == 0 && a.M % 256 == 0 && a.N % 256 == 0) {
-          const long long ncu = num_cu();
-          const long long r_pp = ((long long)(a.M / 256) * (a.N / 256) + ncu - 1) / ncu;
-          const long long r_h = ((long long)(a.M / 128) * (a.N / 384) + ncu - 1) / ncu;
-          if (r_h * 80 <= r_pp * 93) mode = 2;
-        }
-      }
-      if (mode) {
-        const bool half = mode == 2;
-        const int e = half ? launch_q4<1>(d, a, st) : launch_q4<2>(d, a, st);
-        if (e >= 0) { if (a.kernel_id) *a.kernel_id = (half ? 20000 : 19000) + (a.act + 1) * 10 + (a.hm_D ? 5 : (a.resT ? 4 : 1)); return e; }
-      }
-    }
-    if (large && gemm_wide(a.tune) && gemm_tile(a.tune) == 0 && gemm_persist(a.tune) && gemm_raster(a.tune) == 0 && gemm_epi(a.tune)) {
-      const int e = launch_wide(d, a, st);
-      if (e >= 0) { if (a.kernel_id) *a.kernel_id = 3000 + (a.act + 1) * 10 + (a.resT ? 4 : 1); return e; }
-    }
-    if (large && (gemm_tile(a.tune) == 0 || gemm_tile(a.tune) == 2) && gemm_persist(a.tune) && a.batch <= 1 &&
-        a.K >= 2 * 64 && gemm_raster(a.tune) == 0 && gemm_epi(a.tune) &&
-        a.M % TileL::BM == 0 && a.N % TileL::BN == 0 && (long long)a.M * a.lda * 2 < (1LL << 32) &&
-        (long long)a.N * a.ldw * (long long)esw < (1LL << 32)) {
-      const int epi_id = a.hm_D ? 5 : (a.resT ? 4 : ((a.res || a.out32) ? 3 : (a.mul ? 2 : 1)));
-      if (gemm_pp(a.tune) || a.a8) {
-        const int e = launch_pp(d, a, st);
-        if (e >= 0) { if (a.kernel_id) *a.kernel_id = (a.a8 ? 9000 : 1000) + (a.act + 1) * 10 + epi_id; return e; }
-      }
-      if (a.a8) return (int)hipErrorInvalidValue;   // fp8 activations exist on the ping-pong kernel only
-      const int e = launch_persistent(d, a, st);
-      if (e >= 0) { if (a.kernel_id) *a.kernel_id = 2000 + (a.act + 1) * 10 + epi_id; return e; }
-    }
-    if (a.a8 || a.hm_D) return (int)hipErrorInvalidValue;   // (head-major output exists in the persistent kernels' epilogue only)
-    if (large) { if (a.kernel_id) *a.kernel_id = 4000 + (a.act + 1) * 10; return launch_tile<T, TileL, true>(d, a, v, st); }
-  }
-  if (a.a8 || a.hm_D) return (int)hipErrorInvalidValue;
-#ifdef VIMA_GEMM_LAB
   return (int)hipErrorInvalidValue;
-#else
-  if constexpr (sizeof(T) == 2) {
-    // Underfilled 128x128 grids (batch 1 .. 32: M = 8 .. 512) are bound by how fast ONE workgroup walks its K dimension
-    // (a 32-KiB slice per ~1400 clocks, most of the A tile being padding rows): smaller tiles move fewer bytes per slice
-    // and spread the problem over more CUs. Every tile shape accumulates K in the same order, so results do not depend
-    // on the choice.
-    const long long t128 = (long long)((a.M + 127) / 128) * ((a.N + 127) / 128) * (a.batch > 0 ? a.batch : 1);
-    {   // the same class with (almost) the whole K extent in flight (gemm_small.inc); bit-identical to the ring tiles
-      const int gt = gemm_tile(a.tune);
-      const int force = (gt >= 10 && gt <= 12) ? gt : 0;
-      if (v && gt == 0 && a.M <= 32 && gemm_small(a.tune) && gemm_resident(a.tune) && gemm_skinny(a.tune)) {   // at most 32 rows: K split over the waves
-        const int e = launch_skinny(d, a, st);
-        if (e >= 0) return e;
-      }
-      if (v && (force || (gt == 0 && gemm_small(a.tune) && gemm_resident(a.tune) && t128 < 128))) {
-        const int e = launch_resident(d, a, force, st);
-        if (e >= 0) return e;
-      }
-    }
-    if (v && gemm_tile(a.tune) == 0 && gemm_small(a.tune) && t128 < 128) {
-      if (a.kernel_id) *a.kernel_id = (a.M <= 32 ? 7000 : 6000) + (a.act + 1) * 10;
-      if (a.M <= 32) return launch_tile<T, TileXS, true>(d, a, v, st);
-      return launch_tile<T, Tile64, true>(d, a, v, st);
-    }
-    if (gemm_tile(a.tune) == 13 && v) return launch_tile<T, Tile64x128, true>(d, a, v, st);
-    if (gemm_tile(a.tune) == 14 && v) return launch_tile<T, Tile128x64, true>(d, a, v, st);
-    if (gemm_tile(a.tune) == 7 && v) { if (a.kernel_id) *a.kernel_id = 7000 + (a.act + 1) * 10; return launch_tile<T, TileXS, true>(d, a, v, st); }
-    if (gemm_tile(a.tune) == 8 && v) { if (a.kernel_id) *a.kernel_id = 6000 + (a.act + 1) * 10; return launch_tile<T, Tile64, true>(d, a, v, st); }
-  }
-  if (a.kernel_id) *a.kernel_id = (a.x3 ? 21000 : 5000) + (a.act + 1) * 10;
-  if (gemm_variant(a.tune) == 1 || a.w8) return launch_tile<T, TileS, true>(d, a, v, st);
-  return launch_tile<T, TileS, false>(d, a, v, st);
-#endif
 }
 
 }  // namespace
@@ -2574,80 +2299,15 @@ size_t gemm_splitk_bytes(const GemmArgs& a, bool is_bf16) {
 }
 int gemm_splitk_enabled(const Tuning* t) { return gemm_splitk(t); }
 int gemm_k_multiple(bool is_bf16) { return is_bf16 ? 64 : 32; }
-// GEGLU pair over block-interleaved weights (GemmArgs::pair32): for [M, Nout] outputs that would otherwise be two ring-tile launches --
-// neither the dual-accumulator resident form (small grids) nor the persistent 256x256 kernels (large ones)
-// the interleaved [M, 2 Nout] problem fills the chip with full 256x256 tiles: the pair runs on gemm_pp_kernel<ACT_GELU, 6>
-int gemm_pair_large(const Tuning* t, long long M, long long Nout, long long K) {
-#ifdef VIMA_GEMM_LAB
-  return 0;
-#else
-  if (M <= 0 || Nout <= 0 || M % 256 != 0 || Nout % 128 != 0 || K < 128 || (K / 64) % 2 != 0) return 0;
-  if (gemm_tile(t) != 0 || !gemm_persist(t) || !gemm_pp(t) || gemm_raster(t) != 0 || !gemm_epi(t) || gemm_wide(t) || gemm_variant(t) != 1) return 0;
-  return (M / 256) * (2 * Nout / 256) >= 160 ? 1 : 0;
-#endif
-}
-int gemm_pair_ok(const Tuning* t, long long M, long long Nout, long long K) {
-#ifdef VIMA_GEMM_LAB
-  return 0;
-#else
-  if (M <= 0 || Nout <= 0 || Nout % 64 != 0 || K < 64 || K % 64 != 0) return 0;
-  if (gemm_tile(t) != 0 || gemm_variant(t) != 1 || !gemm_epi(t) || gemm_raster(t) != 0) return 0;
-  if (gemm_dual_ok(t, (int)M, (int)Nout)) return 0;
-  if (gemm_pair_large(t, M, Nout, K)) return 1;
-  if (((M + 255) / 256) * ((Nout + 255) / 256) >= 160) return 0;   // `large` without the pair epilogue's shape conditions: the GELU GEMM takes the persistent kernel's gate epilogue
-  if (gemm_small(t) && ((M + 127) / 128) * ((Nout + 127) / 128) < 128) return 0;   // small grids: 64x64 ring tiles / resident kernel
-  return 1;
-#endif
-}
-// Fused-LayerNorm PRODUCER (GemmArgs::sum_out): the partial sums exist in the resident kernel's epilogue and in the ring tiles' LDS epilogue, not
-// in the persistent 256x256 kernels' -- i.e. for every [M, N] output that does not take the `large` path
-int gemm_lnfold_producer_ok(const Tuning* t, long long M, long long N) {
-#ifdef VIMA_GEMM_LAB
-  return 0;
-#else
-  if (M <= 0 || N <= 0 || N % 32 != 0) return 0;
-  const int gt = gemm_tile(t);
-  if (gt >= 2 && gt < 7) return 0;
-  if (gt == 0 && ((M + 255) / 256) * ((N + 255) / 256) >= 160) return 0;
-  return 1;
-#endif
-}
-int gemm_dual_ok(const Tuning* t, int M, int N) {
-  if (!gemm_grouped_ok(t) || M <= 0 || N <= 0 || N % 4 != 0) return 0;
-  if (M <= 32) return 1;
-  return (long long)((M + 63) / 64) * ((N + 63) / 64) <= gemm_res_maxwg(t) ? 1 : 0;
-}
-// Head-major output (GemmArgs::hm_D / hm_L) exists in the persistent 256x256 kernels' bf16-output epilogue: the problem must take that path
-// (same conditions as launch_t's: the large-tile rule, full tiles, the persistent / raster / epilogue knobs, 32-bit LDS-DMA offsets; fp8 operands: gemm_a8_ok),
-// a batch of hm_L rows must be whole tiles and a head a power of two >= 8 columns.
+// What callers ask before they build a form: each is a question about the route of a canonical problem (gemm_route.h, namespace route_q)
+int gemm_pair_large(const Tuning* t, long long M, long long Nout, long long K) { return route_q::pair_large(t, M, Nout, K, num_cu()); }
+int gemm_pair_ok(const Tuning* t, long long M, long long Nout, long long K) { return route_q::pair_ok(t, M, Nout, K, num_cu()); }
+int gemm_lnfold_producer_ok(const Tuning* t, long long M, long long N) { return route_q::lnfold_producer_ok(t, M, N, num_cu()); }
+int gemm_dual_ok(const Tuning* t, int M, int N) { return route_q::dual_ok(t, M, N, num_cu()); }
 int gemm_headmajor_ok(const Tuning* t, long long M, long long N, long long K, long long lda, long long ldw, int hm_D, int hm_L, int a8) {
-  if (hm_D < 8 || (hm_D & (hm_D - 1)) || hm_L <= 0 || hm_L % TileL::BM != 0 || M % hm_L != 0 || N % hm_D != 0) return 0;
-  if (gemm_wide(t)) return 0;   // the opt-in 256x384 kernel has its own epilogue
-  if (a8) return gemm_a8_ok(t, M, N, K, lda, ldw);
-  if (M <= 0 || N <= 0 || K < 128 || K % 64 != 0 || M % TileL::BM != 0 || N % TileL::BN != 0 || N % 8 != 0 || lda % 8 != 0 || ldw % 8 != 0) return 0;
-  const int gt = gemm_tile(t);
-  if (!(gt == 0 || gt == 2) || !gemm_persist(t) || gemm_raster(t) != 0 || !gemm_epi(t)) return 0;
-  if (gt == 0 && (M / TileL::BM) * (N / TileL::BN) < 160) return 0;
-  if (M * lda * 2 >= (1LL << 32) || N * ldw * 2 >= (1LL << 32)) return 0;
-  return 1;
+  return route_q::headmajor_ok(t, M, N, K, lda, ldw, hm_D, hm_L, a8, num_cu());
 }
-// fp8 ACTIVATIONS (GemmArgs::a8) exist on gemm_pp_kernel<.., F8> only: mirrors, condition for condition, the path launch_t takes
-// for an a8 problem (anything else makes launch_gemm return hipErrorInvalidValue), so that callers can decide BEFORE quantising.
-int gemm_a8_ok(const Tuning* t, long long M, long long N, long long K, long long lda, long long ldw) {
-  if (M <= 0 || N <= 0 || K < 256 || K % 256 != 0 || M % TileL::BM != 0 || N % TileL::BN != 0) return 0;
-  if (N % 8 != 0 || lda % 16 != 0 || ldw % 16 != 0) return 0;
-  const int gt = gemm_tile(t);
-  if (!(gt == 0 || gt == 2) || !gemm_persist(t) || gemm_raster(t) != 0 || !gemm_epi(t)) return 0;
-  if (gt == 0 && (M / TileL::BM) * (N / TileL::BN) < 160) return 0;        // `large`: the 256x256 grid fills the chip
-  if (M * lda * 2 >= (1LL << 32) || N * ldw >= (1LL << 32)) return 0;      // 32-bit LDS-DMA offsets (launch_t prices A at 2 bytes)
-  return 1;
-}
-int gemm_grouped_ok(const Tuning* t) {
-#ifdef VIMA_GEMM_LAB
-  return 0;
-#else
-  return gemm_tile(t) == 0 && gemm_small(t) && gemm_resident(t);
-#endif
-}
+int gemm_a8_ok(const Tuning* t, long long M, long long N, long long K, long long lda, long long ldw) { return route_q::a8_ok(t, M, N, K, lda, ldw, num_cu()); }
+int gemm_grouped_ok(const Tuning* t) { return route_q::grouped_ok(t, num_cu()); }
 
 }  // namespace vima
