@@ -78,7 +78,7 @@ def fake_quant_state_dict(sd: dict, t5_fused_rms: bool = True) -> dict:
 
 
 # ---- precision "fp8": fp8 e4m3 ACTIVATIONS into the T5 stack's four GEMMs per layer, one static dequantisation scale per
-# (layer, site) -- sites: 0 stream before qkv, 1 attention context, 2 stream before wi, 3 ReLU hidden (vima_api.hip t5_layer_fp8).
+# (layer, site) -- sites: 0 stream before qkv, 1 attention context, 2 stream before wi, 3 ReLU hidden (vima_api.hip t5_layer_fused with scales).
 def fq_act(t: torch.Tensor, scale: float) -> torch.Tensor:
     """dequant(e4m3(t / scale)), saturating at 448, round to nearest even: what the fp8 GEMM multiplies with."""
     return (t / scale).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).float() * scale
@@ -87,7 +87,7 @@ def fq_act(t: torch.Tensor, scale: float) -> torch.Tensor:
 def make_fp8_act_oracle(sd: dict, act_scales: torch.Tensor, vit_scales: torch.Tensor | None = None, kv_scale: float | None = None, **ctor):
     """OraclePolicy on fake-quantised weights whose T5 stack also fake-quantises the four GEMM inputs of every layer with the
     given scales [n_layers, 4]. The RMSNorm statistics come from the UNquantised stream (the library takes them from the bf16
-    stream's partial sums, vima_api.hip t5_layer_fp8), only the GEMM operand is quantised. `vit_scales` [4, 4]: the same for the
+    stream's partial sums, vima_api.hip t5_layer_fused with scales), only the GEMM operand is quantised. `vit_scales` [4, 4]: the same for the
     ViT while the attribute `fq_vit` is True (the library quantises only chunks of >= 13824 crops: the prompt's, not one
     observation's); `kv_scale`: the prompt entering the decoder's key_value projections."""
     from .vima_oracle import OraclePolicy, FMIN, _lin, t5_relative_position_bucket

@@ -29,9 +29,10 @@ import sys
 def digests(path):
     src = open(path).read()
     out = {}
-    for m in re.finditer(r"^(_Z\S+):\s*;? ?@?.*$", src, flags=re.M):
+    c_kernels = set(re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", src, flags=re.M))   # extern "C" kernels have no _Z name (widen_kernel of vima_api.hip)
+    for m in re.finditer(r"^([A-Za-z_]\S*):\s*;? ?@?.*$", src, flags=re.M):
         end = src.find(".Lfunc_end", m.end())
-        if end < 0:
+        if end < 0 or not (m.group(1).startswith("_Z") or m.group(1) in c_kernels):
             continue
         body = []
         for ln in src[m.end():end].split("\n"):

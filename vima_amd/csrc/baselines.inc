@@ -36,35 +36,15 @@ int rgb_vit(Run& R, const uint8_t* const rgb[2], int per_view, void** y_out) {
   R.linear(P, Kc, h->vit.conv, M * NP, ACT_NONE, nullptr, 0, nullptr, 0, pre, kVitW, nullptr, 0);           // conv1 (vit.py:120, :306)
   OTHER(R, launch_vit_embed_rect(pre, h->vit.cls, h->vit.pos, h->vit.lnpre_g, h->vit.lnpre_b, x, xT, M, S, NP, h->bf16, R.st),
         "vit_embed_rect");
-  const int rows = M * S;
-  auto norm = [&](long long ldin, const float* g, const float* bb, int nrows, void* out) {
-    return sT ? R.lnT(xT, ldin, g, bb, 1e-5f, 0, nrows, kVitW, nullptr, out) : R.ln(x, ldin, g, bb, 1e-5f, 0, nrows, kVitW, nullptr, out);
-  };
-  auto residual = [&](const void* A, int lda, const Lin& L) {   // stream += A . W^T + bias, in place
-    if (!sT) return R.linear(A, lda, L, rows, ACT_NONE, nullptr, 0, x, kVitW, x, kVitW, nullptr, 0);
-    GemmArgs g;
-    g.A = A; g.lda = lda; R.setW(g, L); g.M = rows; g.N = L.N; g.K = L.K; g.bias = L.b;
-    g.resT = xT; g.ldresT = kVitW; g.outT = xT; g.ldT = kVitW;
-    return R.gemm(g);
-  };
-  for (int j = 0; j < kVitLayers; ++j) {   // ResidualAttentionBlock (vit.py:199-236)
-    auto& B = h->vit.blk[j];
-    norm(kVitW, B.ln1g, B.ln1b, rows, hT);
-    R.linear(hT, kVitW, B.in_proj, rows, ACT_NONE, nullptr, 0, nullptr, 0, nullptr, 0, qkv, 3 * kVitW);
-    // nn.MultiheadAttention(768, 24) over the S (8 or 9) tokens of a frame: no mask, 1/sqrt(32) -- the per-(frame, query, head) register kernel of the object-crop ViT
-    // (rounds 1-5 ran the exact generic attention kernel here: 261 us per launch for 191 MB of q|k|v)
-    R.prof_begin(1, 4.0 * M * kVitHeads * (double)S * S * 32);
-    const int ea = launch_vit_attn(qkv, att, M, S, kVitW, kVitHeads, h->bf16, R.st);
-    R.prof_end();
-    R.other(ea, "vit_attn");
-    residual(att, kVitW, B.out_proj);
-    norm(kVitW, B.ln2g, B.ln2b, rows, hT);
-    R.linear(hT, kVitW, B.fc, rows, ACT_QUICKGELU, nullptr, 0, nullptr, 0, nullptr, 0, u, 4 * kVitW);
-    residual(u, 4 * kVitW, B.proj);
+  // the blocks of the object-crop ViT over the S (8 or 9) tokens of a frame (rounds 1-5 ran the exact generic attention kernel here: 261 us per launch for 191 MB of q|k|v)
+  VitBuf vb{P, pre, x, hT, qkv, att, u, y, xT, nullptr};
+  for (int j = 0; j < kVitLayers; ++j) {
+    vit_block(R, h->vit.blk[j], M, S, vb, false, nullptr, nullptr);
     if (R.err) return R.err;
   }
-  if (cls) norm((long long)S * kVitW, h->vit.lnpost_g, h->vit.lnpost_b, M, y);       // x[:, 0, :] (vit.py:326)
-  else norm(kVitW, h->vit.lnpost_g, h->vit.lnpost_b, rows, y);                       // every token (vit.py:132)
+  const long long ldp = cls ? (long long)S * kVitW : kVitW;   // x[:, 0, :] (vit.py:326) / every token (vit.py:132)
+  if (sT) R.lnT(xT, ldp, h->vit.lnpost_g, h->vit.lnpost_b, 1e-5f, 0, cls ? M : M * S, kVitW, nullptr, y);
+  else R.ln(x, ldp, h->vit.lnpost_g, h->vit.lnpost_b, 1e-5f, 0, cls ? M : M * S, kVitW, nullptr, y);
   *y_out = y;
   return R.err;
 }

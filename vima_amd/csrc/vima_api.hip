@@ -168,6 +168,17 @@ struct Arena {          // stream-ordered bump allocator; chunks are only releas
   }
 };
 
+// precision "fp8": one group of activation sites with static e4m3 dequantisation scales (headroom x max |x| of the calibrating pass / 448). The group's first
+// eligible pass runs on operand-type activations and records max |x| per site (cal_begin .. cal_freeze, below the handle); later passes take the scales.
+struct Fp8Cal {
+  const char* group;
+  int sites;
+  bool ready = false;
+  std::vector<float> scale;   // [sites], valid while ready
+  float* amax = nullptr;      // device [sites], allocated by the first calibrating pass
+};
+enum { CAL_T5 = 0, CAL_VIT = 1, CAL_KV = 2 };
+
 struct ProfRec { int cls; hipEvent_t a, b; double flops; double bytes; int kid = 0; int M = 0, N = 0, K = 0; };   // kid: GemmArgs::kernel_id of a GEMM launch (M, N, K: its shape)
 
 }  // namespace
@@ -185,15 +196,10 @@ struct VimaHandle {
   bool a8 = false;
   // the same for the ViT (chunks of >= 13824 crops: sites per block 0 ln_1 output, 1 attention output, 2 ln_2 output, 3 QuickGELU
   // hidden) and for the decoder's prompt K/V projection (one site: prompt + position embedding)
-  bool vit8_ready = false, kv8_ready = false;
-  std::vector<float> vit8_scale, kv8_scale;
-  float *vit8_amax = nullptr, *kv8_amax = nullptr;
-  bool fp8_ready = false;
+  Fp8Cal cal8[3] = {{"T5", kT5Layers * 4}, {"ViT", kVitLayers * 4}, {"prompt K/V", 1}};   // CAL_T5, CAL_VIT, CAL_KV: the group numbers of vima_fp8_act_scales
   int fp8_headroom_pct = 125;        // option "fp8_headroom_pct": a site's scale = headroom x (max |x| of the calibrating batch) / 448, so that a later
                                      // activation up to `headroom` x larger than anything the calibrating batch held still maps below the e4m3 maximum
                                      // instead of saturating (e4m3 is a floating-point format: headroom costs no relative precision above its subnormals)
-  std::vector<float> fp8_scale;      // [kT5Layers * 4] dequantisation scales (headroom * amax / 448)
-  float* fp8_amax = nullptr;         // device, [kT5Layers * 4]
   bool finalized = false;
   int attn_impl = 1;
   Tuning tune;              // GEMM / attention kernel-selection knobs of THIS handle (travel with every launch)
@@ -312,6 +318,27 @@ struct VimaHandle {
 };
 
 namespace {
+
+// ------------------------------------------------------------------------------------------------ fp8 calibration (Fp8Cal)
+// Begin a calibrating pass: the group's max |x| slots (allocated once) are zeroed on the stream; the pass then runs launch_amax into them.
+int cal_begin(VimaHandle* h, Fp8Cal& c, hipStream_t st) {
+  if (!c.amax) {
+    HIPCK(hipMalloc((void**)&c.amax, c.sites * sizeof(float)));
+    h->owned.push_back(c.amax);
+  }
+  HIPCK(hipMemsetAsync(c.amax, 0, c.sites * sizeof(float), st));
+  return 0;
+}
+// Freeze: read the maxima back and turn them into scales (a dead site gets 1). A refused (non-finite) calibration leaves the group not ready and returns the error.
+int cal_freeze(VimaHandle* h, Fp8Cal& c, hipStream_t st) {
+  std::vector<float> am(c.sites);
+  HIPCK(hipMemcpyAsync(am.data(), c.amax, am.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIPCK(hipStreamSynchronize(st));
+  if (int e = fp8_scales_from_amax(am, h->fp8_headroom_pct, c.group, c.scale)) return e;
+  c.ready = true;
+  ++h->state_gen;
+  return 0;
+}
 
 // ------------------------------------------------------------------------------------------------ weight packing
 uint16_t h_f2bf(float f) {
@@ -747,6 +774,10 @@ int pack_all(VimaHandle* h) {
 }
 
 // ------------------------------------------------------------------------------------------------ launch helpers
+// A GEMM input or output of the encoder stacks (T5, ViT, prompt K/V projection), described once: the operand-type buffer and its leading dimension, where the
+// stage runs fp8 activations its e4m3 copy with the site's dequantisation scale (s8 > 0), and for a residual stream kept in fp32 that buffer (same ld).
+struct Opnd { void* p = nullptr; int ld = 0; void* p8 = nullptr; float s8 = 0.f; float* p32 = nullptr; };
+
 struct Run {
   VimaHandle* h;
   hipStream_t st;
@@ -828,6 +859,27 @@ struct Run {
     a.bias = L.b; a.act = act; a.mul = mul; a.ldmul = ldmul; a.res = res; a.ldres = ldres;
     a.out32 = out32; a.ld32 = ld32; a.outT = outT; a.ldT = ldT;
     return gemm(a);
+  }
+  // The same over operands (the encoder stacks): out = act(rs . in . L[row0 .. row0 + N)^T + b) [+ res], M rows. fp8 travels with the operand: an input with a
+  // scale is read from its e4m3 copy, an output with a scale also gets (or, without p, only gets) one. res: the residual stream, fp32 if it has p32, else operand
+  // type. rs / rs_parts: row sums of squares of the T5 RMSNorm folded into L (GemmArgs::rs_ssq); ssq_out: the same statistics of the output, for the next norm.
+  GemmArgs linear_args(const Opnd& in, const Lin& L, int row0, int N, int M, int act, const Opnd* res, const Opnd& out, const float* rs = nullptr,
+                    int rs_parts = 0, float* ssq_out = nullptr) const {
+    GemmArgs a;
+    if (in.s8 > 0.f) { a.A = in.p8; a.a8 = 1; a.ascale = in.s8; }
+    else a.A = in.p;
+    a.lda = in.ld; setW(a, L, row0); a.M = M; a.N = N; a.K = L.K; a.bias = L.b ? L.b + row0 : nullptr; a.act = act;
+    if (res && res->p32) { a.res = res->p32; a.ldres = res->ld; }
+    else if (res) { a.resT = res->p; a.ldresT = res->ld; }
+    a.out32 = out.p32; a.ld32 = out.ld; a.outT = out.p; a.ldT = out.ld;
+    if (out.s8 > 0.f) { a.out8 = out.p8; a.ld8 = out.ld; a.out8_inv = 1.0f / out.s8; }
+    a.rs_ssq = rs; a.rs_parts = rs_parts; a.rs_invk = 1.0f / (float)L.K; a.rs_eps = 1e-6f;
+    a.ssq_out = ssq_out;
+    return a;
+  }
+  int linear(const Opnd& in, const Lin& L, int row0, int N, int M, int act, const Opnd* res, const Opnd& out, const float* rs = nullptr, int rs_parts = 0,
+             float* ssq_out = nullptr) {
+    return gemm(linear_args(in, L, row0, N, M, act, res, out, rs, rs_parts, ssq_out));
   }
   // u = GELU(A1 . L1^T + b1) * bf16(A2 . Lg^T): the value / gate pair of a GEGLU (components.py:31-33, 221-226). ONE dual-accumulator
   // launch where the library has one for this shape (bf16 weights, underfilled grid: batch <= ~32), else the gate GEMM into `g` followed
@@ -941,6 +993,54 @@ int join_aux(Run& R) {
 
 struct VitBuf { void* P; float* pre; float* x; void *hT, *qkv, *att, *u, *y; void *xT, *cT; void *h8 = nullptr, *att8 = nullptr, *u8 = nullptr; };   // xT / cT: stream in the operand type; *8: fp8 operands (precision "fp8")
 
+// One ResidualAttentionBlock (vit.py:199-236) over M images of S tokens, for the object-crop ViT (vit_chunk) and the baselines' whole-frame ViT (rgb_vit):
+//   ln_1 -> in_proj -> attention -> out_proj (+ stream) -> ln_2 -> fc (QuickGELU) -> proj (+ stream)
+// on the stream in the operand type (b.xT, option stream_T) or in fp32 (b.x). sc: the block's four fp8 scales (null: operand-type activations): the LayerNorms and
+// the attention then write e4m3 only, fc writes its hidden in e4m3 only. amax: the block's four max |x| slots (null: not calibrating).
+// cls_only: the last block when only ln_post's row is wanted (vit.py:186): K / V of all rows from in_proj rows [W, 3W), Q of the cls rows (stride S W), and everything
+// behind the attention on M rows, the residual read at stride S W and written compact to b.cT / b.pre (identical values for that row; the others are never read).
+void vit_block(Run& R, const VimaHandle::VitBlock& B, int M, int S, const VitBuf& b, bool cls_only, const float* sc, float* amax) {
+  VimaHandle* h = R.h;
+  constexpr int W = kVitW;
+  const bool sT = h->stream_T != 0;
+  const int rows = M * S, n = cls_only ? M : rows;   // n: rows behind the attention
+  auto s8 = [&](int site) { return sc ? sc[site] : 0.f; };
+  const Opnd x{sT ? b.xT : nullptr, cls_only ? S * W : W, nullptr, 0.f, sT ? nullptr : b.x};                           // the stream as the residual GEMMs read it
+  const Opnd xo = cls_only ? Opnd{sT ? b.cT : nullptr, W, nullptr, 0.f, sT ? nullptr : b.pre} : x;                      // ... and as they write it
+  const Opnd h1{b.hT, W, b.h8, s8(0)}, att{sc ? nullptr : b.att, W, b.att8, s8(1)}, h2{b.hT, W, b.h8, s8(2)}, u{sc ? nullptr : b.u, 4 * W, b.u8, s8(3)};
+  auto norm = [&](const Opnd& in, long long ldin, const float* g, const float* bb, int nrows, const Opnd& out) {
+    if (in.p32) return R.ln(in.p32, ldin, g, bb, 1e-5f, 0, nrows, W, nullptr, out.p);
+    if (out.s8 > 0.f) return R.lnT(in.p, ldin, g, bb, 1e-5f, 0, nrows, W, nullptr, nullptr, out.p8, 1.0f / out.s8);   // the bf16 stream straight to e4m3
+    return R.lnT(in.p, ldin, g, bb, 1e-5f, 0, nrows, W, nullptr, out.p);
+  };
+  auto cal = [&](int site, const void* t, long long nrows, int cols) {
+    if (amax) OTHER(R, launch_amax(t, cols, nrows, cols, amax + site, R.st), "amax");
+  };
+  norm(x, W, B.ln1g, B.ln1b, rows, h1);
+  cal(0, b.hT, rows, W);
+  int e;
+  if (!cls_only) {
+    R.linear(h1, B.in_proj, 0, 3 * W, rows, ACT_NONE, nullptr, Opnd{b.qkv, 3 * W});
+    // nn.MultiheadAttention(768, 24) over the S tokens of an image: no mask, 1/sqrt(32) -- the per-(image, query, head) register kernel
+    R.prof_begin(1, 4.0 * M * kVitHeads * (double)S * S * 32);
+    e = launch_vit_attn(b.qkv, att.p, M, S, W, kVitHeads, h->bf16, R.st, sc ? att.p8 : nullptr, sc ? 1.0f / att.s8 : 1.0f);
+  } else {
+    R.linear(h1, B.in_proj, W, 2 * W, rows, ACT_NONE, nullptr, Opnd{b.qkv, 2 * W});                         // K, V of all S tokens
+    R.linear(Opnd{h1.p, S * W, h1.p8, h1.s8}, B.in_proj, 0, W, M, ACT_NONE, nullptr, Opnd{b.y, W});         // Q of the cls token: A rows strided by S tokens
+    R.prof_begin(1, 4.0 * M * kVitHeads * (double)S * 32);
+    e = launch_vit_attn_cls(b.y, b.qkv, att.p, M, S, W, kVitHeads, h->bf16, R.st, sc ? att.p8 : nullptr, sc ? 1.0f / att.s8 : 1.0f);
+  }
+  R.prof_end();
+  R.other(e, cls_only ? "vit_attn_cls" : "vit_attn");
+  cal(1, b.att, n, W);
+  R.linear(att, B.out_proj, 0, W, n, ACT_NONE, &x, xo);   // stream += attention (cls_only: xc = x_cls + attention)
+  norm(xo, W, B.ln2g, B.ln2b, n, h2);
+  cal(2, b.hT, n, W);
+  R.linear(h2, B.fc, 0, 4 * W, n, ACT_QUICKGELU, nullptr, u);
+  cal(3, b.u, n, 4 * W);
+  R.linear(u, B.proj, 0, W, n, ACT_NONE, &xo, xo);
+}
+
 // ViT (vit.py:171-191) on internal crop rows [r0, r0+mc) -> cat[r0.., 0:768]
 // f8mode 0: operand-type activations; 1: the same + max |x| of every fp8 site into amax[block * 4 + site] (calibration);
 // 2: fp8 e4m3 activations into the 16 large GEMMs with the scales sc[block * 4 + site] (needs stream_T and a chunk whose GEMM
@@ -965,121 +1065,14 @@ void vit_chunk(Run& R, const uint8_t* const crops[2], int per_view, int r0, int 
   const bool sT = h->stream_T != 0;   // residual stream carried in the operand type (see t5_layer_fused)
   OTHER(R, launch_vit_embed(b.pre, h->vit.cls, h->vit.pos, h->vit.lnpre_g, h->vit.lnpre_b, sT ? nullptr : b.x, sT ? b.xT : nullptr, mc,
                             h->bf16, R.st), "vit_embed");
-  const int rows = mc * 5;
+  // the last block computes everything behind its K/V projection for the cls token only (option vit_prune_last) and leaves that row compact in b.cT / b.pre
   const bool prune = h->vit_prune_last != 0;
-  float* x = b.x;
-  // y = x + A W^T + bias on the stream: fp32 (x in place) or operand type (xT in place)
-  auto residual = [&](const void* A, int lda, const Lin& L, int M, const float* res32, int ldres, float* out32, const void* resT,
-                      int ldresT, void* outT, int ldo) {
-    GemmArgs g;
-    g.A = A; g.lda = lda; R.setW(g, L); g.M = M; g.N = L.N; g.K = L.K; g.bias = L.b;
-    if (sT) { g.resT = resT; g.ldresT = ldresT; g.outT = outT; g.ldT = ldo; }
-    else { g.res = res32; g.ldres = ldres; g.out32 = out32; g.ld32 = ldo; }
-    return R.gemm(g);
-  };
-  auto norm = [&](const float* in32, const void* inT, long long ldin, const float* g, const float* bb, int M, void* out) {
-    return sT ? R.lnT(inT, ldin, g, bb, 1e-5f, 0, M, kVitW, nullptr, out) : R.ln(in32, ldin, g, bb, 1e-5f, 0, M, kVitW, nullptr, out);
-  };
-  auto cal = [&](int j, int site, const void* t, long long nrows, int cols) {   // (the pad crops are zero images: real activations, inside the valid rows' range)
-    if (f8mode == 1) OTHER(R, launch_amax(t, cols, nrows, cols, amax + j * 4 + site, R.st), "amax");
-  };
-  // fp8 forms: LayerNorm of the bf16 stream straight to e4m3, GEMM with e4m3 A (and fp8 weights) -> bf16 / stream / e4m3 output
-  auto norm8 = [&](const void* inT, long long ldin, const float* g, const float* bb, int M, float s) {
-    return R.lnT(inT, ldin, g, bb, 1e-5f, 0, M, kVitW, nullptr, nullptr, b.h8, 1.0f / s);
-  };
-  auto gemm8 = [&](const void* A8, int lda, float ascale, const Lin& L, int row0, int N, int M, int act, const void* resT, int ldresT, void* outT,
-                   int ldT, void* out8, int ld8, float oscale) {
-    GemmArgs g;
-    g.A = A8; g.lda = lda; g.a8 = 1; g.ascale = ascale; R.setW(g, L, row0); g.M = M; g.N = N; g.K = L.K; g.bias = L.b ? L.b + row0 : nullptr;
-    g.act = act; g.resT = resT; g.ldresT = ldresT; g.outT = outT; g.ldT = ldT;
-    if (out8) { g.out8 = out8; g.ld8 = ld8; g.out8_inv = 1.0f / oscale; }
-    return R.gemm(g);
-  };
-  if (f8mode == 2) {
-    for (int j = 0; j < kVitLayers - (prune ? 1 : 0); ++j) {
-      auto& B = h->vit.blk[j];
-      const float* s = sc + j * 4;
-      norm8(b.xT, kVitW, B.ln1g, B.ln1b, rows, s[0]);
-      gemm8(b.h8, kVitW, s[0], B.in_proj, 0, 3 * kVitW, rows, ACT_NONE, nullptr, 0, b.qkv, 3 * kVitW, nullptr, 0, 0.f);
-      R.prof_begin(1, 4.0 * mc * kVitHeads * 25.0 * 32);
-      int e = launch_vit_attn(b.qkv, nullptr, mc, 5, kVitW, kVitHeads, true, R.st, b.att8, 1.0f / s[1]);
-      R.prof_end();
-      R.other(e, "vit_attn");
-      gemm8(b.att8, kVitW, s[1], B.out_proj, 0, kVitW, rows, ACT_NONE, b.xT, kVitW, b.xT, kVitW, nullptr, 0, 0.f);
-      norm8(b.xT, kVitW, B.ln2g, B.ln2b, rows, s[2]);
-      gemm8(b.h8, kVitW, s[2], B.fc, 0, 4 * kVitW, rows, ACT_QUICKGELU, nullptr, 0, nullptr, 4 * kVitW, b.u8, 4 * kVitW, s[3]);
-      gemm8(b.u8, 4 * kVitW, s[3], B.proj, 0, kVitW, rows, ACT_NONE, b.xT, kVitW, b.xT, kVitW, nullptr, 0, 0.f);
-    }
-  } else
-  for (int j = 0; j < kVitLayers - (prune ? 1 : 0); ++j) {
-    auto& B = h->vit.blk[j];
-    norm(x, b.xT, kVitW, B.ln1g, B.ln1b, rows, b.hT);
-    cal(j, 0, b.hT, rows, kVitW);
-    R.linear(b.hT, kVitW, B.in_proj, rows, ACT_NONE, nullptr, 0, nullptr, 0, nullptr, 0, b.qkv, 3 * kVitW);
-    R.prof_begin(1, 4.0 * mc * kVitHeads * 25.0 * 32);
-    int e = launch_vit_attn(b.qkv, b.att, mc, 5, kVitW, kVitHeads, h->bf16, R.st);
-    R.prof_end();
-    R.other(e, "vit_attn");
-    cal(j, 1, b.att, rows, kVitW);
-    residual(b.att, kVitW, B.out_proj, rows, x, kVitW, x, b.xT, kVitW, b.xT, kVitW);
-    norm(x, b.xT, kVitW, B.ln2g, B.ln2b, rows, b.hT);
-    cal(j, 2, b.hT, rows, kVitW);
-    R.linear(b.hT, kVitW, B.fc, rows, ACT_QUICKGELU, nullptr, 0, nullptr, 0, nullptr, 0, b.u, 4 * kVitW);
-    cal(j, 3, b.u, rows, 4 * kVitW);
-    residual(b.u, 4 * kVitW, B.proj, rows, x, kVitW, x, b.xT, kVitW, b.xT, kVitW);
-  }
-  const float* xpost = x;        // rows ln_post reads (cls token of every crop)
-  const void* xpostT = b.xT;
-  long long ld_post = 5 * kVitW;
-  if (prune && f8mode == 2) {   // the cls-only last block with fp8 activations
-    auto& B = h->vit.blk[kVitLayers - 1];
-    const float* s = sc + (kVitLayers - 1) * 4;
-    norm8(b.xT, kVitW, B.ln1g, B.ln1b, rows, s[0]);
-    gemm8(b.h8, kVitW, s[0], B.in_proj, kVitW, 2 * kVitW, rows, ACT_NONE, nullptr, 0, b.qkv, 2 * kVitW, nullptr, 0, 0.f);      // K, V of all 5 tokens
-    gemm8(b.h8, 5 * kVitW, s[0], B.in_proj, 0, kVitW, mc, ACT_NONE, nullptr, 0, b.y, kVitW, nullptr, 0, 0.f);                   // Q of the cls token
-    R.prof_begin(1, 4.0 * mc * kVitHeads * 5.0 * 32);
-    int e = launch_vit_attn_cls(b.y, b.qkv, nullptr, mc, 5, kVitW, kVitHeads, true, R.st, b.att8, 1.0f / s[1]);
-    R.prof_end();
-    R.other(e, "vit_attn_cls");
-    gemm8(b.att8, kVitW, s[1], B.out_proj, 0, kVitW, mc, ACT_NONE, b.xT, 5 * kVitW, b.cT, kVitW, nullptr, 0, 0.f);             // xc = x_cls + attn
-    norm8(b.cT, kVitW, B.ln2g, B.ln2b, mc, s[2]);
-    gemm8(b.h8, kVitW, s[2], B.fc, 0, 4 * kVitW, mc, ACT_QUICKGELU, nullptr, 0, nullptr, 4 * kVitW, b.u8, 4 * kVitW, s[3]);
-    gemm8(b.u8, 4 * kVitW, s[3], B.proj, 0, kVitW, mc, ACT_NONE, b.cT, kVitW, b.cT, kVitW, nullptr, 0, 0.f);
-    xpost = b.pre;
-    xpostT = b.cT;
-    ld_post = kVitW;
-  } else if (prune) {
-    // Last block: ln_post only reads the cls row (vit.py:186), so everything after the K/V projection is computed
-    // for the cls token only (identical values for that row; the other 4 rows of the block output are never read).
-    auto& B = h->vit.blk[kVitLayers - 1];
-    constexpr int jl = kVitLayers - 1;
-    norm(x, b.xT, kVitW, B.ln1g, B.ln1b, rows, b.hT);
-    cal(jl, 0, b.hT, rows, kVitW);
-    GemmArgs kvg;   // K,V of all 5 tokens: in_proj rows [W, 3W)
-    kvg.A = b.hT; kvg.lda = kVitW; R.setW(kvg, B.in_proj, kVitW);
-    kvg.M = rows; kvg.N = 2 * kVitW; kvg.K = kVitW; kvg.bias = B.in_proj.b + kVitW; kvg.outT = b.qkv; kvg.ldT = 2 * kVitW;
-    R.gemm(kvg);
-    GemmArgs qg;    // Q of the cls token only: in_proj rows [0, W), A rows strided by 5 tokens
-    qg.A = b.hT; qg.lda = 5 * kVitW; R.setW(qg, B.in_proj, 0); qg.M = mc; qg.N = kVitW; qg.K = kVitW;
-    qg.bias = B.in_proj.b; qg.outT = b.y; qg.ldT = kVitW;
-    R.gemm(qg);
-    R.prof_begin(1, 4.0 * mc * kVitHeads * 5.0 * 32);
-    int e = launch_vit_attn_cls(b.y, b.qkv, b.att, mc, 5, kVitW, kVitHeads, h->bf16, R.st);
-    R.prof_end();
-    R.other(e, "vit_attn_cls");
-    cal(jl, 1, b.att, mc, kVitW);
-    residual(b.att, kVitW, B.out_proj, mc, x, 5 * kVitW, b.pre, b.xT, 5 * kVitW, b.cT, kVitW);   // xc = x_cls + attn
-    norm(b.pre, b.cT, kVitW, B.ln2g, B.ln2b, mc, b.hT);
-    cal(jl, 2, b.hT, mc, kVitW);
-    R.linear(b.hT, kVitW, B.fc, mc, ACT_QUICKGELU, nullptr, 0, nullptr, 0, nullptr, 0, b.u, 4 * kVitW);
-    cal(jl, 3, b.u, mc, 4 * kVitW);
-    residual(b.u, 4 * kVitW, B.proj, mc, b.pre, kVitW, b.pre, b.cT, kVitW, b.cT, kVitW);
-    xpost = b.pre;
-    xpostT = b.cT;
-    ld_post = kVitW;
-  }
+  for (int j = 0; j < kVitLayers; ++j)   // (the pad crops are zero images: real activations, inside the valid rows' range of a calibrating pass)
+    vit_block(R, h->vit.blk[j], mc, 5, b, prune && j == kVitLayers - 1, f8mode == 2 ? sc + j * 4 : nullptr, f8mode == 1 ? amax + j * 4 : nullptr);
   // ln_post on the cls rows, then @ projection into cat[:, 0:768]   (vit.py:186-189)
-  norm(xpost, xpostT, ld_post, h->vit.lnpost_g, h->vit.lnpost_b, mc, b.y);
+  const long long ld_post = prune ? kVitW : 5 * kVitW;
+  if (sT) R.lnT(prune ? b.cT : b.xT, ld_post, h->vit.lnpost_g, h->vit.lnpost_b, 1e-5f, 0, mc, kVitW, nullptr, b.y);
+  else R.ln(prune ? b.pre : b.x, ld_post, h->vit.lnpost_g, h->vit.lnpost_b, 1e-5f, 0, mc, kVitW, nullptr, b.y);
   R.linear(b.y, kVitW, h->vit.projection, mc, ACT_NONE, nullptr, 0, nullptr, 0, nullptr, 0,
            R.offT(cat, (long long)r0 * 2 * kVitW), 2 * kVitW);
 }
@@ -1127,16 +1120,13 @@ int obj_encode(Run& R, const uint8_t* const crops[2], const int64_t* const bbox[
            gemm_a8_ok(&h->tune, (long long)mc * 5, 4 * kVitW, kVitW, kVitW, kVitW) && gemm_a8_ok(&h->tune, (long long)mc * 5, kVitW, 4 * kVitW, 4 * kVitW, 4 * kVitW);
   };
   const bool can8 = h->a8 && h->bf16 && h->stream_T && h->vit_prune_last && fits8(chunk) && a8ok(chunk);
-  const bool calibrate = can8 && !h->vit8_ready;
+  Fp8Cal& c8 = h->cal8[CAL_VIT];
+  const bool calibrate = can8 && !c8.ready;
   if (calibrate) {
-    if (!h->vit8_amax) {
-      HIPCK(hipMalloc((void**)&h->vit8_amax, kVitLayers * 4 * sizeof(float)));
-      h->owned.push_back(h->vit8_amax);
-    }
-    HIPCK(hipMemsetAsync(h->vit8_amax, 0, kVitLayers * 4 * sizeof(float), R.st));
+    if (int e = cal_begin(h, c8, R.st)) return R.err = e;
     if (dual) { HIPCK(hipStreamSynchronize(R.st)); }   // the auxiliary stream's chunks must see the zeroed slots
   }
-  if (can8 && h->vit8_ready)
+  if (can8 && c8.ready)
     for (int i = 0; i < (dual ? 2 : 1); ++i) {
       vb[i].h8 = R.ws<uint8_t>((size_t)chunk * 5 * kVitW);
       vb[i].att8 = R.ws<uint8_t>((size_t)chunk * 5 * kVitW);
@@ -1151,19 +1141,13 @@ int obj_encode(Run& R, const uint8_t* const crops[2], const int64_t* const bbox[
     const int up = (mc + 255) / 256 * 256;
     const int mp = (pad && (up - mc) * 8 <= mc) ? up : mc;
     Run& Rc = (dual && (ci & 1)) ? Rb : R;
-    const int f8mode = (can8 && fits8(mp) && a8ok(mp)) ? (h->vit8_ready ? 2 : 1) : 0;
-    vit_chunk(Rc, crops, per_view, r0, mc, mp, vb[dual ? (ci & 1) : 0], cat, f8mode, h->vit8_amax, h->vit8_scale.data());
+    const int f8mode = (can8 && fits8(mp) && a8ok(mp)) ? (c8.ready ? 2 : 1) : 0;
+    vit_chunk(Rc, crops, per_view, r0, mc, mp, vb[dual ? (ci & 1) : 0], cat, f8mode, c8.amax, c8.scale.data());
     if (R.err || Rb.err) return R.err = (R.err ? R.err : Rb.err);
   }
   if (dual && join_aux(R)) return R.err = 1;
-  if (calibrate) {
-    std::vector<float> am(kVitLayers * 4);
-    HIPCK(hipMemcpyAsync(am.data(), h->vit8_amax, am.size() * sizeof(float), hipMemcpyDeviceToHost, R.st));
-    HIPCK(hipStreamSynchronize(R.st));
-    if (int e = fp8_scales_from_amax(am, h->fp8_headroom_pct, "ViT", h->vit8_scale)) return R.err = e;
-    h->vit8_ready = true;
-    ++h->state_gen;
-  }
+  if (calibrate)
+    if (int e = cal_freeze(h, c8, R.st)) return R.err = e;
   // bbox MLP per view -> cat[:, 768:1536]; then per-view Linear(1536 -> E) scattered to [n, 2qv, E]
   void* t1 = R.wsT((size_t)per_view * 768);
   void* t2 = R.wsT((size_t)per_view * 768);
@@ -1230,11 +1214,8 @@ int t5_bias_table(VimaHandle* h, int L, float** out) {
 
 struct T5Buf { void *hT, *qkv, *ctx, *u; float *ssA, *ssB; void *h8 = nullptr, *ctx8 = nullptr, *u8 = nullptr; };   // ssA / ssB: RMS partial sums [rows][24] (fused path); *8: fp8 copies (precision "fp8")
 
-void t5_layer(Run& R, const VimaHandle::T5Layer& Ly, float* x, const uint8_t* mask, const float* table, int B, int L,
-              const T5Buf& b, int attn_impl) {
-  const int rows = B * L;
-  R.ln(x, kT5Model, Ly.rms1, nullptr, 1e-6f, 1, rows, kT5Model, nullptr, b.hT);
-  R.linear(b.hT, kT5Model, Ly.qkv, rows, ACT_NONE, nullptr, 0, nullptr, 0, nullptr, 0, b.qkv, 3 * kT5Model);
+// self-attention of a T5 layer (every form): q | k | v in b.qkv -> b.ctx, relative-position bias from `table`, no 1/sqrt(d)
+AttnArgs t5_attn_args(Run& R, const T5Buf& b, const uint8_t* mask, const float* table, int B, int L) {
   AttnArgs a;
   a.q = b.qkv; a.ldq = 3 * kT5Model;
   a.k = R.offT(b.qkv, kT5Model); a.ldk = 3 * kT5Model;
@@ -1242,7 +1223,15 @@ void t5_layer(Run& R, const VimaHandle::T5Layer& Ly, float* x, const uint8_t* ma
   a.out = b.ctx; a.ldo = kT5Model;
   a.kmask = mask; a.relbias = table; a.bias_far = R.h->t5_bias_far.count(L) ? R.h->t5_bias_far[L] : 0; a.B = B; a.H = kT5Heads; a.Lq = L; a.Lk = L; a.D = kT5D; a.scale = 1.0f;
   a.mode = ATTN_T5;
-  R.attn(a, attn_impl);
+  return a;
+}
+
+void t5_layer(Run& R, const VimaHandle::T5Layer& Ly, float* x, const uint8_t* mask, const float* table, int B, int L,
+              const T5Buf& b, int attn_impl) {
+  const int rows = B * L;
+  R.ln(x, kT5Model, Ly.rms1, nullptr, 1e-6f, 1, rows, kT5Model, nullptr, b.hT);
+  R.linear(b.hT, kT5Model, Ly.qkv, rows, ACT_NONE, nullptr, 0, nullptr, 0, nullptr, 0, b.qkv, 3 * kT5Model);
+  R.attn(t5_attn_args(R, b, mask, table, B, L), attn_impl);
   R.linear(b.ctx, kT5Model, Ly.o, rows, ACT_NONE, nullptr, 0, x, kT5Model, x, kT5Model, nullptr, 0);
   R.ln(x, kT5Model, Ly.rms2, nullptr, 1e-6f, 1, rows, kT5Model, nullptr, b.hT);
   R.linear(b.hT, kT5Model, Ly.wi, rows, ACT_RELU, nullptr, 0, nullptr, 0, nullptr, 0, b.u, kT5FF);
@@ -1256,91 +1245,37 @@ void t5_layer(Run& R, const VimaHandle::T5Layer& Ly, float* x, const uint8_t* ma
 //   * sum x^2 comes from the producer's epilogue as 24 per-32-column partials per row (deterministic, no atomics).
 // Entry: b.hT / ssq_in describe the incoming x (`parts_in` partials per row); exit: b.hT and the returned buffer
 // describe the outgoing x (24 partials). Removes two 600-MB HBM passes (fp32 read + bf16 write) per layer at cfg-3.
-// precision "fp8", after calibration: the same fused layer with fp8 e4m3 activations into all four GEMMs (stream_T form only).
-// `sc` = this layer's four dequantisation scales followed by the next layer's first one (0 for the last layer): the residual
-// GEMMs write the fp8 copy of the new stream next to the bf16 stream, wi writes its ReLU hidden in fp8 only; the attention
-// context is quantised by a separate pass (its kernel owns 64 of a row's 768 columns).
-const float* t5_layer_fp8(Run& R, const VimaHandle::T5Layer& Ly, const uint8_t* mask, const float* table, int B, int L, const T5Buf& b,
-                          int attn_impl, const float* ssq_in, int parts_in, const float* sc) {
+// One function for every fused form:
+//   * option stream_T: the residual stream IS hT (operand type: bf16 in the bf16 / fp8w precisions, fp32 in the parity mode), hT = T(hT + ctx Wo^T) in place, and
+//     the fp32 copy `x` is not maintained (4 instead of 10 bytes of HBM traffic per stream element and residual GEMM); stream_T = 0: the residual GEMMs update x
+//     and write its operand-type copy to hT.
+//   * sc (precision "fp8" after calibration, stream_T form only; null: operand-type activations) = this layer's four dequantisation scales followed by the next
+//     layer's first one (0 for the last layer): fp8 e4m3 activations into all four GEMMs. The residual GEMMs write the fp8 copy of the new stream next to the bf16
+//     stream, wi writes its ReLU hidden in fp8 only; the attention context is quantised by a separate pass (its kernel owns 64 of a row's 768 columns).
+//   * amax (null: not calibrating): this layer's four max |x| slots of the calibrating pass.
+//   * rows_gemm: option t5_pad, the GEMMs' row count (>= rows, a multiple of 256; the buffers hold that many).
+const float* t5_layer_fused(Run& R, const VimaHandle::T5Layer& Ly, float* x, const uint8_t* mask, const float* table, int B, int L, const T5Buf& b,
+                            int attn_impl, const float* ssq_in, int parts_in, const float* sc, float* amax, int rows_gemm) {
   const int rows = B * L;
-  constexpr int kParts = kT5Model / 32;
-  auto gemm8 = [&](const void* A8, int lda, float ascale, const Lin& W, int act, bool residual, void* outT, int ldT, const float* rs,
-                   int rs_parts, float* ssq_out, void* out8, int ld8, float oscale) {
-    GemmArgs g;
-    g.A = A8; g.lda = lda; g.a8 = 1; g.ascale = ascale; R.setW(g, W); g.M = rows; g.N = W.N; g.K = W.K; g.act = act;
-    if (residual) { g.resT = b.hT; g.ldresT = kT5Model; }
-    g.outT = outT; g.ldT = ldT;
-    g.rs_ssq = rs; g.rs_parts = rs_parts; g.rs_invk = 1.0f / (float)kT5Model; g.rs_eps = 1e-6f;
-    g.ssq_out = ssq_out;
-    if (out8 && oscale > 0.f) { g.out8 = out8; g.ld8 = ld8; g.out8_inv = 1.0f / oscale; }
-    return R.gemm(g);
-  };
-  gemm8(b.h8, kT5Model, sc[0], Ly.qkv_g, ACT_NONE, false, b.qkv, 3 * kT5Model, ssq_in, parts_in, nullptr, nullptr, 0, 0.f);
-  AttnArgs a;
-  a.q = b.qkv; a.ldq = 3 * kT5Model;
-  a.k = R.offT(b.qkv, kT5Model); a.ldk = 3 * kT5Model;
-  a.v = R.offT(b.qkv, 2 * kT5Model); a.ldv = 3 * kT5Model;
-  a.out = b.ctx; a.ldo = kT5Model;
-  a.kmask = mask; a.relbias = table; a.bias_far = R.h->t5_bias_far.count(L) ? R.h->t5_bias_far[L] : 0; a.B = B; a.H = kT5Heads; a.Lq = L; a.Lk = L; a.D = kT5D; a.scale = 1.0f;
-  a.mode = ATTN_T5;
-  R.attn(a, attn_impl);
-  OTHER(R, launch_quant_fp8(b.ctx, kT5Model, rows, kT5Model, 1.0f / sc[1], b.ctx8, kT5Model, R.st), "quant_fp8");
-  gemm8(b.ctx8, kT5Model, sc[1], Ly.o, ACT_NONE, true, b.hT, kT5Model, nullptr, 0, b.ssA, b.h8, kT5Model, sc[2]);
-  gemm8(b.h8, kT5Model, sc[2], Ly.wi_g, ACT_RELU, false, nullptr, kT5FF, b.ssA, kParts, nullptr, b.u8, kT5FF, sc[3]);
-  gemm8(b.u8, kT5FF, sc[3], Ly.wo, ACT_NONE, true, b.hT, kT5Model, nullptr, 0, b.ssB, b.h8, kT5Model, sc[4]);
-  return b.ssB;
-}
-
-const float* t5_layer_fused(Run& R, const VimaHandle::T5Layer& Ly, float* x, const uint8_t* mask, const float* table, int B,
-                            int L, const T5Buf& b, int attn_impl, const float* ssq_in, int parts_in, float* amax = nullptr, int rows_gemm = 0) {
-  const int rows = B * L;
-  const int mrows = rows_gemm > rows ? rows_gemm : rows;      // option t5_pad: the GEMMs' row count (>= rows, a multiple of 256; the buffers hold that many)
-  constexpr int kParts = kT5Model / 32;
+  const int m = rows_gemm > rows ? rows_gemm : rows;
+  constexpr int D = kT5Model, kParts = kT5Model / 32;
+  auto s8 = [&](int site) { return sc ? sc[site] : 0.f; };
+  auto hs = [&](int site) { return Opnd{b.hT, D, b.h8, s8(site), R.h->stream_T ? nullptr : x}; };   // the stream, as the input of / the output for `site`
+  const Opnd ctx{b.ctx, D, b.ctx8, s8(1)}, u{sc ? nullptr : b.u, kT5FF, b.u8, s8(3)}, res = hs(0);
   // calibration of the fp8 activation scales: max |x| of the four GEMM inputs of this layer (bf16 tensors)
   auto cal = [&](int site, const void* t, int cols) {
     if (amax) OTHER(R, launch_amax(t, cols, rows, cols, amax + site, R.st), "amax");
   };
-  cal(0, b.hT, kT5Model);
-  auto gemm = [&](const void* A, int lda, const Lin& W, int act, const float* res, float* out32, void* outT, int ldT,
-                  const float* rs, int rs_parts, float* ssq_out) {
-    GemmArgs g;
-    g.A = A; g.lda = lda; R.setW(g, W); g.M = mrows; g.N = W.N; g.K = W.K; g.act = act;
-    g.res = res; g.ldres = kT5Model; g.out32 = out32; g.ld32 = kT5Model; g.outT = outT; g.ldT = ldT;
-    g.rs_ssq = rs; g.rs_parts = rs_parts; g.rs_invk = 1.0f / (float)kT5Model; g.rs_eps = 1e-6f;
-    g.ssq_out = ssq_out;
-    return R.gemm(g);
-  };
-  gemm(b.hT, kT5Model, Ly.qkv_g, ACT_NONE, nullptr, nullptr, b.qkv, 3 * kT5Model, ssq_in, parts_in, nullptr);
-  AttnArgs a;
-  a.q = b.qkv; a.ldq = 3 * kT5Model;
-  a.k = R.offT(b.qkv, kT5Model); a.ldk = 3 * kT5Model;
-  a.v = R.offT(b.qkv, 2 * kT5Model); a.ldv = 3 * kT5Model;
-  a.out = b.ctx; a.ldo = kT5Model;
-  a.kmask = mask; a.relbias = table; a.bias_far = R.h->t5_bias_far.count(L) ? R.h->t5_bias_far[L] : 0; a.B = B; a.H = kT5Heads; a.Lq = L; a.Lk = L; a.D = kT5D; a.scale = 1.0f;
-  a.mode = ATTN_T5;
-  R.attn(a, attn_impl);
-  cal(1, b.ctx, kT5Model);
-  if (R.h->stream_T) {
-    // The residual stream IS hT (operand type: bf16 in the bf16 / fp8w precisions, fp32 in the parity mode): hT = T(hT + ctx Wo^T)
-    // in place, RMS partials of the stored values -> ssA. The fp32 copy `x` is not maintained (4 instead of 10 bytes of HBM
-    // traffic per stream element and residual GEMM).
-    auto gemm_s = [&](const void* A, int lda, const Lin& W, float* ssq_out) {
-      GemmArgs g;
-      g.A = A; g.lda = lda; R.setW(g, W); g.M = mrows; g.N = W.N; g.K = W.K; g.act = ACT_NONE;
-      g.resT = b.hT; g.ldresT = kT5Model; g.outT = b.hT; g.ldT = kT5Model; g.ssq_out = ssq_out;
-      return R.gemm(g);
-    };
-    gemm_s(b.ctx, kT5Model, Ly.o, b.ssA);
-    cal(2, b.hT, kT5Model);
-    gemm(b.hT, kT5Model, Ly.wi_g, ACT_RELU, nullptr, nullptr, b.u, kT5FF, b.ssA, kParts, nullptr);
-    cal(3, b.u, kT5FF);
-    gemm_s(b.u, kT5FF, Ly.wo, b.ssB);
-    return b.ssB;
-  }
-  // x += ctx Wo^T ; bf16 copy of the new x -> hT ; partial sums of its squares -> ssA
-  gemm(b.ctx, kT5Model, Ly.o, ACT_NONE, x, x, b.hT, kT5Model, nullptr, 0, b.ssA);
-  gemm(b.hT, kT5Model, Ly.wi_g, ACT_RELU, nullptr, nullptr, b.u, kT5FF, b.ssA, kParts, nullptr);
-  gemm(b.u, kT5FF, Ly.wo, ACT_NONE, x, x, b.hT, kT5Model, nullptr, 0, b.ssB);
+  cal(0, b.hT, D);
+  R.linear(hs(0), Ly.qkv_g, 0, 3 * D, m, ACT_NONE, nullptr, Opnd{b.qkv, 3 * D}, ssq_in, parts_in);
+  R.attn(t5_attn_args(R, b, mask, table, B, L), attn_impl);
+  cal(1, b.ctx, D);
+  if (sc) OTHER(R, launch_quant_fp8(b.ctx, D, rows, D, 1.0f / sc[1], b.ctx8, D, R.st), "quant_fp8");
+  R.linear(ctx, Ly.o, 0, D, m, ACT_NONE, &res, hs(2), nullptr, 0, b.ssA);      // stream += ctx Wo^T; partial sums of its squares -> ssA
+  cal(2, b.hT, D);
+  R.linear(hs(2), Ly.wi_g, 0, kT5FF, m, ACT_RELU, nullptr, u, b.ssA, kParts);
+  cal(3, b.u, kT5FF);
+  R.linear(u, Ly.wo, 0, D, m, ACT_NONE, &res, hs(4), nullptr, 0, b.ssB);
   return b.ssB;
 }
 
@@ -1364,23 +1299,24 @@ int t5_stack(Run& R, float* x, const uint8_t* mask, int B, int L, float* out32, 
   const bool one_round = h->dual_t5_rows == 0 && t5_tiles768 > num_cu() * 168 / 256 && t5_tiles768 <= num_cu();
   const bool dual = h->dual_stream && B >= 2 && t5_rows >= h->dual_t5_rows && !one_round;
   const int nb[2] = {dual ? B - B / 2 : B, dual ? B / 2 : 0};
-  T5Buf buf[2];
+  // the halves: half 0 on the caller's stream, half 1 (dual only) on the auxiliary one. Every step below issues all of half 0's launches, then all of half 1's.
+  struct Half { Run& R; int n; long long r0, rows; T5Buf b; const float* ss; int rpad; };   // samples, first row, row count, buffers, the running RMS statistics, padded row count
+  Run Rb{h, h->aux};
+  Half halves[2] = {{R, nb[0], 0, (long long)nb[0] * L, {}, nullptr, 0}, {Rb, nb[1], (long long)nb[0] * L, (long long)nb[1] * L, {}, nullptr, 0}};
+  const int nh = dual ? 2 : 1;
   // option t5_pad: a half whose row count is not a multiple of 256 (the 256x256 tile kernels take nothing else) is computed on the next multiple when it has at
   // least 2048 rows: the pad rows enter as zeros, run through the GEMM chain like any row, are neither attended to nor read back (fused RMSNorm chain with the
   // stream in the operand type only; the fp8-activation layers need whole tiles of REAL rows and are left alone)
-  int rpad[2] = {0, 0};
-  for (int i = 0; i < (dual ? 2 : 1); ++i) {
-    const long long r = (long long)nb[i] * L;
-    if (h->t5_pad && h->t5_fuse_rms && h->stream_T && r >= 2048 && r % 256 != 0 && !gemm_splitk_enabled(&h->tune)) rpad[i] = (int)((r + 255) / 256 * 256);
-  }
-  for (int i = 0; i < (dual ? 2 : 1); ++i) {
-    const size_t rows = rpad[i] ? (size_t)rpad[i] : (size_t)nb[i] * L;
-    buf[i].hT = R.wsT(rows * kT5Model);
-    buf[i].qkv = R.wsT(rows * 3 * kT5Model);
-    buf[i].ctx = R.wsT(rows * kT5Model);
-    buf[i].u = R.wsT(rows * kT5FF);
-    buf[i].ssA = R.ws<float>(rows * (kT5Model / 32));
-    buf[i].ssB = R.ws<float>(rows * (kT5Model / 32));
+  for (int i = 0; i < nh; ++i) {
+    Half& H = halves[i];
+    if (h->t5_pad && h->t5_fuse_rms && h->stream_T && H.rows >= 2048 && H.rows % 256 != 0 && !gemm_splitk_enabled(&h->tune)) H.rpad = (int)((H.rows + 255) / 256 * 256);
+    const size_t rows = H.rpad ? (size_t)H.rpad : (size_t)H.rows;
+    H.b.hT = R.wsT(rows * kT5Model);
+    H.b.qkv = R.wsT(rows * 3 * kT5Model);
+    H.b.ctx = R.wsT(rows * kT5Model);
+    H.b.u = R.wsT(rows * kT5FF);
+    H.b.ssA = R.ws<float>(rows * (kT5Model / 32));
+    H.b.ssB = R.ws<float>(rows * (kT5Model / 32));
   }
   // precision "fp8": fp8 activations when the four GEMM shapes of a layer fit the fp8 kernel (full 256x256 tiles, >= 160 of them for
   // the N = 768 GEMMs) and the scales are calibrated; the first pass of a handle calibrates (fp8w kernels + max |x| per site)
@@ -1392,21 +1328,17 @@ int t5_stack(Run& R, float* x, const uint8_t* mask, int B, int L, float* out32, 
   };
   const bool can8 = h->a8 && h->bf16 && h->stream_T && h->t5_fuse_rms && !gemm_splitk_enabled(&h->tune) && fits8(nb[0]) && fits8(nb[1]) &&
                     a8ok(nb[0]) && a8ok(nb[1]);
-  const bool run8 = can8 && h->fp8_ready;
-  const bool calibrate = can8 && !h->fp8_ready;
-  if (calibrate) {
-    if (!h->fp8_amax) {
-      HIPCK(hipMalloc((void**)&h->fp8_amax, kT5Layers * 4 * sizeof(float)));
-      h->owned.push_back(h->fp8_amax);
-    }
-    HIPCK(hipMemsetAsync(h->fp8_amax, 0, kT5Layers * 4 * sizeof(float), R.st));
-  }
+  Fp8Cal& c8 = h->cal8[CAL_T5];
+  const bool run8 = can8 && c8.ready;
+  const bool calibrate = can8 && !c8.ready;
+  if (calibrate)
+    if (int e = cal_begin(h, c8, R.st)) return R.err = e;
   if (run8)
-    for (int i = 0; i < (dual ? 2 : 1); ++i) {
-      const size_t rows = (size_t)nb[i] * L;
-      buf[i].h8 = R.ws<uint8_t>(rows * kT5Model);
-      buf[i].ctx8 = R.ws<uint8_t>(rows * kT5Model);
-      buf[i].u8 = R.ws<uint8_t>(rows * kT5FF);
+    for (int i = 0; i < nh; ++i) {
+      Half& H = halves[i];
+      H.b.h8 = R.ws<uint8_t>((size_t)H.rows * kT5Model);
+      H.b.ctx8 = R.ws<uint8_t>((size_t)H.rows * kT5Model);
+      H.b.u8 = R.ws<uint8_t>((size_t)H.rows * kT5FF);
     }
   if (R.err) return R.err;
   // with the opt-in split-K, small problems keep the standalone RMSNorm: the producer-side statistics are not available
@@ -1419,79 +1351,58 @@ int t5_stack(Run& R, float* x, const uint8_t* mask, int B, int L, float* out32, 
     OTHER(R, launch_prompt_assemble(src->tok_src, src->word_ids, h->word_table, src->objtok, src->objmask, x, const_cast<uint8_t*>(mask),
                                     B * L, kT5Model, R.st), "prompt_assemble");
   }
-  Run Rb{h, h->aux};
   if (dual && fork_aux(R)) return R.err = 1;
-  const long long off1 = (long long)nb[0] * L;      // first row of the second half
-  float* const x1 = x ? x + off1 * kT5Model : nullptr;   // (direct assembly: there is no fp32 stream, and the stream_T layers never touch it)
-  const float* ss[2] = {nullptr, nullptr};
+  auto xh = [&](const Half& H) { return x ? x + H.r0 * kT5Model : nullptr; };   // the half's rows of the fp32 stream (direct assembly: there is none, and the stream_T layers never touch it)
   int parts = 1;
-  if (direct) {
-    OTHER(R, launch_prompt_assemble_stats(src->tok_src, src->word_ids, h->word_table, src->objtok, src->objmask, buf[0].hT, buf[0].ssB,
-                                          const_cast<uint8_t*>(mask), nb[0] * L, kT5Model, h->bf16, R.st), "prompt_assemble");
-    ss[0] = buf[0].ssB;
-    if (dual) {
-      OTHER(Rb, launch_prompt_assemble_stats(src->tok_src + off1, src->word_ids, h->word_table, src->objtok, src->objmask, buf[1].hT, buf[1].ssB,
-                                             const_cast<uint8_t*>(mask) + off1, nb[1] * L, kT5Model, h->bf16, Rb.st), "prompt_assemble");
-      ss[1] = buf[1].ssB;
-    }
-  } else if (fused) {   // entry of the chain: operand-type copy of x and its row sums of squares (one partial per row)
-    R.other(launch_rms_stats(x, nb[0] * L, kT5Model, buf[0].hT, buf[0].ssB, h->bf16, R.st), "rms_stats");
-    ss[0] = buf[0].ssB;
-    if (dual) {
-      Rb.other(launch_rms_stats(x1, nb[1] * L, kT5Model, buf[1].hT, buf[1].ssB, h->bf16, Rb.st), "rms_stats");
-      ss[1] = buf[1].ssB;
-    }
+  for (int i = 0; i < nh; ++i) {   // entry of the fused chain: operand-type rows of the incoming x in hT and their row sums of squares (one partial per row) in ssB
+    Half& H = halves[i];
+    if (direct)
+      OTHER(H.R, launch_prompt_assemble_stats(src->tok_src + H.r0, src->word_ids, h->word_table, src->objtok, src->objmask, H.b.hT, H.b.ssB,
+                                              const_cast<uint8_t*>(mask) + H.r0, (int)H.rows, kT5Model, h->bf16, H.R.st), "prompt_assemble");
+    else if (fused)
+      H.R.other(launch_rms_stats(xh(H), (int)H.rows, kT5Model, H.b.hT, H.b.ssB, h->bf16, H.R.st), "rms_stats");
+    if (fused) H.ss = H.b.ssB;
   }
-  if (run8) {   // entry: fp8 copy of the incoming stream with layer 0's first scale
-    OTHER(R, launch_quant_fp8(buf[0].hT, kT5Model, (long long)nb[0] * L, kT5Model, 1.0f / h->fp8_scale[0], buf[0].h8, kT5Model, R.st), "quant_fp8");
-    if (dual) OTHER(Rb, launch_quant_fp8(buf[1].hT, kT5Model, (long long)nb[1] * L, kT5Model, 1.0f / h->fp8_scale[0], buf[1].h8, kT5Model, Rb.st), "quant_fp8");
-  }
-  for (int i = 0; i < (dual ? 2 : 1); ++i)
-    if (rpad[i]) {   // zero pad rows: stream entry, its row statistics, and the attention output rows no attention launch writes
-      Run& Ri = i ? Rb : R;
-      const long long r = (long long)nb[i] * L, np = rpad[i] - r;
-      HIPCK(hipMemsetAsync(Ri.offT(buf[i].hT, r * kT5Model), 0, (size_t)np * kT5Model * h->esz(), Ri.st));
-      HIPCK(hipMemsetAsync(Ri.offT(buf[i].ctx, r * kT5Model), 0, (size_t)np * kT5Model * h->esz(), Ri.st));
-      HIPCK(hipMemsetAsync(buf[i].ssB + r * (kT5Model / 32), 0, (size_t)np * (kT5Model / 32) * sizeof(float), Ri.st));
+  if (run8)   // entry: fp8 copy of the incoming stream with layer 0's first scale
+    for (int i = 0; i < nh; ++i) {
+      Half& H = halves[i];
+      OTHER(H.R, launch_quant_fp8(H.b.hT, kT5Model, H.rows, kT5Model, 1.0f / c8.scale[0], H.b.h8, kT5Model, H.R.st), "quant_fp8");
+    }
+  for (int i = 0; i < nh; ++i)
+    if (halves[i].rpad) {   // zero pad rows: the stream's entry, its entry statistics (one partial per row: what layer 0's qkv GEMM reads), and the attention output rows no attention launch writes
+      Half& H = halves[i];
+      const long long r = H.rows, np = H.rpad - r;
+      HIPCK(hipMemsetAsync(R.offT(H.b.hT, r * kT5Model), 0, (size_t)np * kT5Model * h->esz(), H.R.st));
+      HIPCK(hipMemsetAsync(R.offT(H.b.ctx, r * kT5Model), 0, (size_t)np * kT5Model * h->esz(), H.R.st));
+      HIPCK(hipMemsetAsync(H.b.ssB + r, 0, (size_t)np * sizeof(float), H.R.st));
     }
   for (int l = 0; l < kT5Layers; ++l) {
-    if (run8) {
-      float sc[5];
-      for (int k = 0; k < 4; ++k) sc[k] = h->fp8_scale[l * 4 + k];
-      sc[4] = l + 1 < kT5Layers ? h->fp8_scale[(l + 1) * 4] : 0.f;
-      ss[0] = t5_layer_fp8(R, h->t5[l], mask, table, nb[0], L, buf[0], h->attn_impl, ss[0], parts, sc);
-      if (dual) ss[1] = t5_layer_fp8(Rb, h->t5[l], mask + off1, table, nb[1], L, buf[1], h->attn_impl, ss[1], parts, sc);
-      parts = kT5Model / 32;
-    } else if (fused) {
-      float* am = calibrate ? h->fp8_amax + l * 4 : nullptr;
-      ss[0] = t5_layer_fused(R, h->t5[l], x, mask, table, nb[0], L, buf[0], h->attn_impl, ss[0], parts, am, rpad[0]);
-      if (dual) ss[1] = t5_layer_fused(Rb, h->t5[l], x1, mask + off1, table, nb[1], L, buf[1], h->attn_impl, ss[1], parts, am, rpad[1]);
-      parts = kT5Model / 32;
-    } else {
-      t5_layer(R, h->t5[l], x, mask, table, nb[0], L, buf[0], h->attn_impl);
-      if (dual) t5_layer(Rb, h->t5[l], x1, mask + off1, table, nb[1], L, buf[1], h->attn_impl);
+    float sc[5];   // run8: this layer's four scales and the next layer's first one (0 behind the last layer: no e4m3 copy of the final stream)
+    for (int k = 0; k < 5 && run8; ++k) sc[k] = l * 4 + k < kT5Layers * 4 ? c8.scale[l * 4 + k] : 0.f;
+    for (int i = 0; i < nh; ++i) {
+      Half& H = halves[i];
+      if (fused)
+        H.ss = t5_layer_fused(H.R, h->t5[l], xh(H), mask + H.r0, table, H.n, L, H.b, h->attn_impl, H.ss, parts, run8 ? sc : nullptr,
+                              calibrate ? c8.amax + l * 4 : nullptr, H.rpad);
+      else
+        t5_layer(H.R, h->t5[l], xh(H), mask + H.r0, table, H.n, L, H.b, h->attn_impl);
     }
+    parts = kT5Model / 32;
     if (R.err || Rb.err) return R.err = (R.err ? R.err : Rb.err);
   }
-  const bool sT = fused && h->stream_T;   // the stream lives in buf[i].hT
-  if (sT) R.lnT(buf[0].hT, kT5Model, h->t5_final, nullptr, 1e-6f, 1, nb[0] * L, kT5Model, out32, outT);
-  else R.ln(x, kT5Model, h->t5_final, nullptr, 1e-6f, 1, nb[0] * L, kT5Model, out32, outT);
+  for (int i = 0; i < nh; ++i) {   // final RMSNorm; with the fused chain and stream_T the stream lives in hT
+    Half& H = halves[i];
+    float* const o32 = out32 ? out32 + H.r0 * kT5Model : nullptr;
+    void* const oT = outT ? R.offT(outT, H.r0 * kT5Model) : nullptr;
+    if (fused && h->stream_T) H.R.lnT(H.b.hT, kT5Model, h->t5_final, nullptr, 1e-6f, 1, (int)H.rows, kT5Model, o32, oT);
+    else H.R.ln(xh(H), kT5Model, h->t5_final, nullptr, 1e-6f, 1, (int)H.rows, kT5Model, o32, oT);
+  }
   if (dual) {
-    if (sT) Rb.lnT(buf[1].hT, kT5Model, h->t5_final, nullptr, 1e-6f, 1, nb[1] * L, kT5Model,
-                   out32 ? out32 + off1 * kT5Model : nullptr, outT ? R.offT(outT, off1 * kT5Model) : nullptr);
-    else Rb.ln(x1, kT5Model, h->t5_final, nullptr, 1e-6f, 1, nb[1] * L, kT5Model,
-          out32 ? out32 + off1 * kT5Model : nullptr, outT ? R.offT(outT, off1 * kT5Model) : nullptr);
     if (Rb.err) return R.err = Rb.err;
     if (join_aux(R)) return R.err = 1;
   }
-  if (calibrate && !R.err) {   // one-time: read the 48 maxima back and freeze the scales (amax / 448; a dead site gets 1)
-    std::vector<float> am(kT5Layers * 4);
-    HIPCK(hipMemcpyAsync(am.data(), h->fp8_amax, am.size() * sizeof(float), hipMemcpyDeviceToHost, R.st));
-    HIPCK(hipStreamSynchronize(R.st));
-    if (int e = fp8_scales_from_amax(am, h->fp8_headroom_pct, "T5", h->fp8_scale)) return R.err = e;
-    h->fp8_ready = true;
-    ++h->state_gen;
-  }
+  if (calibrate && !R.err)   // one-time: read the 48 maxima back and freeze the scales
+    if (int e = cal_freeze(h, c8, R.st)) return R.err = e;
   return R.err;
 }
 
@@ -1840,17 +1751,18 @@ int vima_set_option(VimaHandle* h, const char* key, int64_t value) {
   else if (k == "restart_batched") h->restart_batched = (int)value;
   else if (k == "t5_fuse_rms") h->t5_fuse_rms = (int)value;
   else if (k == "stream_T") h->stream_T = (int)value;
-  else if (k == "fp8_headroom_pct") { h->fp8_headroom_pct = value < 100 ? 100 : (int)value; h->fp8_ready = false; h->vit8_ready = false; h->kv8_ready = false; }
-  else if (k == "fp8_recalibrate") { h->fp8_ready = false; h->vit8_ready = false; h->kv8_ready = false; }   // precision "fp8": measure the activation scales again
+  else if (k == "fp8_headroom_pct" || k == "fp8_recalibrate") {   // precision "fp8": measure the activation scales (of every group) again
+    if (k == "fp8_headroom_pct") h->fp8_headroom_pct = value < 100 ? 100 : (int)value;
+    for (Fp8Cal& c : h->cal8) c.ready = false;
+  }
   else return fail("vima_set_option: unknown key " + k);
   return 0;
 }
 
 int vima_fp8_act_scales(VimaHandle* h, int group, float* out, int max_n) {
   if (!h) { (void)fail("null handle"); return -1; }
-  const bool ready = group == 0 ? h->fp8_ready : group == 1 ? h->vit8_ready : group == 2 ? h->kv8_ready : false;
-  if (!ready) return 0;
-  const std::vector<float>& v = group == 0 ? h->fp8_scale : group == 1 ? h->vit8_scale : h->kv8_scale;
+  if (group < 0 || group > CAL_KV || !h->cal8[group].ready) return 0;
+  const std::vector<float>& v = h->cal8[group].scale;
   const int n = (int)v.size();
   for (int i = 0; i < n && i < max_n; ++i) out[i] = v[i];
   return n;
@@ -2237,21 +2149,13 @@ static int decode_launch(VimaHandle* h, const float* obs_tok, const uint8_t* obs
   float kv_scale = 0.f;
   if (build_kv && h->a8 && h->bf16 && E % 256 == 0 && rp % 256 == 0 && (long long)(rp / 256) * (2 * E / 256) >= 160 && h->dec[0].kv.ws &&
       gemm_a8_ok(&h->tune, rp, 2 * E, E, E, E)) {
-    if (!h->kv8_ready) {
-      if (!h->kv8_amax) {
-        HIPCK(hipMalloc((void**)&h->kv8_amax, sizeof(float)));
-        h->owned.push_back(h->kv8_amax);
-      }
-      HIPCK(hipMemsetAsync(h->kv8_amax, 0, sizeof(float), R.st));
-      OTHER(R, launch_amax(pT, E, rp, E, h->kv8_amax, R.st), "amax");
-      float am = 0.f;
-      HIPCK(hipMemcpyAsync(&am, h->kv8_amax, sizeof(float), hipMemcpyDeviceToHost, R.st));
-      HIPCK(hipStreamSynchronize(R.st));
-      if (int e = fp8_scales_from_amax(std::vector<float>(1, am), h->fp8_headroom_pct, "prompt K/V", h->kv8_scale)) return R.err = e;
-      h->kv8_ready = true;
-      ++h->state_gen;
+    Fp8Cal& c8 = h->cal8[CAL_KV];
+    if (!c8.ready) {   // measure and freeze inside this call, which itself still runs on operand-type activations
+      if (int e = cal_begin(h, c8, R.st)) return R.err = e;
+      OTHER(R, launch_amax(pT, E, rp, E, c8.amax, R.st), "amax");
+      if (int e = cal_freeze(h, c8, R.st)) return R.err = e;
     } else {
-      kv_scale = h->kv8_scale[0];
+      kv_scale = c8.scale[0];
       p8 = R.ws<uint8_t>((size_t)rp * E);
       if (R.err) return R.err;
       OTHER(R, launch_quant_fp8(pT, E, rp, E, 1.0f / kv_scale, p8, E, R.st), "quant_fp8");
@@ -2269,11 +2173,7 @@ static int decode_launch(VimaHandle* h, const float* obs_tok, const uint8_t* obs
     hm = hist ? false : h->kv_hm;   // hist: gathered below, row-major
   if (use_cache && build_kv) h->kv_hm = hm;
   auto kv_proj = [&](Run& Rr, int i, void* KV) {
-    GemmArgs g;
-    if (p8) { g.A = p8; g.lda = E; g.a8 = 1; g.ascale = kv_scale; }
-    else { g.A = pT; g.lda = E; }
-    Rr.setW(g, h->dec[i].kv); g.M = rp; g.N = 2 * E; g.K = E; g.bias = h->dec[i].kv.b;
-    g.outT = KV; g.ldT = 2 * E;
+    GemmArgs g = Rr.linear_args(Opnd{pT, E, p8, p8 ? kv_scale : 0.f}, h->dec[i].kv, 0, 2 * E, rp, ACT_NONE, nullptr, Opnd{KV, 2 * E});
     if (hm) { g.hm_D = Dx; g.hm_L = Lp; }
     return Rr.gemm(g);
   };
