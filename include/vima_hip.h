@@ -648,6 +648,9 @@ int vima_t5_bucket(int relative_position);
  *                                               bf16-stream / head-major epilogues): 1 its 256x384 tile wherever it fits, 2 its 128x384 tile wherever it fits,
  *                                               3 the 128x384 tile where it needs fewer rounds of the chip than the 256x256 tiling (batch 32), 6 (default) the 256x384 tile
  *                                               for GEMMs of >= 32 768 rows (wall clock of the two-stream model: -1.4 % on the headline step), 0 off; bit-identical results in every mode
+ *                            "gemm_q4_rs"   [1] the fused-RMSNorm consumers with 24 partials per row, a bf16 output and no bias (T5 q|k|v and wi) take gemm_q4_kernel's
+ *                                               256x384 tile as well, wherever "gemm_q4" gives that tile: a lane carries its four row scales through the K loop in
+ *                                               registers; 0 = they stay on gemm_pp_kernel; bit-identical either way
  *                            "gemm_small"   [1] 64x64 / 32x64 tiles for grids that would leave most CUs idle
  *                            "gemm_resident" [1] underfilled grids on gemm_resident_kernel ((almost) the whole K extent in flight, one
  *                                               barrier per chunk of K-slices; bit-identical to the ring tiles), 0: the 4-deep ring tiles

@@ -217,12 +217,14 @@ __device__ __forceinline__ f32x16_t mma8(const Frag8& w, const Frag8& a, f32x16_
 
 // 24 per-32-column partial sums of one row (E = 768) in a fixed order: six independent 16-byte loads (a scalar loop serialises
 // the load latencies); pairs of 32-column partials are summed first -- the same add every producer shape would do for a
-// 64-column group
-__device__ __forceinline__ float ln_tree24(const float* q) {
-  const float4 a = load4(q), b = load4(q + 4), c = load4(q + 8), d = load4(q + 12), e = load4(q + 16), f = load4(q + 20);
+// 64-column group. ln_tree24_v: the tree over values already in registers (gemm_q4_kernel's row-scale form loads them itself)
+__device__ __forceinline__ float ln_tree24_v(const float4& a, const float4& b, const float4& c, const float4& d, const float4& e, const float4& f) {
   const float s0 = a.x + a.y, s1 = a.z + a.w, s2 = b.x + b.y, s3 = b.z + b.w, s4 = c.x + c.y, s5 = c.z + c.w;
   const float s6 = d.x + d.y, s7 = d.z + d.w, s8 = e.x + e.y, s9 = e.z + e.w, s10 = f.x + f.y, s11 = f.z + f.w;
   return (((s0 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7))) + ((s8 + s9) + (s10 + s11));
+}
+__device__ __forceinline__ float ln_tree24(const float* q) {
+  return ln_tree24_v(load4(q), load4(q + 4), load4(q + 8), load4(q + 12), load4(q + 16), load4(q + 20));
 }
 
 // fused RMSNorm row scale: rsqrt(mean of squares + eps) from the producer's per-64-column partial sums (fixed order)
@@ -777,9 +779,12 @@ __global__ __launch_bounds__(TL::THREADS, TL::MINW) void gemm_kernel(const GemmD
 // v_pk_add + one v_cndmask per value and kept the x rsc multiply -- 256 of the 321 VALU instructions per wave of a
 // bias-less, scale-less epilogue (every T5 GEMM) did nothing, and the epilogue is VALU-issue-bound (2 waves per SIMD).
 // NI / MI: 32-column / 32-row blocks per wave (2 / 4: the 256x256 kernels' 128x64 block; 6 / 4 and 6 / 2: gemm_q4_kernel's 128x192 and 64x192)
-template <int ACT, int EPI, bool W8, bool HAS_BIAS, bool HAS_RS, bool OUT8, int NI = 2, int MI = 4>
+// ROWHOOK: called with mi in front of the slabs of 32-row block mi (mi - 1's accumulators are dead from there on); gemm_q4_kernel's row-scale form
+// issues the next tile's partial loads from it.
+struct EpiNoHook { __device__ __forceinline__ void operator()(int) const {} };
+template <int ACT, int EPI, bool W8, bool HAS_BIAS, bool HAS_RS, bool OUT8, int NI = 2, int MI = 4, class ROWHOOK = EpiNoHook>
 __device__ __forceinline__ void tile_epilogue_256_impl(const GemmDev& p, const f32x16_t (&acc)[MI][NI], const float (&rscv)[MI], char* slab,
-                                                       int lane, int m0, int n0, int wm, int wn) {
+                                                       int lane, int m0, int n0, int wm, int wn, const ROWHOOK& rowhook = ROWHOOK()) {
   using T = bf16_t;
   const int act = ACT >= 0 ? ACT : p.act;
   // ---------------------------------------------------------------- epilogue (32x32 fp32 slabs, private LDS region)
@@ -893,6 +898,7 @@ __device__ __forceinline__ void tile_epilogue_256_impl(const GemmDev& p, const f
   };
 #pragma unroll
   for (int mi = 0; mi < MI; ++mi) {
+    rowhook(mi);
     const float rsc = rscv[mi];
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni) {
@@ -2078,6 +2084,14 @@ int launch_q4(GemmDev d, const GemmArgs& a, int epi, hipStream_t st) {
   d.ngroup = ngroup_for(QC::BN, a.K, 2, d.ntiles);   // n-groups whose W panels stay in an XCD's L2
   d.dbg = a.tune ? a.tune->gemm_dbg : nullptr;
   const int grid = d.vtotal < num_cu() ? d.vtotal : num_cu();
+  if constexpr (MIH == 2) {   // epilogue 7: the bf16-output epilogue of a fused-RMSNorm consumer, row scales carried in registers (q4_takes)
+    if (epi == 7) {
+      if (!a.rs_ssq || a.rs_parts != 24 || a.bias) return (int)hipErrorInvalidValue;
+      if (a.act == ACT_NONE) return launch_q4_inst<ACT_NONE, 7, 2>(d, grid, st);
+      if (a.act == ACT_RELU) return launch_q4_inst<ACT_RELU, 7, 2>(d, grid, st);
+      return (int)hipErrorInvalidValue;
+    }
+  }
   switch (a.act * 8 + epi) {
     case ACT_NONE * 8 + 1: return launch_q4_inst<ACT_NONE, 1, MIH>(d, grid, st);
     case ACT_RELU * 8 + 1: return launch_q4_inst<ACT_RELU, 1, MIH>(d, grid, st);

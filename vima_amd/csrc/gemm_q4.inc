@@ -35,6 +35,10 @@
 // counted by hand (LDS reads return in order; the main loop holds no scalar loads, tests/test_kernel_resources.py checks the ISA for that).
 // MIH = 32-row blocks per wave and A half: 2 -> the 256 x 384 tile described above; 1 -> a 128 x 384 tile (wave tile 64 x 192, 12 MFMAs per phase, A slots of 8 KiB,
 // epilogue slabs behind the ring) for problems whose 256-row tilings leave CUs idle: M = 16 384, N = 768 is 192 tiles of 256 x 256 but 256 of 128 x 384.
+// EPI 7 (256 x 384 only) = the bf16-output epilogue (1) of a fused-RMSNorm CONSUMER without bias: every accumulator row is multiplied by
+// rsqrt(sum of the row's 24 partials * rs_invk + rs_eps). The tile has no LDS left for the partials (the 128 x 384 tile parks them behind its ring) and the
+// K loop no registers for them, so a lane carries the four finished scales of its rows through the K loop and the partials of the NEXT tile are fetched
+// across the epilogue, when the 80 fragment registers are dead: see "row scales" in the kernel.
 template <int MIH_>
 struct Q4T {
   static constexpr int MIH = MIH_, RH = MIH_ * 32;             // rows of one A half per wave row
@@ -74,12 +78,25 @@ __device__ __forceinline__ void q4_glds(const void* sbase, unsigned voff, unsign
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff), "s"(sbase), "s"(lds_byte_addr) : "memory");
 }
 
+// one 16-byte global load into accumulator registers whose completion is OURS to wait for. hipcc knows neither the request nor WHEN the registers are
+// written: to it the "=a" output is defined at this statement, so a register-allocator copy or reuse of these AGPRs between the request and rs_landed
+// would read or clobber data that has not arrived. Nothing in the source can forbid that; it holds because the allocator has no other use for AGPRs
+// there, and it was read off the listing (profiles/q4_rms_consumers_isa_digests.txt) -- RE-READ THE LISTING WHEN THE COMPILER CHANGES: only the
+// bit-equality tests (tests/test_q4_rms_consumer_gpu.py, the headline q4 test of tests/test_policy_gpu.py) would catch it otherwise.
+template <int OFF>
+__device__ __forceinline__ void q4_gld(q4_u32x4& d, const void* sbase, unsigned voff) {
+  asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=a"(d) : "v"(voff), "s"(sbase), "n"(OFF) : "memory");
+}
+
 template <int ACT, int EPI, int MIH = 2>
 __global__ __launch_bounds__(Q4::THREADS) __attribute__((amdgpu_waves_per_eu(1, 1))) void gemm_q4_kernel(const GemmDev p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   using QC = Q4T<MIH>;
   constexpr int MI = QC::MI, NI = QC::NI, STAGE = QC::STAGE, RH = QC::RH, PA = QC::PA;
   constexpr int OA0 = QC::OA0, OA1 = QC::OA1, OB0 = QC::OB0, OB1 = QC::OB1;
+  constexpr bool RSQ = EPI == 7;                      // row scales held in registers (launcher: rs_ssq set, rs_parts == 24, no bias)
+  constexpr int EPX = RSQ ? 1 : EPI;                  // the epilogue proper
+  static_assert(!RSQ || MIH == 2, "the 128 x 384 tile keeps its partials in LDS (EPI 1 / 5)");
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -164,8 +181,47 @@ __global__ __launch_bounds__(Q4::THREADS) __attribute__((amdgpu_waves_per_eu(1, 
     q4_glds(W + (rw + row * ldwB), voffW, smem_base + (unsigned)(stq * STAGE + (h ? OB1 : OB0) + (i * 4 + w) * 1024));
   };
 
+  // ---- row scales (EPI 7). In the epilogue a lane needs the scales of rows wm * 128 + mi * 32 + l31, mi = 0 .. 3; lanes l31 and l31 + 32 need the same
+  // four, so each of them fetches and sums TWO rows -- mi = 2 hi and 2 hi + 1: 2 x 24 floats = twelve 16-byte loads -- and one v_permlane32_swap per
+  // value hands both halves all four. The loads are inline asm (hipcc would drain the LDS-DMA stream for a load it tracks) INTO ACCUMULATOR
+  // REGISTERS: in VGPRs the allocator copied and spilled the 48 in-flight registers around the epilogue's own; AGPRs it has no other use for, and
+  // the accumulators of a 32-row block are dead once the block is stored. The requests for the NEXT tile (behind a workgroup's last tile: the
+  // current tile's rows again -- in bounds, never read: the loop leaves before rs_landed and the kernel's final vmcnt(0) covers them; they only keep
+  // the epilogue branch-free) are issued in front of the epilogue's second 32-row block and waited for behind the epilogue and the cursor
+  // arithmetic, with `vmcnt(0)`: a counted wait may only count younger LOADS (see tile_epilogue_256_impl), and what vmcnt(0) waits for besides are
+  // the epilogue's stores and K-tile 1 of the next tile, requested a whole K-tile before the epilogue. The first tile's are requested between
+  // K-tiles 0 and 1 of the prologue, whose own counted wait covers them. rsc holds the current tile's four scales through the K loop.
+  float rsc[4] = {1.0f, 1.0f, 1.0f, 1.0f};
+  auto rs_request = [&](int v, q4_u32x4 (&rq)[12]) {
+    int tm, tn;
+    tile_at(v, tm, tn);
+    const unsigned off = (unsigned)(tm * QC::BM + wm * 128 + hi * 64 + l31) * 96u;   // (launcher: M * 96 < 2^32)
+    q4_gld<0>(rq[0], p.rs_ssq, off); q4_gld<16>(rq[1], p.rs_ssq, off); q4_gld<32>(rq[2], p.rs_ssq, off);
+    q4_gld<48>(rq[3], p.rs_ssq, off); q4_gld<64>(rq[4], p.rs_ssq, off); q4_gld<80>(rq[5], p.rs_ssq, off);
+    q4_gld<3072>(rq[6], p.rs_ssq, off); q4_gld<3088>(rq[7], p.rs_ssq, off); q4_gld<3104>(rq[8], p.rs_ssq, off);
+    q4_gld<3120>(rq[9], p.rs_ssq, off); q4_gld<3136>(rq[10], p.rs_ssq, off); q4_gld<3152>(rq[11], p.rs_ssq, off);
+  };
+  // every request passes through this statement before its registers are named again; DRAIN: with the wait (the prologue has its own)
+  auto rs_landed = [&](auto drain_, q4_u32x4 (&rq)[12]) {
+    if constexpr (decltype(drain_)::value)
+      asm volatile("s_waitcnt vmcnt(0)" : "+a"(rq[0]), "+a"(rq[1]), "+a"(rq[2]), "+a"(rq[3]), "+a"(rq[4]), "+a"(rq[5]), "+a"(rq[6]), "+a"(rq[7]),
+                   "+a"(rq[8]), "+a"(rq[9]), "+a"(rq[10]), "+a"(rq[11]) : : "memory");
+    else
+      asm volatile("" : "+a"(rq[0]), "+a"(rq[1]), "+a"(rq[2]), "+a"(rq[3]), "+a"(rq[4]), "+a"(rq[5]), "+a"(rq[6]), "+a"(rq[7]), "+a"(rq[8]),
+                   "+a"(rq[9]), "+a"(rq[10]), "+a"(rq[11]) : : "memory");
+    // ln_tree24's order, then rms_row_scale's arithmetic -> the same bits as every other tile shape
+    auto f4 = [](const q4_u32x4& u) { return make_float4(__uint_as_float(u.x), __uint_as_float(u.y), __uint_as_float(u.z), __uint_as_float(u.w)); };
+    const float s0 = __builtin_amdgcn_rsqf(ln_tree24_v(f4(rq[0]), f4(rq[1]), f4(rq[2]), f4(rq[3]), f4(rq[4]), f4(rq[5])) * p.rs_invk + p.rs_eps);
+    const float s1 = __builtin_amdgcn_rsqf(ln_tree24_v(f4(rq[6]), f4(rq[7]), f4(rq[8]), f4(rq[9]), f4(rq[10]), f4(rq[11])) * p.rs_invk + p.rs_eps);
+    // swap(x, x): first result = the lower half's value in both halves (rows mi 0 / 1), second = the upper half's (rows mi 2 / 3)
+    const auto x0 = __builtin_amdgcn_permlane32_swap(__float_as_uint(s0), __float_as_uint(s0), false, false);
+    const auto x1 = __builtin_amdgcn_permlane32_swap(__float_as_uint(s1), __float_as_uint(s1), false, false);
+    rsc[0] = __uint_as_float(x0[0]); rsc[1] = __uint_as_float(x1[0]); rsc[2] = __uint_as_float(x0[1]); rsc[3] = __uint_as_float(x1[1]);
+  };
+
   // ---- prologue of the stream (K-tiles 0 and 1 of the first tile, nk >= 2), in the order the steady state would have requested them
   {
+    q4_u32x4 rq[12];
     unsigned ra0, rw0, ra1, rw1;
     cursor(0, ra0, rw0);
     cursor(1, ra1, rw1);
@@ -177,6 +233,7 @@ __global__ __launch_bounds__(Q4::THREADS) __attribute__((amdgpu_waves_per_eu(1, 
     for (int i = 0; i < 6; ++i) pieceB(0, 1, i, rw0);
 #pragma unroll
     for (int i = 0; i < PA; ++i) pieceA(0, 0, i, ra0);
+    if constexpr (RSQ) rs_request(cv, rq);   // older than K-tile 1's 12 + PA pieces: retired by the wait below
 #pragma unroll
     for (int i = 0; i < 6; ++i) pieceB(1, 0, i, rw1);
 #pragma unroll
@@ -184,6 +241,7 @@ __global__ __launch_bounds__(Q4::THREADS) __attribute__((amdgpu_waves_per_eu(1, 
 #pragma unroll
     for (int i = 0; i < 6; ++i) pieceB(1, 1, i, rw1);
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(12 + PA) : "memory");     // K-tile 0 has landed (the 6 + PA + 6 pieces of K-tile 1's B0 / A1 / B1 may be in flight)
+    if constexpr (RSQ) rs_landed(QI<0>{}, rq);
   }
 
   q4_u32x4 fa[MIH][4], fb[3][4];
@@ -216,7 +274,7 @@ __global__ __launch_bounds__(Q4::THREADS) __attribute__((amdgpu_waves_per_eu(1, 
     // wave is done with the epilogue slabs
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    // Fused-RMSNorm consumer (128 x 384 only: the 256 x 384 tile has no LDS left): wave w requests the partials of tile rows [32 w, 32 w + 32) -- 24 floats per
+    // Fused-RMSNorm consumer on the 128 x 384 tile (the 256 x 384 tile has no LDS left and carries its row scales in registers: EPI 7): wave w requests the partials of tile rows [32 w, 32 w + 32) -- 24 floats per
     // row, 3 KiB, contiguous -- by LDS-DMA into their own region. The requests are OLDER than every K-tile request this tile will issue, so the counted
     // waits of its P3 phases (at least two: nk >= 2) retire them and the phase barriers publish them; they are reduced after the loop, from LDS.
     const bool rs_on = MIH == 1 && (EPI == 1 || EPI == 5) && p.rs_ssq != nullptr;    // (launcher: rs_parts == 24)
@@ -358,7 +416,15 @@ __global__ __launch_bounds__(Q4::THREADS) __attribute__((amdgpu_waves_per_eu(1, 
         }
       }
     }
-    tile_epilogue_256<ACT, EPI, false, false, NI, MI>(p, acc, rscv, smem + QC::SLAB_OFF + w * 4096, lane, m0, n0, wm, wn);
+    q4_u32x4 rq[12];
+    if constexpr (RSQ) {
+      // the NEXT tile's partials travel across the epilogue from its second 32-row block on, in the registers of the first one's accumulators
+      const int vq = nv >= 0 ? nv : cv;
+      auto hook = [&](int mi) { if (mi == 1) rs_request(vq, rq); };
+      tile_epilogue_256_impl<ACT, EPX, false, false, true, false, NI, MI>(p, acc, rsc, smem + QC::SLAB_OFF + w * 4096, lane, m0, n0, wm, wn, hook);
+    } else {
+      tile_epilogue_256<ACT, EPX, false, false, NI, MI>(p, acc, rscv, smem + QC::SLAB_OFF + w * 4096, lane, m0, n0, wm, wn);
+    }
     stamp(3);
     __builtin_amdgcn_s_waitcnt(0xC07F);   // this wave's slab reads are done (the barrier at the top of the next tile frees the slot)
     cv = nv;
@@ -366,6 +432,7 @@ __global__ __launch_bounds__(Q4::THREADS) __attribute__((amdgpu_waves_per_eu(1, 
     aC = aN; wC = wN;
     nv = next_valid(cv + G);
     if (nv >= 0) tile_offs(nv, aN, wN);
+    if constexpr (RSQ) rs_landed(QI<1>{}, rq);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the stream's trailing (unused) requests have landed before the LDS is released
 }

@@ -35,6 +35,7 @@ VIMA_KNOB(gemm_splitk, "VIMA_GEMM_SPLITK", 0)
 VIMA_KNOB(gemm_wide, "VIMA_GEMM_WIDE", 0)
 VIMA_KNOB(gemm_pp, "VIMA_GEMM_PP", 1)
 VIMA_KNOB(gemm_q4, "VIMA_GEMM_Q4", 6)
+VIMA_KNOB(gemm_q4_rs, "VIMA_GEMM_Q4_RS", 1)
 VIMA_KNOB(gemm_resident, "VIMA_GEMM_RESIDENT", 1)
 VIMA_KNOB(gemm_res_maxwg, "VIMA_GEMM_RES_MAXWG", 256)
 VIMA_KNOB(gemm_res_nch, "VIMA_GEMM_RES_NCH", 0)
@@ -228,8 +229,15 @@ inline int q4_takes(const GemmArgs& a, bool wide8, int BM) {
   if (a.w8 || a.a8 || a.rb != 0 || a.batch > 1 || a.M % BM || a.N % 384 || a.K < 128 || a.K % 128 || !wide8) return 0;
   if (!lds_dma_offsets_fit(a, 2)) return 0;
   if (a.mul || a.res || a.out32 || a.out8 || a.split_n || a.pair32 || a.sum_out || a.rs_sum) return 0;
-  if (a.rs_ssq && (BM != 128 || a.rs_parts != 24 || a.resT)) return 0;   // fused-RMSNorm consumer: the 128 x 384 tile only (E = 768: 24 partials per row), bf16-output epilogues
+  if (a.rs_ssq && (a.rs_parts != 24 || a.resT)) return 0;   // fused-RMSNorm consumer: E = 768 (24 partials per row), bf16-output epilogues
   if ((long long)(a.M / BM) * (a.N / 384) < 128) return 0;
+  // ... on the 128 x 384 tile the partials sit in LDS behind the ring (epilogues 1 / 5 as they are); the 256 x 384 tile has no LDS left and carries the four
+  // row scales of a lane in registers: its own epilogue 7 -- bf16 output, no bias (the form is instantiated without the bias epilogue: its 48 column registers
+  // beside the four held scales do not fit the kernel's 256 VGPRs, which already stand at 254 / 256), no activation or ReLU: T5's q|k|v and wi. Option gemm_q4_rs = 0 leaves these consumers to gemm_pp_kernel.
+  if (a.rs_ssq && BM == 256) {
+    if (!gemm_q4_rs(a.tune) || a.bias || a.ssq_out || a.hm_D) return 0;
+    return (a.act == ACT_NONE || a.act == ACT_RELU) ? 7 : 0;
+  }
   if (!a.resT && !a.ssq_out) {
     if (a.hm_D) return (a.act == ACT_NONE && a.hm_L % BM == 0) ? 5 : 0;
     return (a.act == ACT_NONE || a.act == ACT_RELU || a.act == ACT_QUICKGELU) ? 1 : 0;
