@@ -446,6 +446,63 @@ int vima_seq_history_room(VimaHandle* h, int32_t* steps_host);
 int vima_decode_fork(VimaHandle* h, const int32_t* source /* HOST [B] */, int B, vima_stream_t stream);
 int vima_seq_decode_fork(VimaHandle* h, const int32_t* source /* HOST [B] */, int B, vima_stream_t stream);
 
+/* ---- episode snapshots: save a sample's decoder state, restore it later (additive, ABI version unchanged) -----------
+ * A fork copies an episode between slots of one batch at one moment; a snapshot carries it across time, slots and handles. The snapshot of sample b
+ * is its episode in COMPACT TIME ORDER, independent of where the ring holds the rows: with n = the env steps the episode has taken (the trailing
+ * batch steps whose advanced rows sum to the sample's ring age, EpisodeBook::steps_of; no such suffix: internal error, nothing changes), the
+ * R = max(n (Q + 1) - 1, 0) rows [o_0 (Q), a_0, o_1 (Q), ...] of every layer's episode K | V cache, in the order of EpisodeBook::history_rows(n),
+ * their key-mask bytes, the position counter and the fresh flag; and (flag VIMA_SNAPSHOT_PROMPT) the sample's prompt: vima_decode_snapshot stores its
+ * block of every layer's prompt K / V cache ROW-MAJOR [layers][Lp][2E] whatever layout the handle's cache has (option kv_headmajor; converted as
+ * kv_gather_kernel does, and back as kv_scatter_kernel does), vima_seq_decode_snapshot the prefix rows [0, P0 = Lp + 1) of the episode cache and
+ * their mask bytes. A snapshot without the prompt leaves the destination's prompt K / V block (prefix rows) untouched on restore: the caller vouches
+ * that the slot holds this prompt -- the cheap form for backtracking inside one prompt group.
+ *
+ * Payload (DEVICE memory, 16-byte aligned, one buffer per snapshot; elements of the handle's operand type, elem_bytes 4 or 2), sections in this order,
+ * each a multiple of 16 bytes:
+ *   header  16 bytes   int32 {position counter, fresh flag, R, 0} -- written and read on the device: neither call synchronises with the host
+ *   mask    pad16(M)   key-mask bytes, M = R (vima_seq_* with the prompt: P0 prefix bytes first, M = P0 + R)
+ *   rows    layers x R x 2E elements
+ *   prompt  layers x Lp x 2E elements (vima_seq_*: layers x P0 x 2E), only with VIMA_SNAPSHOT_PROMPT
+ * VimaEpisodeSnapshotInfo is the host-side description; restore refuses (code 22) an info that does not match the handle: policy kind, embed_dim,
+ * layers, elem_bytes, Q, prompt_len, or a byte count that is not the format's.
+ *
+ * vima_*_snapshot_size: host only; fills infos[i] for samples[i] so that the caller can allocate infos[i].bytes. vima_*_snapshot: packs sample
+ * samples[i] into payloads[i] (capacity[i] >= the size, else code 22) and fills infos[i]; a sample may be listed more than once.
+ * vima_*_restore: slot slots[i] becomes the episode of (payloads[i], infos[i]), at any later time and on any matching handle -- a restart of the slot
+ * followed by an install: its mask row is cleared, the rows go to history_rows(n) of the CURRENT book (the rows the last n batch steps wrote), the
+ * mask bytes to the same rows, counter and flag are written, and on the host the slot's ring age becomes that of a sample restarted n batch steps ago
+ * (so is its vima_decode_steps_left entry). The rule is that of vima_decode_restart_history: n <= the history room, else code 34 and nothing changes.
+ * n = 0 is legal (a just-restarted sample: only the prompt and fresh = 1 travel). Each pair has its own n; one snapshot may go to several slots; a
+ * slot listed twice is refused (22). Other samples keep their bits. vima_decode_restore: the caller passes the snapshot's prompt mask row for the slot
+ * from the next vima_decode_step on (VIMAPolicy.restore_samples updates the tensors).
+ * Refusals, all before anything changes: the other policy family's handle, no running episode batch, a sample / slot outside the batch, a mismatched
+ * info, a too-small capacity, a misaligned payload, and a payload that is not DEVICE memory (hipPointerGetAttributes; code 22).
+ * Cost, whatever the number of pairs and layers: ONE table upload (host copy kept in the handle) and at most 3 launches per call -- episode rows
+ * (episode_pack_kernel / episode_unpack_kernel), prompt K / V (the same kernel), state; vima_seq_*: 2, the prefix rows ride in the first.
+ * Stream-ordered and asynchronous. Captured step graphs stay valid: no pointer and no plan changes. */
+#define VIMA_SNAPSHOT_PROMPT 1
+typedef struct VimaEpisodeSnapshotInfo {
+  int32_t steps;        /* n */
+  int32_t Q;
+  int32_t embed_dim;
+  int32_t layers;
+  int32_t prompt_len;   /* Lp (GPT / Gato: P0 = Lp + 1) */
+  int32_t elem_bytes;
+  int32_t flags;        /* VIMA_SNAPSHOT_* */
+  int32_t policy_kind;  /* VIMA_POLICY_* */
+  int64_t bytes;        /* of the payload */
+} VimaEpisodeSnapshotInfo;
+int vima_decode_snapshot_size(VimaHandle* h, const int32_t* samples /* HOST [n] */, int n, int with_prompt, VimaEpisodeSnapshotInfo* infos /* HOST [n] */);
+int vima_decode_snapshot(VimaHandle* h, const int32_t* samples, int n, int with_prompt, void* const* payloads /* HOST [n] of DEVICE pointers */,
+                         const int64_t* capacity /* HOST [n], bytes */, VimaEpisodeSnapshotInfo* infos, vima_stream_t stream);
+int vima_decode_restore(VimaHandle* h, const int32_t* slots /* HOST [n] */, int n, const void* const* payloads, const VimaEpisodeSnapshotInfo* infos,
+                        vima_stream_t stream);
+int vima_seq_decode_snapshot_size(VimaHandle* h, const int32_t* samples, int n, int with_prompt, VimaEpisodeSnapshotInfo* infos);
+int vima_seq_decode_snapshot(VimaHandle* h, const int32_t* samples, int n, int with_prompt, void* const* payloads, const int64_t* capacity,
+                             VimaEpisodeSnapshotInfo* infos, vima_stream_t stream);
+int vima_seq_decode_restore(VimaHandle* h, const int32_t* slots, int n, const void* const* payloads, const VimaEpisodeSnapshotInfo* infos,
+                            vima_stream_t stream);
+
 /* ---- image preprocessing in front of the policy ------------------------------------------- */
 /* The per-object work of prepare_obs / prepare_prompt (/root/reference/scripts/example.py:374-473 and :243-371; numpy +
  * cv2 per object on the host there): for every frame and every object id, segmentation mask -> pixel bbox ->
@@ -626,6 +683,17 @@ int vima_op_seq_history_install(VimaHandle* h, const uint8_t* mask, const int32_
  * destinations copy nothing. Rows and samples outside the listed (destination, range) set come back unchanged. */
 int vima_op_episode_fork(VimaHandle* h, void* cache, int elem_bytes, int NL, int B, int L, int N, const int32_t* group_src, const int32_t* group_ptr,
                          const int32_t* dsts, const int32_t* range_ptr, const int32_t* ranges, int n_groups, vima_stream_t stream);
+/* launch_episode_pack / launch_episode_unpack (episode_pack_kernel / episode_unpack_kernel) alone, on the caller's DEVICE buffer `cache`
+ * [NL][B][L][N] of elem_bytes-wide elements (4 or 2; N * elem_bytes a multiple of 16 and the buffer 16-byte aligned, else code 22). D = 0: every
+ * sample's block is rows [L][N]; D > 0: head-major [N / D][L][D] (D * elem_bytes a multiple of 16, N a multiple of D). rowmap: HOST [n_map], every
+ * entry in [0, L) (NULL: the identity 0 .. n_map - 1, n_map <= L). Job j moves the nrows[j] <= n_map rows rowmap[n_map - nrows[j] ..] -- a SUFFIX of
+ * the one table -- of sample samples[j], in every layer, between the cache and payloads[j], a DEVICE buffer [NL][nrows[j]][N] (row-major whatever D;
+ * 16-byte aligned; anything but device memory is refused with code 22 before any launch). samples / nrows: HOST [n_jobs]; payloads: HOST array of
+ * n_jobs DEVICE pointers. Pack reads the cache; unpack writes it, refuses a sample listed twice, and leaves every other row and sample unchanged. */
+int vima_op_episode_pack(VimaHandle* h, const void* cache, int elem_bytes, int NL, int B, int L, int N, int D, const int32_t* rowmap, int n_map,
+                         const int32_t* samples, const int32_t* nrows, void* const* payloads, int n_jobs, vima_stream_t stream);
+int vima_op_episode_unpack(VimaHandle* h, void* cache, int elem_bytes, int NL, int B, int L, int N, int D, const int32_t* rowmap, int n_map,
+                           const int32_t* samples, const int32_t* nrows, const void* const* payloads, int n_jobs, vima_stream_t stream);
 /* precision FP8: the calibrated activation scales (dequantisation scale = headroom x max |x| / 448, see VIMA_PRECISION_FP8) of group 0 the T5 stack [12 layers][4 sites:
  * stream before qkv, attention context, stream before wi, ReLU hidden], 1 the ViT [4 blocks][4 sites: ln_1 output, attention output,
  * ln_2 output, QuickGELU hidden], 2 the decoder's prompt K/V projection [1]; returns their number (0 before that group's calibrating

@@ -46,6 +46,14 @@ class VimaSampleOpts(ctypes.Structure):
     _fields_ = [("temperature", vp), ("top_k", ctypes.c_int), ("top_p", c_f32), ("n_samples", ctypes.c_int), ("given", ctypes.c_int)]
 
 
+class VimaEpisodeSnapshotInfo(ctypes.Structure):
+    """VimaEpisodeSnapshotInfo of include/vima_hip.h (vima_decode_snapshot / vima_decode_restore and the vima_seq_* pair), same names, same order."""
+    _fields_ = [(n, c_i32) for n in ("steps", "Q", "embed_dim", "layers", "prompt_len", "elem_bytes", "flags", "policy_kind")] + [("bytes", c_i64)]
+
+
+SNAPSHOT_PROMPT = 1   # VIMA_SNAPSHOT_PROMPT
+
+
 def _header_abi_version() -> int:
     """VIMA_ABI_VERSION the package was built against. The number lives in include/vima_hip.h; `vima_amd/csrc/build.sh` copies it into
     vima_amd/_abi.py next to the library, so that a deployment which ships only the package directory (+ the .so, or a VIMA_HIP_LIB
@@ -112,6 +120,16 @@ PROTOTYPES = {
     "vima_op_episode_fork": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_i32),
                                             ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), ctypes.c_int,
                                             vp]),
+    "vima_op_episode_pack": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.POINTER(c_i32), ctypes.c_int, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), vp, ctypes.c_int, vp]),
+    "vima_op_episode_unpack": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                              ctypes.POINTER(c_i32), ctypes.c_int, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), vp, ctypes.c_int, vp]),
+    "vima_decode_snapshot_size": (ctypes.c_int, [vp, ctypes.POINTER(c_i32), ctypes.c_int, ctypes.c_int, vp]),
+    "vima_decode_snapshot": (ctypes.c_int, [vp, ctypes.POINTER(c_i32), ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]),
+    "vima_decode_restore": (ctypes.c_int, [vp, ctypes.POINTER(c_i32), ctypes.c_int, vp, vp, vp]),
+    "vima_seq_decode_snapshot_size": (ctypes.c_int, [vp, ctypes.POINTER(c_i32), ctypes.c_int, ctypes.c_int, vp]),
+    "vima_seq_decode_snapshot": (ctypes.c_int, [vp, ctypes.POINTER(c_i32), ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]),
+    "vima_seq_decode_restore": (ctypes.c_int, [vp, ctypes.POINTER(c_i32), ctypes.c_int, vp, vp, vp]),
     "vima_action_head": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, vp]),
     "vima_action_embed": (ctypes.c_int, [vp, vp * 4, ctypes.c_int, vp, vp]),
     "vima_action_select": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.POINTER(c_f32), vp * 4, vp, vp, vp, vp]),

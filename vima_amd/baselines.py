@@ -189,6 +189,20 @@ class _BaselinePolicy(VIMAPolicy):
                                       "policies fork with seq_fork")
         return VIMAPolicy.fork_samples(self, source, prompt_token, prompt_token_mask)
 
+    def snapshot_samples(self, samples, prompt_token, prompt_token_mask, with_prompt=True):
+        """VIMAPolicy.snapshot_samples. VIMAFlamingoPolicy only; the decoder-only policies snapshot with `seq_snapshot` (their prompt is the cache prefix)."""
+        if self.KIND != "flamingo":
+            raise NotImplementedError("snapshot_samples needs the XAttnGPT episode caches (VIMAPolicy / VIMAFlamingoPolicy); the decoder-only "
+                                      "policies snapshot with seq_snapshot")
+        return VIMAPolicy.snapshot_samples(self, samples, prompt_token, prompt_token_mask, with_prompt)
+
+    def restore_samples(self, slots, snapshots, prompt_token, prompt_token_mask):
+        """VIMAPolicy.restore_samples. VIMAFlamingoPolicy only; the decoder-only policies restore with `seq_restore`."""
+        if self.KIND != "flamingo":
+            raise NotImplementedError("restore_samples needs the XAttnGPT episode caches (VIMAPolicy / VIMAFlamingoPolicy); the decoder-only "
+                                      "policies restore with seq_restore")
+        return VIMAPolicy.restore_samples(self, slots, snapshots, prompt_token, prompt_token_mask)
+
     def history_room(self) -> int:
         if self.KIND != "flamingo":
             raise NotImplementedError("history_room: VIMAPolicy / VIMAFlamingoPolicy only (the decoder-only policies have seq_history_room)")
@@ -353,6 +367,32 @@ class _BaselinePolicy(VIMAPolicy):
             raise _lib.VimaError("seq_fork: no running episode (call seq_prefill first)")
         src, src_p = self._fork_source(source, B)
         _lib.check(self._lib.vima_seq_decode_fork(self._handle, src_p, B, self._stream()))
+
+    def seq_snapshot(self, samples):
+        """Episode snapshots of the listed samples of the stepping batch -> list[EpisodeSnapshot] (vima_amd/episodes.py;
+        vima_seq_decode_snapshot): the sample's prefix rows [prompt | sep] and the rows of its env steps in compact time order, in every
+        layer's K/V cache, their key mask, position counter and restart flag -- wherever the ring holds the rows now. Nothing is recomputed,
+        the batch is not touched, there are no prompt tensors to carry: the prompt is the cache prefix. One upload and 2 launches whatever
+        the number of samples and layers. Snapshots live on the device; `.cpu()` / `.state_dict()` carry them anywhere."""
+        self._seq_only("seq_snapshot (VIMAFlamingoPolicy snapshots with snapshot_samples)")
+        if getattr(self, "_seq_t", None) is None:
+            raise _lib.VimaError("seq_snapshot: no running episode (call seq_prefill first)")
+        from . import episodes
+        return episodes.take(self, True, samples, True)
+
+    def seq_restore(self, slots, snapshots):
+        """Slot `slots[i]` of the stepping batch becomes the episode of `snapshots[i]` (vima_seq_decode_restore): a restart of the slot
+        followed by an install of the snapshot's rows in the cache rows the last `snapshot.steps` batch steps wrote -- at any later step, in
+        any slot, on any policy of the same kind, embed_dim, layers, precision element size, Q and prompt length (another batch size,
+        another ring phase). The slot's next `seq_step` consumes or ignores its row of `prev_action_token` as the snapshot's sample would
+        have. `steps_left()` of the slot is that of a sample restarted `snapshot.steps` batch steps ago. One snapshot may go to several
+        slots; CPU snapshots are moved to the device here. More steps than `seq_history_room()`: IndexError; a mismatched snapshot or a
+        slot listed twice: ValueError; nothing changes in either case."""
+        self._seq_only("seq_restore (VIMAFlamingoPolicy restores with restore_samples)")
+        if getattr(self, "_seq_t", None) is None:
+            raise _lib.VimaError("seq_restore: no running episode (call seq_prefill first)")
+        from . import episodes
+        episodes.put(self, True, slots, snapshots)
 
     def seq_history_room(self) -> int:
         """The largest T `seq_restart(..., history=)` accepts now: the most recent batch steps whose cache rows are all still there (without

@@ -1,5 +1,5 @@
 // Host bookkeeping of an episode cache: which cache rows the next env steps of a batch write, and which may be overwritten. Plain C++17, no HIP:
-// tests/episode_book_driver.cpp and tests/episode_fork_driver.cpp (forks) hold it on the CPU against the Python restatements.
+// tests/episode_book_driver.cpp and tests/episode_fork_driver.cpp (forks), tests/episode_snapshot_driver.cpp (snapshots) hold it on the CPU against the Python restatements.
 //
 // Rows [0, P0) of every sample's cache block are a fixed prefix (P0 = 0 for the XAttnGPT policies, prompt + separator for GPT / Gato); the rows
 // [P0, Lmax) behind it are ONE row index space for the whole batch, linear or a ring (options decode_ring / seq_ring). A call of T env steps is one
@@ -79,6 +79,17 @@ struct EpisodeBook {
   }
 
   void install(const std::vector<int>& list, int a) { for (int b : list) age[(size_t)b] = a; }
+
+  // Episode snapshots: the number n of env steps sample b's episode has taken -- the trailing slots whose advances sum to age[b] exactly (0 right
+  // after a restart); history_rows(n, .) then lists the episode's rows in compact time order. -1 when no suffix of the slot record sums to the age
+  // (the record was trimmed below the episode, which a legal ring never does). A snapshot is restored by install(list, history_rows(n, .)) on the
+  // book of that later moment, under the rule of every installed history: n <= room()
+  int steps_of(int b) const {
+    const int a = age[(size_t)b];
+    int n = 0, sum = 0;
+    for (int j = (int)slots.size() - 1; j >= 0 && sum < a; --j) { sum += slots[j].adv; ++n; }
+    return sum == a ? n : -1;
+  }
 
   // how many further single steps would succeed if sample b alone were never restarted: the single-step plan run forward
   int steps_left(int b) const {

@@ -197,6 +197,34 @@ int launch_episode_fork(const EpisodeForkArgs& a, bool is_bf16, hipStream_t st);
 // per-sample episode state of n (destination, source) pairs (DEVICE arrays): the whole key-mask row [Lmax], the position counter and the fresh flag
 int launch_episode_fork_state(const int* dsts, const int* srcs, int n, uint8_t* mask, int* poscnt, uint8_t* fresh, int Lmax, hipStream_t st);
 
+// ---- episode snapshots (episode_snapshot.hip): a sample's episode rows packed into / unpacked from a caller's payload, in compact time order
+// One job = nrows compact rows of one sample in EVERY layer of a cache [NL][B][L][N]: compact row k of the job is cache row map[map0 + k] (map ==
+// nullptr: row map0 + k) and sits at payload + layer * layer_stride + k * N elements. A work unit = rpc whole rows of one (layer, job); unit0 =
+// the units of the jobs in front of it (per layer), so that a flat unit number finds its job by bisection.
+struct SnapJob { long long payload, layer_stride; int sample, map0, nrows, unit0; };   // payload: DEVICE address, layer_stride in bytes
+constexpr int kSnapChunk = 1024;   // 16-byte vectors a workgroup keeps in flight: 256 threads x 4
+struct EpisodeSnapArgs {
+  void* cache = nullptr;            // [NL][B][L][N], operand type
+  const SnapJob* jobs = nullptr;    // DEVICE [n_jobs], nrows > 0, unit0 ascending
+  const int* map = nullptr;         // DEVICE row table of the call (every entry in [0, L): the caller checks), or nullptr
+  int n_jobs = 0, units = 0;        // units: of all jobs in one layer
+  int NL = 0, B = 0, L = 0, N = 0;
+  int D = 0;                        // > 0: the sample's block is head-major [N / D][L][D] (the prompt K / V cache under kv_headmajor); 0: rows [L][N]
+  int rpc = 1;                      // rows per unit: max(1, kSnapChunk / (16-byte vectors per row))
+};
+inline int snap_rows_per_unit(long long row_vectors) { return row_vectors >= kSnapChunk ? 1 : (int)(kSnapChunk / row_vectors); }
+// hipErrorInvalidValue (1) for a bad shape, 22 when N (or D) * sizeof(element) is no multiple of 16 or the cache is misaligned. The grid is
+// min(NL * units, 2048) workgroups. pack reads the cache and writes the payloads, unpack the reverse; jobs of one unpack call name distinct samples
+int launch_episode_pack(const EpisodeSnapArgs& a, bool is_bf16, hipStream_t st);
+int launch_episode_unpack(const EpisodeSnapArgs& a, bool is_bf16, hipStream_t st);
+// The per-sample state of n pairs, one workgroup each. The payload starts with 16 bytes {position counter, fresh flag, rows, 0} (int32), followed by
+// npre + nrows key-mask bytes: those of cache rows [0, npre) and of rows map[map0 + k]. Unpack first clears the slot's mask row over [lo, hi).
+struct SnapStateJob { long long payload; int sample, map0, nrows, npre; };
+int launch_episode_pack_state(const SnapStateJob* jobs, int n, const int* map, const uint8_t* mask, const int* poscnt, const uint8_t* fresh, int Lmax,
+                              hipStream_t st);
+int launch_episode_unpack_state(const SnapStateJob* jobs, int n, const int* map, uint8_t* mask, int* poscnt, uint8_t* fresh, int Lmax, int lo, int hi,
+                                hipStream_t st);
+
 // ---------------------------------------------------------------- attention
 // ViT: 5-token (S <= 8) multi-head attention on packed qkv T [M*S, 3*W] -> T [M*S, W]; head dim 32
 // out8 (bf16 mode): write the result as fp8 e4m3(value * inv8) [M*S, W] bytes INSTEAD of the operand-type output

@@ -247,6 +247,7 @@ struct VimaHandle {
   std::vector<int> restart_list;                 // host copy of the flagged sample indices (source of the upload)
   std::vector<int> hist_rowmap;                  // host copy of the history's compact row -> cache row map (source of the upload)
   std::vector<int> fork_table;                   // host copy of a fork's job table (vima_decode_fork / vima_seq_decode_fork; source of the upload)
+  std::vector<long long> snap_table;             // host copy of a snapshot / restore call's table (jobs, state jobs, row map; source of the upload)
   // hipGraph replay of the per-env-step entry points (option "graphs"): at small batch a step is ~1300 launches of
   // microsecond kernels and the HOST launch rate is the bound. The launch sequence of a call is captured the second time
   // the same (entry point, shapes, pointers, options, workspace generation) is seen and replayed afterwards.
@@ -3572,6 +3573,314 @@ int vima_op_episode_fork(VimaHandle* h, void* cache, int elem_bytes, int NL, int
   void* const caches[2] = {cache, nullptr};
   const int Ls[2] = {L, 0};
   return fork_launch(R, T, d, s, caches, Ls, NL, B, N, elem_bytes == 2, nullptr, nullptr, nullptr, 0);
+}
+
+// ---- episode snapshots (episode_snapshot.hip) -------------------------------------------------------------------------------------
+// The host side of one snapshot / restore call, kept in the handle (snap_table: the source of the ONE upload): [jobs of cache 0 | jobs of cache 1 |
+// state jobs | row map]. Cache 0 is the episode K | V cache under the call's row map, cache 1 the prompt K / V cache under the identity.
+namespace {
+struct SnapTable {
+  std::vector<SnapJob> jobs[2];
+  int units[2] = {0, 0};
+  std::vector<SnapStateJob> state;
+  std::vector<int> map;
+  void add(int c, const void* payload, long long layer_stride, int sample, int map0, int nrows, int rpc) {
+    if (nrows <= 0) return;
+    jobs[c].push_back(SnapJob{(long long)(uintptr_t)payload, layer_stride, sample, map0, nrows, units[c]});
+    units[c] += (nrows + rpc - 1) / rpc;
+  }
+};
+struct SnapCache { void* cache; int L, D; bool mapped; };
+// byte offsets of the payload's sections (include/vima_hip.h)
+struct SnapLayout { long long mask, rows, prompt, bytes, row_bytes; int R, npre; bool has_prompt; };
+SnapLayout snap_layout(const VimaEpisodeSnapshotInfo& I, bool seq) {
+  SnapLayout s{};
+  const long long R = std::max<long long>((long long)I.steps * (I.Q + 1) - 1, 0);
+  s.has_prompt = (I.flags & VIMA_SNAPSHOT_PROMPT) != 0;
+  s.R = (int)R;
+  s.npre = seq && s.has_prompt ? I.prompt_len : 0;
+  s.row_bytes = (long long)2 * I.embed_dim * I.elem_bytes;
+  s.mask = 16;
+  s.rows = s.mask + (s.npre + R + 15) / 16 * 16;
+  s.prompt = s.rows + (long long)I.layers * R * s.row_bytes;
+  s.bytes = s.prompt + (s.has_prompt ? (long long)I.layers * I.prompt_len * s.row_bytes : 0);
+  return s;
+}
+// a payload must be DEVICE memory: a kernel is never handed a pageable or unregistered host address
+int snap_device_ptr(const std::string& fn, const void* p, long long bytes, int i) {
+  const std::string what = fn + ": payload " + std::to_string(i);
+  if (!p) return fail(what + " is null", 22);
+  if (reinterpret_cast<uintptr_t>(p) & 15) return fail(what + " is not 16-byte aligned", 22);
+  hipPointerAttribute_t pa{};
+  if (hipPointerGetAttributes(&pa, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(what + " is not device memory (hipPointerGetAttributes does not know the address)", 22);
+  }
+  if (pa.type != hipMemoryTypeDevice) return fail(what + " is not device memory (host and managed addresses are refused)", 22);
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) == hipSuccess) {
+    if (reinterpret_cast<const char*>(p) + bytes > reinterpret_cast<const char*>(base) + size)
+      return fail(what + " is shorter than the " + std::to_string(bytes) + " bytes the call moves", 22);
+  } else {
+    (void)hipGetLastError();
+  }
+  return 0;
+}
+}  // namespace
+
+// uploads the table and launches: per cache with jobs one pack / unpack launch, then (mask given) the per-pair state -- at most 3 launches
+static int snap_launch(Run& R, const SnapTable& T, bool pack, const SnapCache c[2], int NL, int B, int N, bool is_bf16, uint8_t* mask, int* poscnt,
+                       uint8_t* fresh, int Lmax, int lo, int hi) {
+  VimaHandle* h = R.h;
+  static_assert(sizeof(SnapJob) == 32 && sizeof(SnapStateJob) == 24, "the table is laid out in 8-byte words");
+  const size_t nj0 = T.jobs[0].size(), nj1 = T.jobs[1].size(), ns = T.state.size(), nm = T.map.size();
+  const size_t o1 = nj0 * 4, os = o1 + nj1 * 4, om = os + ns * 3, words = om + (nm + 1) / 2;
+  if (words == 0) return 0;
+  std::vector<long long>& tab = h->snap_table;
+  tab.assign(words, 0);
+  if (nj0) memcpy(tab.data(), T.jobs[0].data(), nj0 * sizeof(SnapJob));
+  if (nj1) memcpy(tab.data() + o1, T.jobs[1].data(), nj1 * sizeof(SnapJob));
+  if (ns) memcpy(tab.data() + os, T.state.data(), ns * sizeof(SnapStateJob));
+  if (nm) memcpy(tab.data() + om, T.map.data(), nm * sizeof(int));
+  long long* dev = R.ws<long long>(words);
+  if (R.err) return R.err;
+  HIPCK(hipMemcpyAsync(dev, tab.data(), words * sizeof(long long), hipMemcpyHostToDevice, R.st));
+  const int* dmap = reinterpret_cast<const int*>(dev + om);
+  const int rpc = snap_rows_per_unit((long long)N * (is_bf16 ? 2 : 4) / 16);
+  for (int i = 0; i < 2; ++i) {
+    if (T.jobs[i].empty()) continue;
+    EpisodeSnapArgs a;
+    a.cache = c[i].cache; a.jobs = reinterpret_cast<const SnapJob*>(dev + (i ? o1 : 0)); a.map = c[i].mapped ? dmap : nullptr;
+    a.n_jobs = (int)T.jobs[i].size(); a.units = T.units[i]; a.NL = NL; a.B = B; a.L = c[i].L; a.N = N; a.D = c[i].D; a.rpc = rpc;
+    if (pack) OTHER(R, launch_episode_pack(a, is_bf16, R.st), "episode_pack");
+    else OTHER(R, launch_episode_unpack(a, is_bf16, R.st), "episode_unpack");
+  }
+  if (mask && ns) {
+    const SnapStateJob* sj = reinterpret_cast<const SnapStateJob*>(dev + os);
+    if (pack) OTHER(R, launch_episode_pack_state(sj, (int)ns, dmap, mask, poscnt, fresh, Lmax, R.st), "episode_pack_state");
+    else OTHER(R, launch_episode_unpack_state(sj, (int)ns, dmap, mask, poscnt, fresh, Lmax, lo, hi, R.st), "episode_unpack_state");
+  }
+  return R.err;
+}
+
+// the policy and running-batch checks of the six entry points
+static int snap_ready(VimaHandle* h, const std::string& fn, bool seq) {
+  if (seq) {
+    if (int e = seq_ready(h, fn.c_str())) return e;
+    if (!h->seq_live) return fail(fn + ": no running episode batch (start one with vima_seq_prefill)");
+  } else {
+    if (int e = check_ready(h)) return e;
+    if (h->cfg.policy_kind != VIMA_POLICY_VIMA && h->cfg.policy_kind != VIMA_POLICY_FLAMINGO)
+      return fail(fn + ": the handle's policy has no XAttnGPT episode caches (GPT / GATO handles use the vima_seq_decode_* form)");
+    if (!(h->ep_step >= 0 && h->kv_valid && h->kv_B == h->ep_B && h->kv_Lp == h->ep_Lp))
+      return fail(fn + ": no running episode batch (start one with vima_decode_step(step = 0))");
+  }
+  if (((size_t)2 * h->cfg.embed_dim * h->esz()) % 16) return fail(fn + ": rows of 2 x embed_dim elements must be a multiple of 16 bytes", 22);
+  if (!seq && h->kv_hm && ((size_t)(h->cfg.embed_dim / h->cfg.xattn_n_heads) * h->esz()) % 16)
+    return fail(fn + ": head-major prompt K / V pieces must be a multiple of 16 bytes", 22);
+  return 0;
+}
+
+static VimaEpisodeSnapshotInfo snap_info(const VimaHandle* h, bool seq, int steps, bool with_prompt) {
+  VimaEpisodeSnapshotInfo I{};
+  I.steps = steps; I.Q = h->ep_Q; I.embed_dim = h->cfg.embed_dim; I.layers = h->cfg.xf_n_layers;
+  I.prompt_len = seq ? h->book.P0 : h->ep_Lp; I.elem_bytes = (int)h->esz();
+  I.flags = with_prompt ? VIMA_SNAPSHOT_PROMPT : 0; I.policy_kind = h->cfg.policy_kind;
+  I.bytes = snap_layout(I, seq).bytes;
+  return I;
+}
+
+// fills infos[i] for samples[i]; refuses a sample outside the batch (22) or whose age no suffix of the slot record sums to (internal error)
+static int snap_infos(VimaHandle* h, const std::string& fn, bool seq, const int32_t* samples, int n, int with_prompt, VimaEpisodeSnapshotInfo* infos) {
+  if (!samples || !infos || n < 0) return fail(fn + ": null argument");
+  for (int i = 0; i < n; ++i) {
+    const int b = samples[i];
+    if (b < 0 || b >= h->ep_B) return fail(fn + ": sample " + std::to_string(b) + " is not a sample of the batch [0, " + std::to_string(h->ep_B) + ")", 22);
+    const int steps = h->book.steps_of(b);
+    if (steps < 0 || steps > h->book.room())
+      return fail(fn + ": internal error: no run of the last batch steps adds up to the age of sample " + std::to_string(b));
+    infos[i] = snap_info(h, seq, steps, with_prompt != 0);
+  }
+  return 0;
+}
+
+// row table of a call whose longest episode has nmax steps: [identity over the prefix (seq) | history_rows(nmax)]; -> the age history_rows returns
+static int snap_rowmap(VimaHandle* h, const std::string& fn, bool seq, int nmax, std::vector<int>& map) {
+  const int P0 = seq ? h->book.P0 : 0, Rmax = std::max(nmax * (h->ep_Q + 1) - 1, 0);
+  map.resize((size_t)P0 + Rmax);
+  for (int l = 0; l < P0; ++l) map[(size_t)l] = l;
+  if (nmax > 0) h->book.history_rows(nmax, map.data() + P0);
+  for (int l = P0; l < P0 + Rmax; ++l)
+    if (map[(size_t)l] < P0 || map[(size_t)l] >= h->ep_Lmax) return fail(fn + ": internal error: episode row outside the cache");
+  return 0;
+}
+
+static int snap_take(VimaHandle* h, const std::string& fn, bool seq, const int32_t* samples, int n, int with_prompt, void* const* payloads,
+                     const int64_t* capacity, VimaEpisodeSnapshotInfo* infos, hipStream_t st) {
+  if (int e = snap_ready(h, fn, seq)) return e;
+  if (!payloads || !capacity) return fail(fn + ": null argument");
+  std::vector<VimaEpisodeSnapshotInfo> I((size_t)std::max(n, 0));
+  if (int e = snap_infos(h, fn, seq, samples, n, with_prompt, I.data())) return e;
+  if (n == 0) return 0;
+  int nmax = 0;
+  for (int i = 0; i < n; ++i) {
+    nmax = std::max(nmax, I[(size_t)i].steps);
+    if (capacity[i] < I[(size_t)i].bytes)
+      return fail(fn + ": payload " + std::to_string(i) + " has room for " + std::to_string(capacity[i]) + " bytes, the snapshot takes " +
+                  std::to_string(I[(size_t)i].bytes), 22);
+    if (int e = snap_device_ptr(fn, payloads[i], I[(size_t)i].bytes, i)) return e;
+    for (int j = 0; j < i; ++j)
+      if (payloads[j] == payloads[i]) return fail(fn + ": payloads " + std::to_string(j) + " and " + std::to_string(i) + " are the same buffer", 22);
+  }
+  SnapTable T;
+  if (int e = snap_rowmap(h, fn, seq, nmax, T.map)) return e;
+  const int E = h->cfg.embed_dim, NL = h->cfg.xf_n_layers, Lmax = h->ep_Lmax, B = h->ep_B;
+  const int rpc = snap_rows_per_unit((long long)2 * E * (long long)h->esz() / 16), total = (int)T.map.size();
+  for (int i = 0; i < n; ++i) {
+    const SnapLayout s = snap_layout(I[(size_t)i], seq);
+    char* p = static_cast<char*>(payloads[i]);
+    T.add(0, p + s.rows, (long long)s.R * s.row_bytes, samples[i], total - s.R, s.R, rpc);
+    if (s.has_prompt) T.add(seq ? 0 : 1, p + s.prompt, (long long)I[(size_t)i].prompt_len * s.row_bytes, samples[i], 0, I[(size_t)i].prompt_len, rpc);
+    T.state.push_back(SnapStateJob{(long long)(uintptr_t)p, samples[i], total - s.R, s.R, s.npre});
+  }
+  Run R{h, st};
+  const SnapCache c[2] = {{h->ep_kv, Lmax, 0, true}, {h->kv_cache, h->ep_Lp, h->kv_hm ? E / h->cfg.xattn_n_heads : 0, false}};
+  if (snap_launch(R, T, true, c, NL, B, 2 * E, h->bf16, h->ep_mask, h->ep_poscnt, h->ep_fresh, Lmax, 0, 0)) return R.err;
+  for (int i = 0; i < n; ++i) infos[i] = I[(size_t)i];
+  return 0;
+}
+
+static int snap_restore(VimaHandle* h, const std::string& fn, bool seq, const int32_t* slots, int n, const void* const* payloads,
+                        const VimaEpisodeSnapshotInfo* infos, hipStream_t st) {
+  if (int e = snap_ready(h, fn, seq)) return e;
+  if (!slots || !payloads || !infos || n < 0) return fail(fn + ": null argument");
+  if (n == 0) return 0;
+  const int B = h->ep_B, room = h->book.room();
+  int nmax = 0;
+  for (int i = 0; i < n; ++i) {
+    const VimaEpisodeSnapshotInfo& I = infos[i];
+    const std::string who = fn + ": snapshot " + std::to_string(i);
+    if (slots[i] < 0 || slots[i] >= B) return fail(fn + ": slot " + std::to_string(slots[i]) + " is not a sample of the batch [0, " + std::to_string(B) + ")", 22);
+    for (int j = 0; j < i; ++j)
+      if (slots[j] == slots[i]) return fail(fn + ": slot " + std::to_string(slots[i]) + " is listed twice", 22);
+    const VimaEpisodeSnapshotInfo want = snap_info(h, seq, I.steps, (I.flags & VIMA_SNAPSHOT_PROMPT) != 0);
+    if (I.policy_kind != want.policy_kind) return fail(who + " was taken from another policy kind", 22);
+    if (I.embed_dim != want.embed_dim || I.layers != want.layers)
+      return fail(who + " has embed_dim " + std::to_string(I.embed_dim) + " and " + std::to_string(I.layers) + " layers, the handle " +
+                  std::to_string(want.embed_dim) + " and " + std::to_string(want.layers), 22);
+    if (I.elem_bytes != want.elem_bytes)
+      return fail(who + " holds " + std::to_string(I.elem_bytes) + "-byte elements, the handle's caches " + std::to_string(want.elem_bytes) + "-byte (precision)", 22);
+    if (I.Q != want.Q) return fail(who + " has Q = " + std::to_string(I.Q) + ", the running batch Q = " + std::to_string(want.Q), 22);
+    if (I.prompt_len != want.prompt_len)
+      return fail(who + " has a prompt of " + std::to_string(I.prompt_len) + " rows, the running batch " + std::to_string(want.prompt_len) + " (Lp)", 22);
+    if (I.steps < 0 || (I.flags & ~VIMA_SNAPSHOT_PROMPT) || I.bytes != want.bytes) return fail(who + ": the info is not one this library wrote", 22);
+    if (I.steps > room)
+      return fail(who + " holds " + std::to_string(I.steps) + " steps and does not fit: room for " + std::to_string(room) +
+                  " (the batch steps whose cache rows are all still there)", 34);
+    if (int e = snap_device_ptr(fn, payloads[i], I.bytes, i)) return e;
+    nmax = std::max(nmax, I.steps);
+  }
+  SnapTable T;
+  if (int e = snap_rowmap(h, fn, seq, nmax, T.map)) return e;
+  const int E = h->cfg.embed_dim, NL = h->cfg.xf_n_layers, Lmax = h->ep_Lmax, P0 = seq ? h->book.P0 : 0;
+  const int rpc = snap_rows_per_unit((long long)2 * E * (long long)h->esz() / 16), total = (int)T.map.size();
+  std::vector<int> ages((size_t)n), tmp(T.map.size() + 1);
+  for (int i = 0; i < n; ++i) {
+    const SnapLayout s = snap_layout(infos[i], seq);
+    const char* p = static_cast<const char*>(payloads[i]);
+    ages[(size_t)i] = infos[i].steps > 0 ? h->book.history_rows(infos[i].steps, tmp.data()) : 0;
+    T.add(0, p + s.rows, (long long)s.R * s.row_bytes, slots[i], total - s.R, s.R, rpc);
+    if (s.has_prompt) T.add(seq ? 0 : 1, p + s.prompt, (long long)infos[i].prompt_len * s.row_bytes, slots[i], 0, infos[i].prompt_len, rpc);
+    T.state.push_back(SnapStateJob{(long long)(uintptr_t)p, slots[i], total - s.R, s.R, s.npre});
+  }
+  Run R{h, st};
+  const SnapCache c[2] = {{h->ep_kv, Lmax, 0, true}, {h->kv_cache, h->ep_Lp, h->kv_hm ? E / h->cfg.xattn_n_heads : 0, false}};
+  // the restart of the slot: its old episode's keys are masked -- everywhere behind the prefix (the ring's written part; rows beyond it are never read)
+  if (snap_launch(R, T, false, c, NL, B, 2 * E, h->bf16, h->ep_mask, h->ep_poscnt, h->ep_fresh, Lmax, P0, seq ? h->book.written_end() : Lmax)) return R.err;
+  for (int i = 0; i < n; ++i) h->book.install(std::vector<int>{slots[i]}, ages[(size_t)i]);
+  return 0;
+}
+
+int vima_decode_snapshot_size(VimaHandle* h, const int32_t* samples, int n, int with_prompt, VimaEpisodeSnapshotInfo* infos) {
+  if (int e = snap_ready(h, "vima_decode_snapshot_size", false)) return e;
+  return snap_infos(h, "vima_decode_snapshot_size", false, samples, n, with_prompt, infos);
+}
+
+int vima_decode_snapshot(VimaHandle* h, const int32_t* samples, int n, int with_prompt, void* const* payloads, const int64_t* capacity,
+                         VimaEpisodeSnapshotInfo* infos, vima_stream_t stream) {
+  return snap_take(h, "vima_decode_snapshot", false, samples, n, with_prompt, payloads, capacity, infos, (hipStream_t)stream);
+}
+
+int vima_decode_restore(VimaHandle* h, const int32_t* slots, int n, const void* const* payloads, const VimaEpisodeSnapshotInfo* infos,
+                        vima_stream_t stream) {
+  return snap_restore(h, "vima_decode_restore", false, slots, n, payloads, infos, (hipStream_t)stream);
+}
+
+int vima_seq_decode_snapshot_size(VimaHandle* h, const int32_t* samples, int n, int with_prompt, VimaEpisodeSnapshotInfo* infos) {
+  if (int e = snap_ready(h, "vima_seq_decode_snapshot_size", true)) return e;
+  return snap_infos(h, "vima_seq_decode_snapshot_size", true, samples, n, with_prompt, infos);
+}
+
+int vima_seq_decode_snapshot(VimaHandle* h, const int32_t* samples, int n, int with_prompt, void* const* payloads, const int64_t* capacity,
+                             VimaEpisodeSnapshotInfo* infos, vima_stream_t stream) {
+  return snap_take(h, "vima_seq_decode_snapshot", true, samples, n, with_prompt, payloads, capacity, infos, (hipStream_t)stream);
+}
+
+int vima_seq_decode_restore(VimaHandle* h, const int32_t* slots, int n, const void* const* payloads, const VimaEpisodeSnapshotInfo* infos,
+                            vima_stream_t stream) {
+  return snap_restore(h, "vima_seq_decode_restore", true, slots, n, payloads, infos, (hipStream_t)stream);
+}
+
+// vima_op_episode_pack / vima_op_episode_unpack behind one body
+static int op_episode_snap(VimaHandle* h, const char* fn, bool pack, void* cache, int elem_bytes, int NL, int B, int L, int N, int D,
+                           const int32_t* rowmap, int n_map, const int32_t* samples, const int32_t* nrows, const void* const* payloads, int n_jobs,
+                           hipStream_t st) {
+  if (int e = op_begin(h, fn)) return e;
+  OP_REQ(cache && samples && nrows && payloads, "null argument");
+  OP_REQ(elem_bytes == 2 || elem_bytes == 4, "elem_bytes must be 4 (fp32) or 2 (bf16)");
+  OP_REQ(NL > 0 && B > 0 && L > 0 && N > 0 && D >= 0 && n_map >= 0 && n_jobs >= 0, "NL, B, L and N must be positive, D, n_map and n_jobs not negative");
+  if (((long long)N * elem_bytes) % 16 || ((uintptr_t)cache & 15))
+    return fail(std::string(fn) + ": rows of N elements must be a multiple of 16 bytes and the cache 16-byte aligned", 22);
+  if (D > 0 && (((long long)D * elem_bytes) % 16 || N % D))
+    return fail(std::string(fn) + ": head-major pieces of D elements must be a multiple of 16 bytes and divide N", 22);
+  OP_REQ(rowmap || n_map <= L, "the identity map holds at most L rows");
+  SnapTable T;
+  for (int l = 0; l < n_map && rowmap; ++l) {
+    if (rowmap[l] < 0 || rowmap[l] >= L) return fail(std::string(fn) + ": rowmap[" + std::to_string(l) + "] = " + std::to_string(rowmap[l]) + " is not a row of the cache [0, " + std::to_string(L) + ")", 22);
+    T.map.push_back(rowmap[l]);
+  }
+  const long long row_bytes = (long long)N * elem_bytes;
+  const int rpc = snap_rows_per_unit(row_bytes / 16);
+  std::vector<char> seen((size_t)B, 0);
+  for (int j = 0; j < n_jobs; ++j) {
+    OP_REQ(samples[j] >= 0 && samples[j] < B, "a sample is not a sample of the cache");
+    OP_REQ(nrows[j] >= 0 && nrows[j] <= n_map, "a job moves at most n_map rows");
+    if (!pack) {
+      if (seen[(size_t)samples[j]]) return fail(std::string(fn) + ": sample " + std::to_string(samples[j]) + " is listed twice", 22);
+      seen[(size_t)samples[j]] = 1;
+    }
+    if (nrows[j] == 0) continue;
+    if (int e = snap_device_ptr(fn, payloads[j], (long long)NL * nrows[j] * row_bytes, j)) return e;
+    T.add(0, payloads[j], (long long)nrows[j] * row_bytes, samples[j], n_map - nrows[j], nrows[j], rpc);
+  }
+  if (T.jobs[0].empty()) return 0;
+  if (int e = snap_device_ptr(std::string(fn) + " (cache)", cache, (long long)NL * B * L * row_bytes, 0)) return e;
+  Run R{h, st};
+  const SnapCache c[2] = {{cache, L, D, rowmap != nullptr}, {nullptr, 0, 0, false}};
+  return snap_launch(R, T, pack, c, NL, B, N, elem_bytes == 2, nullptr, nullptr, nullptr, 0, 0, 0);
+}
+
+int vima_op_episode_pack(VimaHandle* h, const void* cache, int elem_bytes, int NL, int B, int L, int N, int D, const int32_t* rowmap, int n_map,
+                         const int32_t* samples, const int32_t* nrows, void* const* payloads, int n_jobs, vima_stream_t stream) {
+  return op_episode_snap(h, "vima_op_episode_pack", true, const_cast<void*>(cache), elem_bytes, NL, B, L, N, D, rowmap, n_map, samples, nrows,
+                         const_cast<const void* const*>(payloads), n_jobs, (hipStream_t)stream);
+}
+
+int vima_op_episode_unpack(VimaHandle* h, void* cache, int elem_bytes, int NL, int B, int L, int N, int D, const int32_t* rowmap, int n_map,
+                           const int32_t* samples, const int32_t* nrows, const void* const* payloads, int n_jobs, vima_stream_t stream) {
+  return op_episode_snap(h, "vima_op_episode_unpack", false, cache, elem_bytes, NL, B, L, N, D, rowmap, n_map, samples, nrows, payloads, n_jobs,
+                         (hipStream_t)stream);
 }
 #undef OP_REQ
 

@@ -562,6 +562,60 @@ class VIMAPolicy(nn.Module):
             prompt_token_mask[dst] = prompt_token_mask[from_]
         return prompt_token, prompt_token_mask
 
+    def snapshot_samples(self, samples, prompt_token: torch.Tensor, prompt_token_mask: torch.Tensor, with_prompt: bool = True):
+        """Episode snapshots of the listed samples of the batch that is stepping with `forward_step` -> list[EpisodeSnapshot]
+        (vima_amd/episodes.py; vima_decode_snapshot). A snapshot is the sample's episode in compact time order -- the K/V rows of its env
+        steps in every layer, their key mask, position counter and restart flag, wherever the ring holds them now -- and, with
+        `with_prompt`, its prompt K/V block, its `prompt_token[:, b]` column and its `prompt_token_mask[b]` row. Nothing is recomputed and
+        the batch is not touched. `with_prompt=False` is the cheap form for backtracking inside one prompt group: on restore the slot's
+        prompt K/V and the caller's prompt columns stay as they are, and the caller vouches that they are this episode's.
+        Snapshots live on the device; `.cpu()`, `.state_dict()` and `torch.save` carry them anywhere. One upload and at most 3 launches,
+        whatever the number of samples and layers; no host synchronisation."""
+        from . import episodes
+        self._ready()
+        snaps = episodes.take(self, False, samples, with_prompt)
+        if with_prompt:
+            prompt_token = prompt_token.to(self._device)
+            prompt_token_mask = prompt_token_mask.to(self._device)
+            for b, s in zip(episodes._index_list(samples, "snapshot_samples"), snaps):
+                s.prompt_token, s.prompt_token_mask = prompt_token[:, b].clone(), prompt_token_mask[b].clone()
+        return snaps
+
+    def restore_samples(self, slots, snapshots, prompt_token: torch.Tensor, prompt_token_mask: torch.Tensor):
+        """Slot `slots[i]` of the batch that is stepping with `forward_step` becomes the episode of `snapshots[i]` (vima_decode_restore): a
+        restart of the slot followed by an install of the snapshot's rows in the cache rows the last `snapshot.steps` batch steps wrote.
+        Works at any later step, in any slot, and on any policy with the same kind, embed_dim, layers, precision element size, Q and
+        prompt length -- another batch size, another ring phase, the other prompt K/V layout. Nothing is recomputed. The slot's next
+        `forward_step` consumes or ignores its row of the previous-action token as the snapshot's sample would have, and returns what that
+        sample would have returned (up to the summation order of the attention over differently placed rows; at the same moment: bit for
+        bit). `steps_left()` of the slot is that of a sample restarted `snapshot.steps` batch steps ago.
+
+        Each pair has its own step count; one snapshot may go to several slots; CPU snapshots are moved to the device here. A snapshot
+        with more steps than `history_room()`: IndexError; a snapshot that does not match the policy or the running batch, or a slot
+        listed twice: ValueError; nothing changes in either case. Snapshots taken with the prompt overwrite `prompt_token[:, slot]` and
+        `prompt_token_mask[slot]` -- in place where the tensors already live on the device -- and the UPDATED tensors are returned as
+        (prompt_token, prompt_token_mask); prompt-less snapshots leave them alone. The step graphs captured under option `graphs` stay
+        valid."""
+        from . import episodes
+        self._ready()
+        dev = self._device
+        if prompt_token.stride(-1) != 1:
+            prompt_token = prompt_token.contiguous()
+        prompt_token = prompt_token.to(dev)
+        prompt_token_mask = prompt_token_mask.to(device=dev)
+        snaps = [snapshots] if isinstance(snapshots, episodes.EpisodeSnapshot) else list(snapshots)
+        for s in snaps:
+            if s.has_prompt and (s.prompt_token is None or tuple(s.prompt_token.shape) != (prompt_token.shape[0], prompt_token.shape[2])):
+                raise ValueError(f"restore_samples: the snapshot's prompt_token column is {None if s.prompt_token is None else tuple(s.prompt_token.shape)}, "
+                                 f"the batch's prompts are [{prompt_token.shape[0]}, B, {prompt_token.shape[2]}]")
+        self._kv_key = None
+        slots, snaps = episodes.put(self, False, slots, snaps)
+        for d, s in zip(slots, snaps):
+            if s.has_prompt:
+                prompt_token[:, d] = s.prompt_token.to(prompt_token.dtype)
+                prompt_token_mask[d] = s.prompt_token_mask.to(prompt_token_mask.dtype)
+        return prompt_token, prompt_token_mask
+
     def history_room(self) -> int:
         """The largest T `restart_samples(..., history=)` accepts now: the number of most recent batch steps whose cache rows are all still
         there (without `decode_ring`: the steps taken since step 0). Host bookkeeping only."""
