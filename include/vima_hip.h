@@ -453,7 +453,7 @@ int vima_seq_decode_fork(VimaHandle* h, const int32_t* source /* HOST [B] */, in
  * R = max(n (Q + 1) - 1, 0) rows [o_0 (Q), a_0, o_1 (Q), ...] of every layer's episode K | V cache, in the order of EpisodeBook::history_rows(n),
  * their key-mask bytes, the position counter and the fresh flag; and (flag VIMA_SNAPSHOT_PROMPT) the sample's prompt: vima_decode_snapshot stores its
  * block of every layer's prompt K / V cache ROW-MAJOR [layers][Lp][2E] whatever layout the handle's cache has (option kv_headmajor; converted as
- * kv_gather_kernel does, and back as kv_scatter_kernel does), vima_seq_decode_snapshot the prefix rows [0, P0 = Lp + 1) of the episode cache and
+ * kv_rows_kernel does from the cache, and back as it does to the cache), vima_seq_decode_snapshot the prefix rows [0, P0 = Lp + 1) of the episode cache and
  * their mask bytes. A snapshot without the prompt leaves the destination's prompt K / V block (prefix rows) untouched on restore: the caller vouches
  * that the slot holds this prompt -- the cheap form for backtracking inside one prompt group.
  *

@@ -1,13 +1,14 @@
 """CPU references, input builders, case tables and gates shared by tests/test_seq_norm_reference.py (which pins all of this on the CPU) and
-tests/test_seq_norm_gpu.py (which holds the norm and sequence-assembly kernels of elementwise.hip / baseline_kernels.hip against it, one
-launch per case, per output element):
+tests/test_seq_norm_gpu.py (which holds the norm and sequence-assembly kernels of elementwise.hip / baseline_kernels.hip / episode_rows.hip
+against it, one launch per case, per output element):
 
   layernorm_kernel<T>, <bf16, bf16>, layernorm_rows2_kernel<1..4>, layernorm2_kernel, rms_stats_kernel              (vima_op_norm)
   prompt_assemble_kernel, prompt_assemble_stats_kernel                                                               (vima_op_prompt_assemble)
-  dec_embed_kernel, dec_embed_chunk_kernel at T = 1, restart_samples_kernel, prompt_pos_kernel, gather_pred_kernel  (vima_op_dec_embed, _step ...)
-  action_l1_kernel, add_row_table_kernel, rows_to_headmajor_kernel, kv_scatter_kernel                               (vima_op_action_l1 ...)
-  seq_embed_kernel, seq_embed_prefill_kernel, seq_embed_chunk_kernel at T = 1 (vima_op_seq_embed_step), seq_restart_kernel, seq_kv_store_kernel,
-  broadcast_rows_kernel
+  dec_embed_kernel, dec_embed_chunk_kernel at T = 1, prompt_pos_kernel, gather_pred_kernel                           (vima_op_dec_embed, _step ...)
+  action_l1_kernel, add_row_table_kernel, broadcast_rows_kernel                                                      (vima_op_action_l1 ...)
+  seq_embed_kernel, also as the prefill (vima_op_seq_embed_prefill), seq_embed_chunk_kernel at T = 1 (vima_op_seq_embed_step)
+  kv_rows_kernel in three of its forms (vima_op_rows_to_headmajor, vima_op_kv_scatter, vima_op_seq_kv_store), episode_restart_kernel with and
+  without a position counter (vima_op_restart_samples, vima_op_seq_restart)
 
 References are fp64 (norms, ssq, action_l1) or exact fp32 (everything else: a gather plus ONE IEEE fp32 add, which torch on the CPU performs
 with the same bits), and are written with cumsum / cat / index_select / reshape / permute only -- none of the kernels' index arithmetic.

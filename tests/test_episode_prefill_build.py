@@ -121,26 +121,29 @@ def test_the_chunked_ring_schedule_has_what_its_test_is_about():
 
 @needs_hipcc
 def test_new_kernels_compile_without_scratch():
-    """Every new kernel of elementwise.hip, both operand types, cross-compiles for gfx950 with scratch size 0. Figures of this record (ROCm 7.2
-    hipcc), VGPRs / LDS bytes per block, all at occupancy 8 waves per SIMD: dec_embed_chunk_kernel 22 / 3072 (float and bf16),
-    gather_pred_kernel (with the lead argument) 14 / 0, kv_gather_kernel 12 / 0, kv_scatter_rows_kernel 12 / 0, history_install_kernel 22 / 1024,
-    mask_rows_gather_kernel 4 / 0."""
-    out = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-result",
-                          "--cuda-device-only", "-S", os.path.join(ROOT, "vima_amd", "csrc", "elementwise.hip"), "-o", os.devnull,
-                          "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    res, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and name:
-            res[name][m.group(1).split(" ")[0]] = int(m.group(2))
-    want = {"dec_embed_chunk_kernel": 2, "gather_pred_kernel": 1, "kv_gather_kernel": 2, "kv_scatter_rows_kernel": 2, "history_install_kernel": 1,
-            "mask_rows_gather_kernel": 1}
+    """Every kernel of the episode prefill, both operand types where it has them, cross-compiles for gfx950 with scratch size 0: those of
+    elementwise.hip and the ones the two policy families share (episode_rows.hip; kv_rows_kernel knows no operand type, so it has ONE
+    instantiation for the gather, the scatter and the row-map scatter alike). Figures of this record (ROCm 7.2 hipcc), VGPRs / LDS bytes per
+    block, all at occupancy 8 waves per SIMD: dec_embed_chunk_kernel 22 / 3072 (float and bf16), gather_pred_kernel (with the lead argument)
+    14 / 0, mask_rows_gather_kernel 4 / 0, kv_rows_kernel 8 / 0, episode_restart_kernel 32 / 0, episode_install_kernel 32 / 16."""
+    res = {}
+    for src in ("elementwise.hip", "episode_rows.hip"):
+        out = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-result",
+                              "--cuda-device-only", "-S", os.path.join(ROOT, "vima_amd", "csrc", src), "-o", os.devnull,
+                              "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-2000:]
+        name = None
+        for line in out.stderr.splitlines():
+            m = re.search(r"Function Name: (\S+)", line)
+            if m:
+                name = m.group(1)
+                res[name] = {}
+                continue
+            m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]): (\d+)", line)
+            if m and name:
+                res[name][m.group(1).split(" ")[0]] = int(m.group(2))
+    want = {"dec_embed_chunk_kernel": 2, "gather_pred_kernel": 1, "mask_rows_gather_kernel": 1, "kv_rows_kernel": 1, "episode_restart_kernel": 1,
+            "episode_install_kernel": 1}
     for kernel, n in want.items():
         found = {k: v for k, v in res.items() if kernel in k}
         assert len(found) == n, (kernel, sorted(found))

@@ -1,4 +1,4 @@
-"""The norm and sequence-assembly kernels of elementwise.hip / baseline_kernels.hip, one launch each through the operator entry points
+"""The norm and sequence-assembly kernels of elementwise.hip / baseline_kernels.hip / episode_rows.hip, one launch each through the operator entry points
 (vima_op_norm, vima_op_prompt_assemble, vima_op_dec_embed, ... -- include/vima_hip.h), per output element against
 tests/seq_norm_reference.py (references, cases and gates; tests/test_seq_norm_reference.py pins them on the CPU).
 

@@ -121,24 +121,27 @@ def test_the_chunked_ring_schedule_has_what_its_test_is_about(kind, wraps):
 
 @needs_hipcc
 def test_new_kernels_compile_without_scratch():
-    """The new kernels of baseline_kernels.hip cross-compile for gfx950 with scratch size 0. Figures of this record (ROCm 7.2 hipcc), VGPRs / LDS
-    bytes per block: seq_embed_chunk_kernel 31 / 0 (float and bf16); seq_history_install_kernel 32 / 16; seq_embed_kernel (with the list argument)
-    22 / 0 (float and bf16)."""
-    out = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-result",
-                          "--cuda-device-only", "-S", os.path.join(ROOT, "vima_amd", "csrc", "baseline_kernels.hip"), "-o", os.devnull,
-                          "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    res, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and name:
-            res[name][m.group(1).split(" ")[0]] = int(m.group(2))
-    want = {"seq_embed_chunk_kernel": 2, "seq_history_install_kernel": 1, "16seq_embed_kernel": 2}
+    """The kernels of the baselines' episode prefill cross-compile for gfx950 with scratch size 0: those of baseline_kernels.hip and the history
+    install both policy families share (episode_rows.hip). Figures of this record (ROCm 7.2 hipcc), VGPRs / LDS bytes per block:
+    seq_embed_chunk_kernel 31 / 0 (float and bf16); episode_install_kernel 32 / 16; seq_embed_kernel (with the list and the episode-state
+    arguments: it is the prefill too) 26 / 0 (float and bf16)."""
+    res = {}
+    for src in ("baseline_kernels.hip", "episode_rows.hip"):
+        out = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-result",
+                              "--cuda-device-only", "-S", os.path.join(ROOT, "vima_amd", "csrc", src), "-o", os.devnull,
+                              "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-2000:]
+        name = None
+        for line in out.stderr.splitlines():
+            m = re.search(r"Function Name: (\S+)", line)
+            if m:
+                name = m.group(1)
+                res[name] = {}
+                continue
+            m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]): (\d+)", line)
+            if m and name:
+                res[name][m.group(1).split(" ")[0]] = int(m.group(2))
+    want = {"seq_embed_chunk_kernel": 2, "episode_install_kernel": 1, "16seq_embed_kernel": 2}
     for kernel, n in want.items():
         found = {k: v for k, v in res.items() if kernel in k}
         assert len(found) == n, (kernel, sorted(found))

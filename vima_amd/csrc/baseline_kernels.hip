@@ -1,6 +1,7 @@
 // Token plumbing of the reference's BASELINE policies (VIMAGPTPolicy / VIMAGatoPolicy / VIMAFlamingoPolicy; SURVEY.md 8(f)
 // row 4): whole 64x128 RGB frames through a rectangular ViT with 32x32 patches, the decoder-only sequence assembly, and its incremental
-// form for rollouts (prefill / step / restart embedding and the K | V copy into the episode cache).
+// form for rollouts (prefill / step embedding; the episode-cache plumbing shared with XAttnGPT -- row copies, restart, history install -- is in
+// episode_rows.hip).
 // All HBM-bound elementwise work (one pass over the data, 16-byte accesses); the arithmetic of these policies runs on the
 // same GEMM / attention / LayerNorm kernels as the VIMA hot path.
 #include "kernels.h"
@@ -110,13 +111,19 @@ __global__ __launch_bounds__(256) void broadcast_rows_kernel(const float* __rest
 //   else j = l-Lp-1, t = j / (Q+1), s = j % (Q+1): s < Q -> obs token (t, b, s), else action token (t, b); position nv + 1 + j
 // with nv = number of valid prompt tokens of sample b. One wave per row; nv is recomputed per wave (Lp <= 512 bytes).
 // list (optional, DEVICE array [B]): sample b of the call reads row list[b] of prompt / pmask; obs_tok / act_tok stay indexed by b.
+// Incremental decoding (vima_seq_prefill / vima_seq_decode_step / vima_seq_decode_restart) feeds this sequence in pieces -- rows [0, Lp] once, then
+// the rows of one env step per call (seq_embed_chunk_kernel) -- and every layer's K | V stay in an episode cache of n_pos rows per sample. The
+// episode state lives on the device: cache_mask [B][n_pos] (the key mask, at the cache's row stride), posbase[b] = the position id of sample b's
+// next valid row, fresh[b] = 1 after a restart (the sample's next action slot is absent). The prefill is this kernel at L = Lp + 1 with cache_mask /
+// posbase given: rows l <= Lp also write cache_mask[list[b]][l] (row stride cache_ld) and the separator row posbase[list[b]] = nv + 1.
 // ---------------------------------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void seq_embed_kernel(const float* __restrict__ prompt, long long sb, long long sl,
                                                         const uint8_t* __restrict__ pmask, const float* __restrict__ sep,
                                                         const float* __restrict__ obs_tok, const float* __restrict__ act_tok,
                                                         const float* __restrict__ pos_table, int n_pos, float* x32, T* xT,
-                                                        uint8_t* mask, const int* __restrict__ list, int B, int L, int Lp, int Q, int E) {
+                                                        uint8_t* mask, const int* __restrict__ list, int B, int L, int Lp, int Q, int E,
+                                                        uint8_t* cache_mask, int* posbase, int cache_ld) {
   const int lane = threadIdx.x & 63;
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= (long long)B * L) return;
@@ -149,57 +156,12 @@ __global__ __launch_bounds__(256) void seq_embed_kernel(const float* __restrict_
     *reinterpret_cast<float4*>(x32 + row * E + c) = o;
     store4(xT + row * E + c, o);
   }
-  if (lane == 0) mask[row] = m;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Incremental decoding of the decoder-only policies (vima_seq_prefill / vima_seq_decode_step / vima_seq_decode_restart): the sequence of
-// seq_embed_kernel is fed in pieces -- rows [0, Lp] once, then the rows of one env step per call -- and every layer's K | V stay in an episode
-// cache of n_pos rows per sample. The episode state lives on the device: cache_mask [B][n_pos] (the key mask, at the cache's row stride),
-// posbase[b] = the position id of sample b's next valid row, fresh[b] = 1 after a restart (the sample's next action slot is absent).
-// ---------------------------------------------------------------------------------------------------------------
-
-// The prompt + separator part of seq_embed_kernel, L = Lp + 1 rows per sample; one wave per row. Output block r (rows r L .. of x32 / xT / mask)
-// is computed from sample b = list ? list[r] : r of prompt / pmask (the batched restart prefills a compact list of samples) and the episode
-// state of sample b is written: cache_mask[b][0 .. Lp] and posbase[b] = nv + 1.
-template <typename T>
-__global__ __launch_bounds__(256) void seq_embed_prefill_kernel(const float* __restrict__ prompt, long long sb, long long sl,
-                                                                const uint8_t* __restrict__ pmask, const float* __restrict__ sep,
-                                                                const float* __restrict__ pos_table, int n_pos, float* x32, T* xT,
-                                                                uint8_t* mask, uint8_t* cache_mask, int* posbase,
-                                                                const int* __restrict__ list, int n, int Lp, int E) {
-  const int lane = threadIdx.x & 63;
-  const int L = Lp + 1;
-  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= (long long)n * L) return;
-  const int r = (int)(row / L), l = (int)(row % L);
-  const int b = list ? list[r] : r;
-  float cnt = 0.f;
-  for (int j = lane; j < Lp; j += 64) cnt += pmask[(long long)b * Lp + j] ? 1.f : 0.f;
-  const int nv = (int)wave_sum(cnt);
-  const float* src;
-  int pos;
-  uint8_t m = 1;
-  if (l < Lp) {
-    src = prompt + (long long)b * sb + (long long)l * sl;
-    pos = l < nv ? l : nv - 1;
-    m = pmask[(long long)b * Lp + l] ? 1 : 0;
-  } else {
-    src = sep;
-    pos = nv;
-  }
-  pos = pos < 0 ? 0 : (pos >= n_pos ? n_pos - 1 : pos);
-  for (int c = lane * 4; c < E; c += 256) {
-    const float4 a = *reinterpret_cast<const float4*>(src + c);
-    const float4 p = *reinterpret_cast<const float4*>(pos_table + (long long)pos * E + c);
-    const float4 o = make_float4(a.x + p.x, a.y + p.y, a.z + p.z, a.w + p.w);
-    *reinterpret_cast<float4*>(x32 + row * E + c) = o;
-    store4(xT + row * E + c, o);
-  }
   if (lane == 0) {
     mask[row] = m;
-    cache_mask[(long long)b * n_pos + l] = m;
-    if (l == Lp) posbase[b] = nv + 1;
+    if (cache_mask && l <= Lp) {
+      cache_mask[(long long)bp * cache_ld + l] = m;
+      if (l == Lp) posbase[bp] = nv + 1;
+    }
   }
 }
 
@@ -247,57 +209,6 @@ __global__ __launch_bounds__(256) void seq_embed_chunk_kernel(const float* __res
   }
 }
 
-// Per-sample restart: the listed samples forget their history rows [lo, hi) (every cached key of the old episode masked; rows [0, lo) are
-// rewritten by the prefill of the new prompt) and their next action slot is marked absent. One workgroup per listed sample.
-__global__ __launch_bounds__(256) void seq_restart_kernel(const int* __restrict__ list, uint8_t* cache_mask, uint8_t* fresh, int lo, int hi,
-                                                          int n_pos) {
-  const int b = list[blockIdx.x];
-  for (int i = lo + threadIdx.x; i < hi; i += 256) cache_mask[(long long)b * n_pos + i] = 0;
-  if (threadIdx.x == 0) fresh[b] = 1;
-}
-
-// The episode state of an installed history (vima_seq_decode_restart_history), one workgroup per listed sample b = list[r]: what seq_restart_kernel
-// does to the old episode (rows [lo, hi) masked), then the key mask of the L compact rows of the call ([prompt | sep | history], mask [n, L]) at the
-// cache rows rowmap[l] (DEVICE array [L], shared by the samples; the identity over the prefix), posbase[b] = the number of valid rows (nv + 1 + the
-// history's) and fresh[b] = 0: the sample is mid-episode and its next step consumes its action token.
-__global__ __launch_bounds__(256) void seq_history_install_kernel(const uint8_t* __restrict__ mask, const int* __restrict__ list,
-                                                                  const int* __restrict__ rowmap, int L, int lo, int hi, int n_pos,
-                                                                  uint8_t* cache_mask, int* posbase, uint8_t* fresh) {
-  __shared__ float part[4];
-  const int r = blockIdx.x, b = list[r];
-  for (int i = lo + threadIdx.x; i < hi; i += 256) cache_mask[(long long)b * n_pos + i] = 0;
-  __syncthreads();   // the mapped rows below lie inside [lo, hi): written after the clearing
-  float cnt = 0.f;
-  for (int l = threadIdx.x; l < L; l += 256) {
-    const uint8_t mk = mask[(long long)r * L + l] ? 1 : 0;
-    cache_mask[(long long)b * n_pos + rowmap[l]] = mk;
-    cnt += (float)mk;
-  }
-  cnt = wave_sum(cnt);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    posbase[b] = (int)((part[0] + part[1]) + (part[2] + part[3]));
-    fresh[b] = 0;
-  }
-}
-
-// K | V of a prefill to the episode cache: rows [n * L] of width N at row stride ld_in (the k | v columns of a dense q | k | v buffer) -> rows
-// [0, L) of sample (list ? list[r] : r)'s block of a cache of Lmax rows per sample; 16-byte chunks
-template <typename T>
-__global__ __launch_bounds__(256) void seq_kv_store_kernel(const T* __restrict__ in, long long ld_in, T* __restrict__ out,
-                                                           const int* __restrict__ list, int L, int N, int Lmax) {
-  constexpr int EPC = 16 / (int)sizeof(T);
-  const int r = blockIdx.y;
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  const int cpr = N / EPC;
-  if (i >= (long long)L * cpr) return;
-  const int l = (int)(i / cpr), c = (int)(i % cpr) * EPC;
-  const int b = list ? list[r] : r;
-  const uint4 v = *reinterpret_cast<const uint4*>(in + ((long long)r * L + l) * ld_in + c);
-  *reinterpret_cast<uint4*>(out + ((long long)b * Lmax + l) * N + c) = v;
-}
-
 __global__ __launch_bounds__(256) void fill_u8_kernel(uint8_t* p, long long n, uint8_t v) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i < n) p[i] = v;
@@ -335,31 +246,18 @@ int launch_broadcast_rows(const float* src, float* out, long long rows, int E, i
 
 int launch_seq_embed(const float* prompt, long long sb, long long sl, const uint8_t* pmask, const float* sep, const float* obs_tok,
                      const float* act_tok, const float* pos_table, int n_pos, float* x32, void* xT, uint8_t* mask, int B, int L, int Lp,
-                     int Q, int E, bool is_bf16, hipStream_t st, const int* list) {
+                     int Q, int E, bool is_bf16, hipStream_t st, const int* list, uint8_t* cache_mask, int* posbase, int cache_ld) {
   if (B <= 0 || L <= 0) return 0;
   if (E % 4 || sb % 4 || sl % 4) return (int)hipErrorInvalidValue;
+  // the episode state: both or neither, and rows [0, Lp] must exist in the position table and in a row of the cache mask
+  if ((cache_mask || posbase) && (!cache_mask || !posbase || Lp + 1 > n_pos || Lp + 1 > cache_ld)) return (int)hipErrorInvalidValue;
   const long long rows = (long long)B * L;
   if (is_bf16)
     hipLaunchKernelGGL(seq_embed_kernel<bf16_t>, dim3(nblk(rows, 4)), dim3(256), 0, st, prompt, sb, sl, pmask, sep, obs_tok, act_tok, pos_table,
-                       n_pos, x32, (bf16_t*)xT, mask, list, B, L, Lp, Q, E);
+                       n_pos, x32, (bf16_t*)xT, mask, list, B, L, Lp, Q, E, cache_mask, posbase, cache_ld);
   else
     hipLaunchKernelGGL(seq_embed_kernel<float>, dim3(nblk(rows, 4)), dim3(256), 0, st, prompt, sb, sl, pmask, sep, obs_tok, act_tok, pos_table,
-                       n_pos, x32, (float*)xT, mask, list, B, L, Lp, Q, E);
-  return (int)hipGetLastError();
-}
-
-int launch_seq_embed_prefill(const float* prompt, long long sb, long long sl, const uint8_t* pmask, const float* sep, const float* pos_table,
-                             int n_pos, float* x32, void* xT, uint8_t* mask, uint8_t* cache_mask, int* posbase, const int* list, int n, int Lp,
-                             int E, bool is_bf16, hipStream_t st) {
-  if (n <= 0 || Lp <= 0) return 0;
-  if (E % 4 || sb % 4 || sl % 4 || Lp + 1 > n_pos) return (int)hipErrorInvalidValue;
-  const long long rows = (long long)n * (Lp + 1);
-  if (is_bf16)
-    hipLaunchKernelGGL(seq_embed_prefill_kernel<bf16_t>, dim3(nblk(rows, 4)), dim3(256), 0, st, prompt, sb, sl, pmask, sep, pos_table, n_pos, x32,
-                       (bf16_t*)xT, mask, cache_mask, posbase, list, n, Lp, E);
-  else
-    hipLaunchKernelGGL(seq_embed_prefill_kernel<float>, dim3(nblk(rows, 4)), dim3(256), 0, st, prompt, sb, sl, pmask, sep, pos_table, n_pos, x32,
-                       (float*)xT, mask, cache_mask, posbase, list, n, Lp, E);
+                       n_pos, x32, (float*)xT, mask, list, B, L, Lp, Q, E, cache_mask, posbase, cache_ld);
   return (int)hipGetLastError();
 }
 
@@ -377,34 +275,6 @@ int launch_seq_embed_chunk(const float* obs_tok, const float* act_tok, const flo
   else
     hipLaunchKernelGGL(seq_embed_chunk_kernel<float>, dim3(B), dim3(256), 0, st, obs_tok, act_tok, pos_table, n_pos, x32, (float*)xT, cache_mask,
                        posbase, fresh, row0, T, B, Q, has_act ? 1 : 0, E);
-  return (int)hipGetLastError();
-}
-
-int launch_seq_history_install(const uint8_t* mask, const int* list, const int* rowmap, int n, int L, int lo, int hi, int n_pos,
-                               uint8_t* cache_mask, int* posbase, uint8_t* fresh, hipStream_t st) {
-  if (n <= 0) return 0;
-  if (L <= 0 || L > n_pos || lo < 0 || hi > n_pos || !mask || !list || !rowmap || !cache_mask || !posbase || !fresh) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(seq_history_install_kernel, dim3(n), dim3(256), 0, st, mask, list, rowmap, L, lo, hi, n_pos, cache_mask, posbase, fresh);
-  return (int)hipGetLastError();
-}
-
-int launch_seq_restart(const int* list, int n, uint8_t* cache_mask, uint8_t* fresh, int lo, int hi, int n_pos, hipStream_t st) {
-  if (n <= 0) return 0;
-  if (lo < 0 || hi > n_pos) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(seq_restart_kernel, dim3(n), dim3(256), 0, st, list, cache_mask, fresh, lo, hi, n_pos);
-  return (int)hipGetLastError();
-}
-
-int launch_seq_kv_store(const void* in, long long ld_in, void* out, const int* list, int n, int L, int N, int Lmax, bool is_bf16,
-                        hipStream_t st) {
-  const int epc = is_bf16 ? 8 : 4;
-  if (n <= 0 || L <= 0 || N <= 0) return 0;
-  if (N % epc || ld_in % epc || L > Lmax || n > 65535 || ((uintptr_t)in & 15) || ((uintptr_t)out & 15)) return (int)hipErrorInvalidValue;
-  const dim3 grid(nblk((long long)L * (N / epc), 256), (unsigned)n);
-  if (is_bf16)
-    hipLaunchKernelGGL(seq_kv_store_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)in, ld_in, (bf16_t*)out, list, L, N, Lmax);
-  else
-    hipLaunchKernelGGL(seq_kv_store_kernel<float>, grid, dim3(256), 0, st, (const float*)in, ld_in, (float*)out, list, L, N, Lmax);
   return (int)hipGetLastError();
 }
 

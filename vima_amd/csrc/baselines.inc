@@ -158,14 +158,14 @@ int hfgpt_block_tail(Run& R, const VimaHandle::DecLayer& D, const HfgptWs& w, fl
 
 // HFGPT.forward (gpt/gpt.py:45-80) on an assembled sequence: x32 / xT [B*L, E] (positions already added), key mask [B, L].
 // Post-LN blocks: a = attn(x), then hfgpt_block_tail. Result in x32 (and xT).
-// kv_cache (vima_seq_prefill / vima_seq_decode_restart): every layer's k | v rows are also COPIED to rows [0, L) of the episode cache
-// [layer][kv_B][kv_Lmax][2E], block kv_list[r] (DEVICE array; nullptr: r) for the r-th sample of this call. A copy, not the c_attn GEMM's
+// kv_store (vima_seq_prefill / vima_seq_decode_restart): every layer's k | v rows are also COPIED to rows [0, L) of the episode cache
+// (ep_layer), block kv_list[r] (DEVICE array; nullptr: r) for the r-th sample of this call. A copy, not the c_attn GEMM's
 // row-remap epilogue: the attention of these rows reads the dense q | k | v of the call, so the remap would need the k | v columns twice (a
 // second GEMM launch per layer), while the copy is one HBM-bound pass over 2E columns, leaves the arithmetic of `vima_seq_decode` untouched
 // (same GEMM, same attention launch: the prefilled rows carry its bits) and serves the full prefill and the listed restart alike.
 // kv_rowmap (vima_seq_decode_restart_history; DEVICE array [L], needs kv_list): row l goes to cache row kv_rowmap[l] instead of l -- still one launch per layer.
-int hfgpt_stack(Run& R, float* x32, void* xT, const uint8_t* mask, int B, int L, void* kv_cache = nullptr, const int* kv_list = nullptr,
-                int kv_B = 0, int kv_Lmax = 0, const int* kv_rowmap = nullptr) {
+int hfgpt_stack(Run& R, float* x32, void* xT, const uint8_t* mask, int B, int L, bool kv_store = false, const int* kv_list = nullptr,
+                const int* kv_rowmap = nullptr) {
   VimaHandle* h = R.h;
   const int E = h->cfg.embed_dim, Hs = h->cfg.sattn_n_heads, rq = B * L;
   const HfgptWs w = hfgpt_ws(R, rq, 3 * E);
@@ -174,12 +174,11 @@ int hfgpt_stack(Run& R, float* x32, void* xT, const uint8_t* mask, int B, int L,
   for (int i = 0; i < h->cfg.xf_n_layers; ++i) {
     auto& D = h->dec[i];
     R.linear(xT, E, D.c_attn, rq, ACT_NONE, nullptr, 0, nullptr, 0, nullptr, 0, qkv, 3 * E);
-    if (kv_cache && kv_rowmap)
-      OTHER(R, launch_kv_scatter_rows(R.offT(qkv, E), 3 * E, R.offT(kv_cache, (long long)i * kv_B * kv_Lmax * 2 * E), kv_list, kv_rowmap, B, L, kv_Lmax,
-                                      2 * E, h->bf16, R.st), "kv_scatter_rows");
-    else if (kv_cache)
-      OTHER(R, launch_seq_kv_store(R.offT(qkv, E), 3 * E, R.offT(kv_cache, (long long)i * kv_B * kv_Lmax * 2 * E), kv_list, B, L, 2 * E, kv_Lmax,
-                                   h->bf16, R.st), "seq_kv_store");
+    if (kv_store) {
+      KvRowsArgs c;
+      c.in = R.offT(qkv, E); c.ld = 3 * E; c.out = ep_layer(h, i); c.list = kv_list; c.rowmap = kv_rowmap; c.n = B; c.L = L; c.N = 2 * E; c.Lc = h->ep_Lmax;
+      OTHER(R, launch_kv_rows(c, (int)h->esz(), R.st), kv_rowmap ? "kv_scatter_rows" : "seq_kv_store");
+    }
     AttnArgs s;   // Attention._attn (gpt/gpt.py:268-301): /sqrt(d), w*b + -1e4*(1-b), + (1-mask)*finfo.min
     s.q = qkv; s.ldq = 3 * E; s.k = R.offT(qkv, E); s.ldk = 3 * E; s.v = R.offT(qkv, 2 * E); s.ldv = 3 * E;
     s.out = w.ctx; s.ldo = E; s.B = B; s.H = Hs; s.Lq = L; s.Lk = L; s.D = E / Hs; s.kmask = mask;
@@ -200,7 +199,7 @@ int hfgpt_step_stack(Run& R, float* x32, void* xT, int B, int Lq, int row, int L
   if (R.err) return R.err;
   for (int i = 0; i < h->cfg.xf_n_layers; ++i) {
     auto& D = h->dec[i];
-    void* cache = R.offT(h->ep_kv, (long long)i * B * Lmax * 2 * E);
+    void* cache = ep_layer(h, i);
     c_attn_append(R, D.c_attn, xT, rq, Lq, row, Lmax, cache, w.qkv);
     AttnArgs s;
     attn_from_cache(R, s, w.qkv, cache, row, Lmax, Lk, win_end);

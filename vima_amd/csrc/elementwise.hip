@@ -1,6 +1,7 @@
 // HBM-bound helper kernels of the VIMA policy hot path (gfx950, wave64): normalisation, image patchify,
 // token plumbing. Each cites the reference lines it replaces. fp32 statistics everywhere; the operand type T of
 // the matrix-core GEMMs (bf16, or fp32 in parity mode) only appears at the GEMM-input boundary.
+// The episode caches' per-sample plumbing (row copies, restart, history install) serves the baselines too and lives in episode_rows.hip.
 #include "kernels.h"
 #include <stdlib.h>
 
@@ -563,16 +564,6 @@ __global__ __launch_bounds__(256) void dec_embed_chunk_kernel(const float* __res
   }
 }
 
-// per-sample episode restart (vima_decode_restart): flagged samples forget their history (every cached key masked), their position
-// counter restarts at 0 and their next step's action slot is marked absent
-__global__ __launch_bounds__(256) void restart_samples_kernel(const uint8_t* __restrict__ flags, uint8_t* hist_mask, int* poscnt, uint8_t* fresh,
-                                                               int Lmax) {
-  const int b = blockIdx.x;
-  if (!flags[b]) return;
-  for (int i = threadIdx.x; i < Lmax; i += 256) hist_mask[(long long)b * Lmax + i] = 0;
-  if (threadIdx.x == 0) { poscnt[b] = 0; fresh[b] = 1; }
-}
-
 // prompt + xattn_positions_embed[cumsum(prompt_mask) - 1]  (vima_policy.py:147, xattn_gpt.py:110-114) -> T [B, Lp, E]
 // With a sample list (batched vima_decode_restart) output block blockIdx.x is computed from sample list[blockIdx.x] of prompt / mask.
 template <typename T>
@@ -850,96 +841,6 @@ int launch_prompt_assemble(const int* tok_src, const long long* word_ids, const 
   return (int)hipGetLastError();
 }
 
-// rows [L][N] (row-major) -> [N / D][L][D]: one sample's K | V rows into the head-major prompt cache (vima_decode_restart); 16-byte chunks
-template <typename T>
-__global__ __launch_bounds__(256) void rows_to_headmajor_kernel(const T* __restrict__ in, T* __restrict__ out, int L, int N, int D) {
-  constexpr int EPC = 16 / (int)sizeof(T);
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  const int cpr = N / EPC;
-  if (i >= (long long)L * cpr) return;
-  const int l = (int)(i / cpr), n = (int)(i % cpr) * EPC;
-  const uint4 v = *reinterpret_cast<const uint4*>(in + (long long)l * N + n);
-  *reinterpret_cast<uint4*>(out + ((long long)(n / D) * L + l) * D + n % D) = v;
-}
-
-int launch_rows_to_headmajor(const void* in, void* out, int L, int N, int D, bool is_bf16, hipStream_t st) {
-  const int epc = is_bf16 ? 8 : 4;
-  if (L <= 0 || N <= 0) return 0;
-  if (D % epc || N % D) return (int)hipErrorInvalidValue;
-  const long long n = (long long)L * (N / epc);
-  if (is_bf16) hipLaunchKernelGGL(rows_to_headmajor_kernel<bf16_t>, dim3(nblk(n, 256)), dim3(256), 0, st, (const bf16_t*)in, (bf16_t*)out, L, N, D);
-  else hipLaunchKernelGGL(rows_to_headmajor_kernel<float>, dim3(nblk(n, 256)), dim3(256), 0, st, (const float*)in, (float*)out, L, N, D);
-  return (int)hipGetLastError();
-}
-
-// K | V rows of n listed samples, in [n * L][N] (row-major, sample r = rows r L ..), to each sample's block of the prompt K / V cache (batched
-// vima_decode_restart): block list[r] of `out` (L * N elements per sample), row-major [L][N] (hm = 0) or head-major [N / D][L][D]; 16-byte chunks
-template <typename T>
-__global__ __launch_bounds__(256) void kv_scatter_kernel(const T* __restrict__ in, T* __restrict__ out, const int* __restrict__ list, int L, int N,
-                                                          int D, int hm) {
-  constexpr int EPC = 16 / (int)sizeof(T);
-  const int r = blockIdx.y;
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  const int cpr = N / EPC;
-  if (i >= (long long)L * cpr) return;
-  const int l = (int)(i / cpr), n = (int)(i % cpr) * EPC;
-  const uint4 v = *reinterpret_cast<const uint4*>(in + ((long long)r * L + l) * N + n);
-  T* dst = out + (long long)list[r] * L * N;
-  *reinterpret_cast<uint4*>(dst + (hm ? ((long long)(n / D) * L + l) * D + n % D : (long long)l * N + n)) = v;
-}
-
-// The inverse of kv_scatter_kernel: block list[r] of a cache of L * N elements per sample (either layout) -> rows [n * L][N]
-template <typename T>
-__global__ __launch_bounds__(256) void kv_gather_kernel(const T* __restrict__ in, T* __restrict__ out, const int* __restrict__ list, int L, int N,
-                                                         int D, int hm) {
-  constexpr int EPC = 16 / (int)sizeof(T);
-  const int r = blockIdx.y;
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  const int cpr = N / EPC;
-  if (i >= (long long)L * cpr) return;
-  const int l = (int)(i / cpr), n = (int)(i % cpr) * EPC;
-  const T* src = in + (long long)list[r] * L * N;
-  const uint4 v = *reinterpret_cast<const uint4*>(src + (hm ? ((long long)(n / D) * L + l) * D + n % D : (long long)l * N + n));
-  *reinterpret_cast<uint4*>(out + ((long long)r * L + l) * N + n) = v;
-}
-
-// Row-map form of kv_scatter_kernel (vima_decode_restart_history): N columns of rows [n * L] (leading dimension ld) -> row rowmap[l] of sample
-// list[r] in a row-major cache of Lmax rows of N elements per sample; the row map is shared by the samples
-template <typename T>
-__global__ __launch_bounds__(256) void kv_scatter_rows_kernel(const T* __restrict__ in, int ld, T* __restrict__ out, const int* __restrict__ list,
-                                                               const int* __restrict__ rowmap, int L, int Lmax, int N) {
-  constexpr int EPC = 16 / (int)sizeof(T);
-  const int r = blockIdx.y;
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  const int cpr = N / EPC;
-  if (i >= (long long)L * cpr) return;
-  const int l = (int)(i / cpr), n = (int)(i % cpr) * EPC;
-  const uint4 v = *reinterpret_cast<const uint4*>(in + ((long long)r * L + l) * ld + n);
-  *reinterpret_cast<uint4*>(out + ((long long)list[r] * Lmax + rowmap[l]) * N + n) = v;
-}
-
-// The episode state of an installed history (vima_decode_restart_history): key mask of the L compact rows -> cache row rowmap[l] of sample list[r],
-// position counter = the history's number of valid tokens, and the sample is mid-episode (its next step consumes its action token)
-__global__ __launch_bounds__(256) void history_install_kernel(const uint8_t* __restrict__ mask, const int* __restrict__ list,
-                                                               const int* __restrict__ rowmap, int L, int Lmax, uint8_t* hist_mask, int* poscnt,
-                                                               uint8_t* fresh) {
-  __shared__ int part[256];
-  const int r = blockIdx.x, b = list[r];
-  int cnt = 0;
-  for (int l = threadIdx.x; l < L; l += 256) {
-    const uint8_t mk = mask[(long long)r * L + l] ? 1 : 0;
-    hist_mask[(long long)b * Lmax + rowmap[l]] = mk;
-    cnt += mk;
-  }
-  part[threadIdx.x] = cnt;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) { poscnt[b] = part[0]; fresh[b] = 0; }
-}
-
 // out[r][l] = in[list[r]][l]: the flagged samples' rows of a byte mask [B][L]
 __global__ __launch_bounds__(256) void mask_rows_gather_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, const int* __restrict__ list,
                                                                 int L) {
@@ -952,45 +853,6 @@ int launch_mask_rows_gather(const uint8_t* in, uint8_t* out, const int* list, in
   if (n <= 0 || L <= 0) return 0;
   if (n > 65535 || !in || !out || !list) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(mask_rows_gather_kernel, dim3(nblk(L, 256), (unsigned)n), dim3(256), 0, st, in, out, list, L);
-  return (int)hipGetLastError();
-}
-
-int launch_kv_gather(const void* in, void* out, const int* list, int n, int L, int N, int D, int hm, bool is_bf16, hipStream_t st) {
-  const int epc = is_bf16 ? 8 : 4;
-  if (n <= 0 || L <= 0 || N <= 0) return 0;
-  if (N % epc || (hm && (D % epc || N % D)) || n > 65535) return (int)hipErrorInvalidValue;
-  const dim3 grid(nblk((long long)L * (N / epc), 256), (unsigned)n);
-  if (is_bf16) hipLaunchKernelGGL(kv_gather_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)in, (bf16_t*)out, list, L, N, D, hm);
-  else hipLaunchKernelGGL(kv_gather_kernel<float>, grid, dim3(256), 0, st, (const float*)in, (float*)out, list, L, N, D, hm);
-  return (int)hipGetLastError();
-}
-
-int launch_kv_scatter_rows(const void* in, int ld, void* out, const int* list, const int* rowmap, int n, int L, int Lmax, int N, bool is_bf16,
-                           hipStream_t st) {
-  const int epc = is_bf16 ? 8 : 4;
-  if (n <= 0 || L <= 0 || N <= 0) return 0;
-  if (N % epc || ld % epc || ld < N || L > Lmax || n > 65535 || !list || !rowmap) return (int)hipErrorInvalidValue;
-  const dim3 grid(nblk((long long)L * (N / epc), 256), (unsigned)n);
-  if (is_bf16) hipLaunchKernelGGL(kv_scatter_rows_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)in, ld, (bf16_t*)out, list, rowmap, L, Lmax, N);
-  else hipLaunchKernelGGL(kv_scatter_rows_kernel<float>, grid, dim3(256), 0, st, (const float*)in, ld, (float*)out, list, rowmap, L, Lmax, N);
-  return (int)hipGetLastError();
-}
-
-int launch_history_install(const uint8_t* mask, const int* list, const int* rowmap, int n, int L, int Lmax, uint8_t* hist_mask, int* poscnt,
-                           uint8_t* fresh, hipStream_t st) {
-  if (n <= 0) return 0;
-  if (L <= 0 || L > Lmax || !mask || !list || !rowmap || !hist_mask || !poscnt || !fresh) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(history_install_kernel, dim3(n), dim3(256), 0, st, mask, list, rowmap, L, Lmax, hist_mask, poscnt, fresh);
-  return (int)hipGetLastError();
-}
-
-int launch_kv_scatter(const void* in, void* out, const int* list, int n, int L, int N, int D, int hm, bool is_bf16, hipStream_t st) {
-  const int epc = is_bf16 ? 8 : 4;
-  if (n <= 0 || L <= 0 || N <= 0) return 0;
-  if (N % epc || (hm && (D % epc || N % D)) || n > 65535) return (int)hipErrorInvalidValue;
-  const dim3 grid(nblk((long long)L * (N / epc), 256), (unsigned)n);
-  if (is_bf16) hipLaunchKernelGGL(kv_scatter_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)in, (bf16_t*)out, list, L, N, D, hm);
-  else hipLaunchKernelGGL(kv_scatter_kernel<float>, grid, dim3(256), 0, st, (const float*)in, (float*)out, list, L, N, D, hm);
   return (int)hipGetLastError();
 }
 
@@ -1034,12 +896,6 @@ int launch_dec_embed_chunk(const float* obs_tok, const uint8_t* obs_mask, const 
   else
     hipLaunchKernelGGL(dec_embed_chunk_kernel<float>, dim3(B), dim3(256), 0, st, obs_tok, obs_mask, act_tok, pos_table, n_pos,
                        x32, (float*)xT, hist_mask, poscnt, row0, Lmax, T, B, Q, has_act ? 1 : 0, E, fresh);
-  return (int)hipGetLastError();
-}
-
-int launch_restart_samples(const uint8_t* flags, uint8_t* hist_mask, int* poscnt, uint8_t* fresh, int B, int Lmax, hipStream_t st) {
-  if (B <= 0) return 0;
-  hipLaunchKernelGGL(restart_samples_kernel, dim3(B), dim3(256), 0, st, flags, hist_mask, poscnt, fresh, Lmax);
   return (int)hipGetLastError();
 }
 

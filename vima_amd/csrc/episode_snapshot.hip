@@ -9,7 +9,7 @@
 // is a chunk of rpc whole rows (about kSnapChunk 16-byte vectors) and every lane resolves the row of each of its four vectors from the table. The
 // table is ONE per call: compact row k counted from the end is the same cache row whatever the episode's length, so every job reads a suffix.
 // Four global_load_dwordx4 per lane are in flight together, unconditional at clamped (in-bounds) indices; only the stores are predicated. No LDS.
-// The head-major prompt K / V layout ([N / D][L][D] per sample) is addressed as kv_gather_kernel / kv_scatter_kernel do: a row's contiguous pieces
+// The head-major prompt K / V layout ([N / D][L][D] per sample) is addressed as kv_rows_kernel (episode_rows.hip) does: a row's contiguous pieces
 // are D elements; the payload is row-major [NL][rows][N] whatever the cache's layout.
 // Plain loads and stores. Jobs of one unpack call name distinct samples, pack only reads the cache: no unit reads what another writes.
 #include "kernels.h"

@@ -102,8 +102,6 @@ int launch_prompt_assemble(const int* tok_src, const long long* word_ids, const 
 // launch_rms_stats would produce from the fp32 rows, bit for bit) + mask; the fp32 prompt is not materialised
 int launch_prompt_assemble_stats(const int* tok_src, const long long* word_ids, const float* word_table, const float* obj_tokens,
                                  const uint8_t* obj_mask, void* xT, float* ssq, uint8_t* mask, int rows, int E, bool is_bf16, hipStream_t st);
-// rows [L][N] of the operand type -> [N / D][L][D] (one sample's block of the head-major prompt K / V cache)
-int launch_rows_to_headmajor(const void* in, void* out, int L, int N, int D, bool is_bf16, hipStream_t st);
 // decoder input: interleave [o_1..o_Q, a] per step, cumsum position ids, + positions_embed
 int launch_dec_embed(const float* obs_tok, const uint8_t* obs_mask, const float* act_tok, const float* pos_table,
                      int n_pos, float* x32, void* xT, uint8_t* mask, int T, int B, int Q, int L_act, int E,
@@ -115,27 +113,12 @@ int launch_dec_embed(const float* obs_tok, const uint8_t* obs_mask, const float*
 int launch_dec_embed_chunk(const float* obs_tok, const uint8_t* obs_mask, const float* act_tok, const float* pos_table, int n_pos,
                            float* x32, void* xT, uint8_t* hist_mask, int* poscnt, int row0, int Lmax, int T, int B, int Q,
                            int has_act, int E, bool is_bf16, hipStream_t st, uint8_t* fresh);
-// per-sample episode restart: for flags[b] != 0 (device array) mask sample b's whole history, reset its position counter, mark its
-// next action slot absent (fresh[b] = 1, consumed by launch_dec_embed_chunk)
-int launch_restart_samples(const uint8_t* flags, uint8_t* hist_mask, int* poscnt, uint8_t* fresh, int B, int Lmax, hipStream_t st);
 // prompt + xattn_positions_embed[cumsum(mask)-1] -> T [B*Lp, E]; input strides in elements (seq-first views ok)
 // list (DEVICE array [B], optional): output block r is computed from sample list[r] of prompt / mask instead of sample r
 int launch_prompt_pos(const float* prompt, long long sb, long long sl, const uint8_t* mask, const float* pos_table,
                       int n_pos, void* outT, int B, int Lp, int E, bool is_bf16, hipStream_t st, const int* list = nullptr);
-// rows [n * L][N] of the operand type (sample r = rows r * L ..) -> block list[r] (DEVICE array [n]) of a cache of L * N elements per sample:
-// row-major [L][N] (hm = 0) or head-major [N / D][L][D] (the prompt K / V cache's two layouts)
-int launch_kv_scatter(const void* in, void* out, const int* list, int n, int L, int N, int D, int hm, bool is_bf16, hipStream_t st);
 // out[r][l] = in[list[r]][l], r < n: rows of a byte mask [B][L] by a sample list (DEVICE array)
 int launch_mask_rows_gather(const uint8_t* in, uint8_t* out, const int* list, int n, int L, hipStream_t st);
-// the inverse of launch_kv_scatter: block list[r] of the cache (either layout) -> rows [n * L][N]
-int launch_kv_gather(const void* in, void* out, const int* list, int n, int L, int N, int D, int hm, bool is_bf16, hipStream_t st);
-// row-map form: N columns of rows [n * L] (leading dimension ld) -> row rowmap[l] (DEVICE array [L], shared by the samples) of sample list[r] in a
-// row-major cache of Lmax rows of N elements per sample (the episode K | V cache)
-int launch_kv_scatter_rows(const void* in, int ld, void* out, const int* list, const int* rowmap, int n, int L, int Lmax, int N, bool is_bf16,
-                           hipStream_t st);
-// installed history: hist_mask[list[r]][rowmap[l]] = mask[r][l], poscnt[list[r]] = the number of valid rows, fresh[list[r]] = 0
-int launch_history_install(const uint8_t* mask, const int* list, const int* rowmap, int n, int L, int Lmax, uint8_t* hist_mask, int* poscnt,
-                           uint8_t* fresh, hipStream_t st);
 // out[t,b,:] = x[b, lead + (Q-1) + (Q+1) t, :]; lead = 1 when every slot of Q + 1 rows starts with an action row (a chunk behind batch step 0)
 int launch_gather_pred(const float* x, float* out, int T, int B, int Q, int Lq, int E, hipStream_t st, int lead = 0);
 
@@ -147,17 +130,15 @@ int launch_vit_embed_rect(const float* pre, const float* cls, const float* pos, 
                           int M, int S, int n_patch, bool is_bf16, hipStream_t st);
 // out[r,:] = src[r % period,:] (fp32)
 int launch_broadcast_rows(const float* src, float* out, long long rows, int E, int period, hipStream_t st);
-// decoder-only input [B,L,E]: [prompt | sep | (Q obs tokens, action)*] + positions_embed, key mask [B,L]
-int launch_seq_embed(const float* prompt, long long sb, long long sl, const uint8_t* pmask, const float* sep, const float* obs_tok,
-                     const float* act_tok, const float* pos_table, int n_pos, float* x32, void* xT, uint8_t* mask, int B, int L, int Lp,
-                     int Q, int E, bool is_bf16, hipStream_t st, const int* list = nullptr);
 // incremental decoding of the decoder-only policies. Episode state on the device: cache_mask [B][n_pos] (key mask at the cache's row stride),
 // posbase[b] (position id of sample b's next valid row), fresh[b] (1 after a restart: the next action slot is absent).
-// rows [0, Lp] ([prompt | sep] + positions) of n samples -> x32 / xT / mask [n, Lp + 1]; block r comes from sample list[r] (DEVICE array,
-// optional: identity) whose cache_mask rows [0, Lp] and posbase (= valid prompt tokens + 1) are written
-int launch_seq_embed_prefill(const float* prompt, long long sb, long long sl, const uint8_t* pmask, const float* sep, const float* pos_table,
-                             int n_pos, float* x32, void* xT, uint8_t* mask, uint8_t* cache_mask, int* posbase, const int* list, int n, int Lp,
-                             int E, bool is_bf16, hipStream_t st);
+// decoder-only input [B,L,E]: [prompt | sep | (Q obs tokens, action)*] + positions_embed, key mask [B,L]; block r comes from sample list[r] of
+// prompt / pmask (DEVICE array, optional: identity). With cache_mask / posbase (the prefill of an episode: L = Lp + 1, no obs_tok / act_tok) the
+// episode state of that sample is written too: cache_mask[.][0 .. Lp] at row stride cache_ld and posbase (= valid prompt tokens + 1)
+int launch_seq_embed(const float* prompt, long long sb, long long sl, const uint8_t* pmask, const float* sep, const float* obs_tok,
+                     const float* act_tok, const float* pos_table, int n_pos, float* x32, void* xT, uint8_t* mask, int B, int L, int Lp,
+                     int Q, int E, bool is_bf16, hipStream_t st, const int* list = nullptr, uint8_t* cache_mask = nullptr, int* posbase = nullptr,
+                     int cache_ld = 0);
 // the rows of T >= 1 env steps as one chunk (vima_seq_decode_step is T = 1): T (Q + 1) rows per sample (one fewer without has_act: the first slot of
 // batch step 0 has no action row) at cache rows [row0, ..); obs_tok [T, B, Q, E], act_tok [T, B, E] (has_act) / [T - 1, B, E] -> x32 / xT; positions
 // continue posbase[b]; cache_mask[b][row0 + i] and posbase[b] are updated, fresh[b] is consumed (a fresh sample's first action row: zeros, key
@@ -165,16 +146,29 @@ int launch_seq_embed_prefill(const float* prompt, long long sb, long long sl, co
 int launch_seq_embed_chunk(const float* obs_tok, const float* act_tok, const float* pos_table, int n_pos, float* x32, void* xT,
                            uint8_t* cache_mask, int* posbase, uint8_t* fresh, int row0, int T, int B, int Q, int has_act, int E, bool is_bf16,
                            hipStream_t st);
-// installed history of the n listed samples: cache_mask[list[r]][lo .. hi) = 0, then cache_mask[list[r]][rowmap[l]] = mask[r][l] (l < L),
-// posbase[list[r]] = the number of valid rows, fresh[list[r]] = 0
-int launch_seq_history_install(const uint8_t* mask, const int* list, const int* rowmap, int n, int L, int lo, int hi, int n_pos,
-                               uint8_t* cache_mask, int* posbase, uint8_t* fresh, hipStream_t st);
-// for the n listed samples (DEVICE array): cache_mask[b][lo .. hi) = 0, fresh[b] = 1
-int launch_seq_restart(const int* list, int n, uint8_t* cache_mask, uint8_t* fresh, int lo, int hi, int n_pos, hipStream_t st);
-// rows [n * L] of width N (operand type, row stride ld_in) -> rows [0, L) of sample list[r]'s (optional: r's) block of a cache of Lmax rows per sample
-int launch_seq_kv_store(const void* in, long long ld_in, void* out, const int* list, int n, int L, int N, int Lmax, bool is_bf16,
-                        hipStream_t st);
 int launch_fill_u8(uint8_t* p, long long n, uint8_t v, hipStream_t st);
+
+// ---- episode caches, both policy families (episode_rows.hip)
+// Rows between a compact buffer and the samples' blocks of a cache, one launch: 16-byte vectors, grid (vectors of a sample, n)
+struct KvRowsArgs {
+  const void* in = nullptr;
+  void* out = nullptr;
+  const int* list = nullptr;     // DEVICE [n]: cache block of compact sample r (nullptr: r)
+  const int* rowmap = nullptr;   // DEVICE [L]: cache row of compact row l, shared by the samples (nullptr: l)
+  int n = 0, L = 0, N = 0;       // compact side: n samples x L rows x N elements ...
+  long long ld = 0;              // ... at this leading dimension (>= N)
+  int Lc = 0;                    // rows per sample block of the cache (block = Lc * N elements)
+  int D = 0;                     // > 0: block is head-major [N / D][Lc][D]; 0: row-major [Lc][N]
+  bool to_cache = true;          // compact -> cache (scatter / store) or cache -> compact (gather)
+};
+// hipErrorInvalidValue when N, ld or D is no whole number of 16-byte vectors, N % D != 0, ld < N, L > Lc, n > 65535 or a buffer is misaligned
+int launch_kv_rows(const KvRowsArgs& a, int elem_bytes, hipStream_t st);
+// for the n listed samples (DEVICE array): mask[b][lo .. hi) = 0, fresh[b] = 1 (consumed by the next chunk's embedding), poscnt[b] = 0 (optional)
+int launch_episode_restart(const int* list, int n, uint8_t* mask, int* poscnt, uint8_t* fresh, int lo, int hi, int Lmax, hipStream_t st);
+// installed history of the n listed samples: cache_mask[list[r]][lo .. hi) = 0, then cache_mask[list[r]][rowmap[l]] = mask[r][l] (l < L),
+// poscnt[list[r]] = the number of valid rows, fresh[list[r]] = 0
+int launch_history_install(const uint8_t* mask, const int* list, const int* rowmap, int n, int L, int lo, int hi, int Lmax, uint8_t* cache_mask,
+                           int* poscnt, uint8_t* fresh, hipStream_t st);
 
 // ---- episode fork (episode_fork.hip): a sample's episode state copied into other batch slots, in place
 // One job = one row range [row0, row0 + nrows) of sample `src`, copied to the ndst samples dsts[dst0 ..) in EVERY layer of a cache [NL][B][L][N]:

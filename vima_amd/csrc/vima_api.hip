@@ -947,6 +947,15 @@ struct Run {
   } while (0)
 
 // ------------------------------------------------------------------------------------------------ episode cache (decode_launch, hfgpt_step_stack)
+// Layer i of the episode batch's caches (ep_B samples): the self-attention K | V cache [NL][ep_B][ep_Lmax][2E] and the prompt K / V cache
+// [NL][ep_B][Lp][2E] (either layout)
+void* ep_layer(const VimaHandle* h, int i) {
+  return reinterpret_cast<char*>(h->ep_kv) + (size_t)i * h->ep_B * h->ep_Lmax * 2 * h->cfg.embed_dim * h->esz();
+}
+void* kv_layer(const VimaHandle* h, int i, int Lp) {
+  return reinterpret_cast<char*>(h->kv_cache) + (size_t)i * h->ep_B * Lp * 2 * h->cfg.embed_dim * h->esz();
+}
+
 // c_attn of the new rows xT [rq = B Lq, E]: q dense [rq, E], k | v APPENDED to the layer's episode cache [B][Lmax][2E] by the GEMM's row-remap
 // epilogue (row b Lq + i -> b Lmax + row + i). One launch (q columns dense, k | v columns remapped) where the split form exists, two otherwise.
 int c_attn_append(Run& R, const Lin& c_attn, const void* xT, int rq, int Lq, int row, int Lmax, void* cache, void* q) {
@@ -2034,7 +2043,7 @@ static int decode_prepare(VimaHandle* h, const float* act_tok, int T, int B, int
     kv_cache_mode = step == 0 ? 1 : 2;
     if (step == 0) {   // a new episode batch: the one that ran ends here
       if (int e = ep_reserve(h, B, Lmax)) return e;
-      h->ep_step = -1;
+      h->ep_step = -1; h->ep_B = B; h->ep_Lmax = Lmax;   // the caches' shape (ep_layer); the episode itself is valid from decode_commit on
       h->book.begin(B, Q, 0, Lmax, ring);
     }
     u = h->book.plan(T);   // the book is at `step` (the continuity check above): a chunk is ONE unit of Lq rows
@@ -2202,9 +2211,11 @@ static int decode_launch(VimaHandle* h, const float* obs_tok, const uint8_t* obs
     if (dual) HIPCK(hipStreamWaitEvent(R.st, h->ev_layer[i], 0));
     else if (build_kv)   // single stream: project right before use (without a cache all layers share one buffer)
       kv_proj(R, i, KV);
-    else if (hist)       // the flagged samples' blocks of the prompt K / V cache (either layout), which the restart in front of this pass has rebuilt
-      OTHER(R, launch_kv_gather(reinterpret_cast<char*>(h->kv_cache) + (size_t)h->ep_B * Lp * 2 * E * h->esz() * i, KV, hlist, B, Lp, 2 * E, Dx,
-                                h->kv_hm ? 1 : 0, h->bf16, R.st), "kv_gather");
+    else if (hist) {     // the flagged samples' blocks of the prompt K / V cache (either layout), which the restart in front of this pass has rebuilt
+      KvRowsArgs c;
+      c.in = kv_layer(h, i, Lp); c.out = KV; c.list = hlist; c.n = B; c.L = c.Lc = Lp; c.N = c.ld = 2 * E; c.D = h->kv_hm ? Dx : 0; c.to_cache = false;
+      OTHER(R, launch_kv_rows(c, (int)h->esz(), R.st), "kv_gather");
+    }
     AttnArgs a;
     a.q = Qb; a.ldq = E; a.out = ctx; a.ldo = E;
     if (hm) {   // [B][2 Hx][Lp][Dx]: K heads 0 .. Hx-1, V heads Hx .. 2 Hx-1
@@ -2238,16 +2249,18 @@ static int decode_launch(VimaHandle* h, const float* obs_tok, const uint8_t* obs
     s.scale = 1.0f / sqrtf((float)(E / Hs)); s.mode = ATTN_CAUSAL;
     if (inc) {
       // q of the new tokens, their k | v rows appended to the layer's episode cache at rows [L_hist, L_hist + Lq); history + themselves are the keys
-      void* cache = reinterpret_cast<char*>(h->ep_kv) + (size_t)i * B * Lmax * 2 * E * h->esz();
+      void* cache = ep_layer(h, i);
       c_attn_append(R, D.c_attn, xT, rq, Lq, L_hist, Lmax, cache, qkv);
       attn_from_cache(R, s, qkv, cache, L_hist, Lmax, P.u.Lk, P.u.win_end);
     } else {
       R.linear(xT, E, D.c_attn, rq, ACT_NONE, nullptr, 0, nullptr, 0, nullptr, 0, qkv, 3 * E);
       s.q = qkv; s.ldq = 3 * E; s.k = R.offT(qkv, E); s.ldk = 3 * E; s.v = R.offT(qkv, 2 * E); s.ldv = 3 * E;
       s.kmask = dmask; s.Lk = Lq;
-      if (hist)   // the history's K | V rows of this layer -> the episode cache, at the rows the batch steps behind them wrote
-        OTHER(R, launch_kv_scatter_rows(R.offT(qkv, E), 3 * E, reinterpret_cast<char*>(h->ep_kv) + (size_t)i * h->ep_B * Lmax * 2 * E * h->esz(), hlist,
-                                        hmap, B, Lq, Lmax, 2 * E, h->bf16, R.st), "kv_scatter_rows");
+      if (hist) {   // the history's K | V rows of this layer -> the episode cache, at the rows the batch steps behind them wrote
+        KvRowsArgs c;
+        c.in = R.offT(qkv, E); c.ld = 3 * E; c.out = ep_layer(h, i); c.list = hlist; c.rowmap = hmap; c.n = B; c.L = Lq; c.N = 2 * E; c.Lc = Lmax;
+        OTHER(R, launch_kv_rows(c, (int)h->esz(), R.st), "kv_scatter_rows");
+      }
     }
     R.attn(s, h->attn_impl);
     R.linear(ctx, E, D.c_proj, rq, ACT_NONE, nullptr, 0, x32, E, a32, E, nullptr, 0);   // x + a
@@ -2264,7 +2277,8 @@ static int decode_launch(VimaHandle* h, const float* obs_tok, const uint8_t* obs
   }
   if (inc) OTHER(R, launch_gather_pred(x32, out, T, B, Q, Lq, E, R.st, has_act), "gather_pred");   // the last obs row of every slot (T = 1: row Lq - 1)
   else if (out) OTHER(R, launch_gather_pred(x32, out, T, B, Q, Lq, E, R.st), "gather_pred");
-  if (hist) OTHER(R, launch_history_install(dmask, hlist, hmap, B, Lq, Lmax, h->ep_mask, h->ep_poscnt, h->ep_fresh, R.st), "history_install");
+  if (hist)   // lo = hi = 0: the restart in front of this pass has cleared the samples' mask rows
+    OTHER(R, launch_history_install(dmask, hlist, hmap, B, Lq, 0, 0, Lmax, h->ep_mask, h->ep_poscnt, h->ep_fresh, R.st), "history_install");
   if (dual && join_aux(R)) return 1;
   return R.err;
 }
@@ -2351,24 +2365,24 @@ int vima_decode_restart(VimaHandle* h, const uint8_t* restart, int B, const floa
   Run R{h, (hipStream_t)stream};
   h->restart_list = flagged_list(restart, B);
   const int n_r = (int)h->restart_list.size();
-  const bool batched = h->restart_batched != 0 && Lp > 32 && n_r > 0;
+  if (n_r == 0) return 0;   // nothing flagged: nothing to launch
+  const bool batched = h->restart_batched != 0 && Lp > 32;
   const int n_ws = batched ? n_r : 1;
-  uint8_t* flags = R.ws<uint8_t>((size_t)B);
-  int* list = batched ? R.ws<int>((size_t)n_r) : nullptr;
+  int* list = R.ws<int>((size_t)n_r);
   void* pT = R.wsT((size_t)n_ws * Lp * E);
   void* kvrow = (h->kv_hm || batched) ? R.wsT((size_t)n_ws * Lp * 2 * E) : nullptr;   // row-major K | V before the scatter / the head-major transposition
   if (R.err) return R.err;
-  HIPCK(hipMemcpyAsync(flags, restart, (size_t)B, hipMemcpyHostToDevice, R.st));
-  OTHER(R, launch_restart_samples(flags, h->ep_mask, h->ep_poscnt, h->ep_fresh, B, h->ep_Lmax, R.st), "restart_samples");
-  const size_t kv_layer_bytes = (size_t)B * Lp * 2 * E * h->esz();
+  HIPCK(hipMemcpyAsync(list, h->restart_list.data(), (size_t)n_r * sizeof(int), hipMemcpyHostToDevice, R.st));
+  OTHER(R, launch_episode_restart(list, n_r, h->ep_mask, h->ep_poscnt, h->ep_fresh, 0, h->ep_Lmax, h->ep_Lmax, R.st), "restart_samples");
+  KvRowsArgs c;   // row-major K | V rows of kvrow -> the samples' blocks of a layer of the prompt K / V cache, in the cache's layout
+  c.in = kvrow; c.L = c.Lc = Lp; c.N = c.ld = 2 * E; c.D = h->kv_hm ? E / h->cfg.xattn_n_heads : 0;
   if (batched) {
-    HIPCK(hipMemcpyAsync(list, h->restart_list.data(), (size_t)n_r * sizeof(int), hipMemcpyHostToDevice, R.st));
     OTHER(R, launch_prompt_pos(prompt, stride_b, stride_l, prompt_mask, h->xpos_emb, h->cfg.xattn_n_positions, pT, n_r, Lp, E, h->bf16, R.st, list),
           "prompt_pos");
     for (int i = 0; i < NL && !R.err; ++i) {
       R.linear(pT, E, h->dec[i].kv, n_r * Lp, ACT_NONE, nullptr, 0, nullptr, 0, nullptr, 0, kvrow, 2 * E);
-      OTHER(R, launch_kv_scatter(kvrow, reinterpret_cast<char*>(h->kv_cache) + kv_layer_bytes * i, list, n_r, Lp, 2 * E, E / h->cfg.xattn_n_heads,
-                                 h->kv_hm ? 1 : 0, h->bf16, R.st), "kv_scatter");
+      c.out = kv_layer(h, i, Lp); c.list = list; c.n = n_r;
+      OTHER(R, launch_kv_rows(c, (int)h->esz(), R.st), "kv_scatter");
     }
   }
   for (int b = 0; b < B && !R.err && !batched; ++b) {
@@ -2376,12 +2390,13 @@ int vima_decode_restart(VimaHandle* h, const uint8_t* restart, int B, const floa
     OTHER(R, launch_prompt_pos(prompt + (long long)b * stride_b, stride_b, stride_l, prompt_mask + (long long)b * Lp, h->xpos_emb,
                                h->cfg.xattn_n_positions, pT, 1, Lp, E, h->bf16, R.st), "prompt_pos");
     for (int i = 0; i < NL; ++i) {
-      void* KV = reinterpret_cast<char*>(h->kv_cache) + kv_layer_bytes * i + (size_t)b * Lp * 2 * E * h->esz();
+      void* KV = R.offT(kv_layer(h, i, Lp), (long long)b * Lp * 2 * E);
       if (!h->kv_hm) {
         R.linear(pT, E, h->dec[i].kv, Lp, ACT_NONE, nullptr, 0, nullptr, 0, nullptr, 0, KV, 2 * E);
       } else {   // head-major cache: the sample's block is [2 Hx][Lp][Dx]; Lp rows are too few for the kernel that writes it directly
         R.linear(pT, E, h->dec[i].kv, Lp, ACT_NONE, nullptr, 0, nullptr, 0, nullptr, 0, kvrow, 2 * E);
-        OTHER(R, launch_rows_to_headmajor(kvrow, KV, Lp, 2 * E, E / h->cfg.xattn_n_heads, h->bf16, R.st), "rows_to_headmajor");
+        c.out = KV; c.n = 1;
+        OTHER(R, launch_kv_rows(c, (int)h->esz(), R.st), "rows_to_headmajor");
       }
     }
   }
@@ -2573,12 +2588,12 @@ int vima_seq_prefill(VimaHandle* h, const float* prompt, int64_t stride_b, int64
   uint8_t* mask = R.ws<uint8_t>((size_t)B * L);
   if (R.err) return R.err;
   HIPCK(hipMemsetAsync(h->ep_fresh, 0, (size_t)B, R.st));
-  OTHER(R, launch_seq_embed_prefill(prompt, stride_b, stride_l, prompt_mask, h->sep_token, h->pos_emb, Lmax, x32, xT, mask, h->ep_mask,
-                                    h->ep_poscnt, nullptr, B, Lp, E, h->bf16, R.st), "seq_embed_prefill");
-  if (hfgpt_stack(R, x32, xT, mask, B, L, h->ep_kv, nullptr, B, Lmax)) return R.err;
+  h->ep_B = B; h->ep_Q = rgb_tokens_per_image(h->cfg.policy_kind); h->ep_Lp = Lp; h->ep_Lmax = Lmax;   // (ep_layer reads the caches' shape)
+  OTHER(R, launch_seq_embed(prompt, stride_b, stride_l, prompt_mask, h->sep_token, nullptr, nullptr, h->pos_emb, Lmax, x32, xT, mask, B, L, Lp, h->ep_Q,
+                            E, h->bf16, R.st, nullptr, h->ep_mask, h->ep_poscnt, Lmax), "seq_embed_prefill");
+  if (hfgpt_stack(R, x32, xT, mask, B, L, true)) return R.err;
   h->seq_live = true;
-  h->book.begin(B, rgb_tokens_per_image(h->cfg.policy_kind), L, Lmax, h->seq_ring != 0);   // the fixed prefix: prompt + separator
-  h->ep_B = B; h->ep_Q = rgb_tokens_per_image(h->cfg.policy_kind); h->ep_Lp = Lp; h->ep_Lmax = Lmax;
+  h->book.begin(B, h->ep_Q, L, Lmax, h->seq_ring != 0);   // the fixed prefix: prompt + separator
   return 0;
 }
 
@@ -2668,10 +2683,10 @@ int vima_seq_decode_restart(VimaHandle* h, const uint8_t* restart, int B, const 
   if (R.err) return R.err;
   HIPCK(hipMemcpyAsync(list, h->restart_list.data(), (size_t)n_r * sizeof(int), hipMemcpyHostToDevice, R.st));
   // ring mode: the sample's history may lie anywhere in the written part [P0, hw) of the ring
-  OTHER(R, launch_seq_restart(list, n_r, h->ep_mask, h->ep_fresh, L, h->book.written_end(), Lmax, R.st), "seq_restart");
-  OTHER(R, launch_seq_embed_prefill(prompt, stride_b, stride_l, prompt_mask, h->sep_token, h->pos_emb, Lmax, x32, xT, mask, h->ep_mask,
-                                    h->ep_poscnt, list, n_r, Lp, E, h->bf16, R.st), "seq_embed_prefill");
-  hfgpt_stack(R, x32, xT, mask, n_r, L, h->ep_kv, list, B, Lmax);
+  OTHER(R, launch_episode_restart(list, n_r, h->ep_mask, nullptr, h->ep_fresh, L, h->book.written_end(), Lmax, R.st), "seq_restart");
+  OTHER(R, launch_seq_embed(prompt, stride_b, stride_l, prompt_mask, h->sep_token, nullptr, nullptr, h->pos_emb, Lmax, x32, xT, mask, n_r, L, Lp, h->ep_Q,
+                            E, h->bf16, R.st, list, h->ep_mask, h->ep_poscnt, Lmax), "seq_embed_prefill");
+  hfgpt_stack(R, x32, xT, mask, n_r, L, true, list);
   if (!R.err) h->book.restart(h->restart_list);
   return R.err;
 }
@@ -2732,9 +2747,9 @@ int vima_seq_decode_restart_history(VimaHandle* h, const uint8_t* restart, int B
   HIPCK(hipMemcpyAsync(hmap, h->hist_rowmap.data(), (size_t)L * sizeof(int), hipMemcpyHostToDevice, R.st));
   OTHER(R, launch_seq_embed(prompt, stride_b, stride_l, prompt_mask, h->sep_token, hist_obs, hist_act, h->pos_emb, h->cfg.n_positions, x32, xT, mask,
                             n_r, L, Lp, Q, E, h->bf16, R.st, list), "seq_embed");
-  if (hfgpt_stack(R, x32, xT, mask, n_r, L, h->ep_kv, list, B, Lmax, hmap)) return R.err;
+  if (hfgpt_stack(R, x32, xT, mask, n_r, L, true, list, hmap)) return R.err;
   if (out) OTHER(R, launch_gather_pred(x32 + (size_t)P0 * E, out, T, n_r, Q, L, E, R.st), "gather_pred");   // teacher-forced: the last obs row of every history step
-  OTHER(R, launch_seq_history_install(mask, list, hmap, n_r, L, P0, hi, Lmax, h->ep_mask, h->ep_poscnt, h->ep_fresh, R.st), "seq_history_install");
+  OTHER(R, launch_history_install(mask, list, hmap, n_r, L, P0, hi, Lmax, h->ep_mask, h->ep_poscnt, h->ep_fresh, R.st), "seq_history_install");
   if (!R.err) h->book.install(h->restart_list, age);
   return R.err;
 }
@@ -3237,8 +3252,18 @@ int vima_op_restart_samples(VimaHandle* h, const uint8_t* flags, uint8_t* hist_m
   if (int e = op_begin(h, fn)) return e;
   OP_REQ(flags && hist_mask && poscnt && fresh, "null argument");
   OP_REQ(B > 0 && Lmax > 0, "B and Lmax must be positive");
+  // a test entry, never captured: the DEVICE flags come back to the host, which builds the sample list launch_episode_restart takes
   Run R{h, (hipStream_t)stream};
-  OTHER(R, launch_restart_samples(flags, hist_mask, poscnt, fresh, B, Lmax, R.st), "vima_op_restart_samples: restart_samples");
+  std::vector<uint8_t> host((size_t)B);
+  HIPCK(hipMemcpyAsync(host.data(), flags, (size_t)B, hipMemcpyDeviceToHost, R.st));
+  HIPCK(hipStreamSynchronize(R.st));
+  const std::vector<int> flagged = flagged_list(host.data(), B);
+  if (flagged.empty()) return 0;
+  int* list = R.ws<int>(flagged.size());
+  if (R.err) return R.err;
+  HIPCK(hipMemcpyAsync(list, flagged.data(), flagged.size() * sizeof(int), hipMemcpyHostToDevice, R.st));
+  OTHER(R, launch_episode_restart(list, (int)flagged.size(), hist_mask, poscnt, fresh, 0, Lmax, Lmax, R.st), "vima_op_restart_samples: restart_samples");
+  HIPCK(hipStreamSynchronize(R.st));   // `flagged` is the source of the upload
   return R.err;
 }
 
@@ -3302,7 +3327,9 @@ int vima_op_rows_to_headmajor(VimaHandle* h, const float* in, int L, int N, int 
   void* iT = R.wsT((size_t)n); void* oT = R.wsT((size_t)n);
   if (R.err) return R.err;
   OTHER(R, launch_cast(in, iT, n, h->bf16, R.st), "cast");
-  OTHER(R, launch_rows_to_headmajor(iT, oT, L, N, D, h->bf16, R.st), "vima_op_rows_to_headmajor: rows_to_headmajor");
+  KvRowsArgs c;
+  c.in = iT; c.out = oT; c.n = 1; c.L = c.Lc = L; c.N = c.ld = N; c.D = D;
+  OTHER(R, launch_kv_rows(c, (int)h->esz(), R.st), "vima_op_rows_to_headmajor: rows_to_headmajor");
   return op_widen(R, oT, out, n);
 }
 
@@ -3319,7 +3346,9 @@ int vima_op_kv_scatter(VimaHandle* h, const float* in, const int32_t* list, int 
   OTHER(R, launch_cast(in, iT, ni, h->bf16, R.st), "cast");
   void* oT = op_stage_out(R, out, no);
   if (!oT) return R.err;
-  OTHER(R, launch_kv_scatter(iT, oT, list, n, L, N, D, hm, h->bf16, R.st), "vima_op_kv_scatter: kv_scatter");
+  KvRowsArgs c;
+  c.in = iT; c.out = oT; c.list = list; c.n = n; c.L = c.Lc = L; c.N = c.ld = N; c.D = hm ? D : 0;
+  OTHER(R, launch_kv_rows(c, (int)h->esz(), R.st), "vima_op_kv_scatter: kv_scatter");
   return op_widen(R, oT, out, no);
 }
 
@@ -3337,7 +3366,9 @@ int vima_op_seq_kv_store(VimaHandle* h, const float* in, int64_t ld_in, const in
   OTHER(R, launch_cast(in, iT, ni, h->bf16, R.st), "cast");
   void* oT = op_stage_out(R, out, no);
   if (!oT) return R.err;
-  OTHER(R, launch_seq_kv_store(iT, ld_in, oT, list, n, L, N, Lmax, h->bf16, R.st), "vima_op_seq_kv_store: seq_kv_store");
+  KvRowsArgs c;
+  c.in = iT; c.ld = ld_in; c.out = oT; c.list = list; c.n = n; c.L = L; c.N = N; c.Lc = Lmax;
+  OTHER(R, launch_kv_rows(c, (int)h->esz(), R.st), "vima_op_seq_kv_store: seq_kv_store");
   return op_widen(R, oT, out, no);
 }
 
@@ -3379,8 +3410,8 @@ int vima_op_seq_embed_prefill(VimaHandle* h, const float* prompt, int64_t sb, in
   const long long ne = (long long)n * (Lp + 1) * E;
   void* oT = R.wsT((size_t)ne);
   if (R.err) return R.err;
-  OTHER(R, launch_seq_embed_prefill(prompt, sb, sl, pmask, sep, pos_table, n_pos, x32, oT, mask, cache_mask, posbase, list, n, Lp, E, h->bf16, R.st),
-        "vima_op_seq_embed_prefill: seq_embed_prefill");
+  OTHER(R, launch_seq_embed(prompt, sb, sl, pmask, sep, nullptr, nullptr, pos_table, n_pos, x32, oT, mask, n, Lp + 1, Lp, 1, E, h->bf16, R.st, list,
+                            cache_mask, posbase, n_pos), "vima_op_seq_embed_prefill: seq_embed_prefill");
   return xT ? op_widen(R, oT, xT, ne) : R.err;
 }
 
@@ -3423,7 +3454,7 @@ int vima_op_seq_history_install(VimaHandle* h, const uint8_t* mask, const int32_
   OP_REQ(mask && list && rowmap && cache_mask && posbase && fresh, "null argument");
   OP_REQ(n > 0 && L > 0 && n_pos > 0, "n, L and n_pos must be positive");
   Run R{h, (hipStream_t)stream};
-  OTHER(R, launch_seq_history_install(mask, list, rowmap, n, L, lo, hi, n_pos, cache_mask, posbase, fresh, R.st),
+  OTHER(R, launch_history_install(mask, list, rowmap, n, L, lo, hi, n_pos, cache_mask, posbase, fresh, R.st),
         "vima_op_seq_history_install: seq_history_install");
   return R.err;
 }
@@ -3434,7 +3465,7 @@ int vima_op_seq_restart(VimaHandle* h, const int32_t* list, int n, int lo, int h
   OP_REQ(list && cache_mask && fresh, "null argument");
   OP_REQ(n > 0 && n_pos > 0, "n and n_pos must be positive");
   Run R{h, (hipStream_t)stream};
-  OTHER(R, launch_seq_restart(list, n, cache_mask, fresh, lo, hi, n_pos, R.st), "vima_op_seq_restart: seq_restart");
+  OTHER(R, launch_episode_restart(list, n, cache_mask, nullptr, fresh, lo, hi, n_pos, R.st), "vima_op_seq_restart: seq_restart");
   return R.err;
 }
 
