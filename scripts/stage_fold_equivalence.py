@@ -7,7 +7,8 @@ three fp8 calibrators, the baselines' ViT): profiles/stage_fold_equivalence.txt 
 Every case runs in a fresh child process per library (VIMA_HIP_LIB), one process at a time, each under its own time limit; the script stops
 at the first child that fails, times out or differs. Per case the two libraries must agree on: the SHA-256 of every output tensor's bytes,
 the GEMM launch log (kernel, M, N, K in launch order), the per-class launch counts / FLOPs / bytes and, in fp8 cases, the scale vectors
-of the three calibrated groups. The kernels are deterministic (amax is a max), so a difference is a bug, not noise."""
+of the three calibrated groups. The `episodes` group (scripts/episode_entry_cases.py; --only episodes) adds host values (history_room, steps_left,
+graph_stats) and, for every refused call, its return code and vima_last_error() text. The kernels are deterministic (amax is a max), so a difference is a bug, not noise."""
 import argparse
 import hashlib
 import json
@@ -25,7 +26,7 @@ class Rec:
     """What one child reports: output hashes, launch logs, scales and the facts that show a branch was engaged."""
 
     def __init__(self, pol):
-        self.pol, self.out = pol, {"sha256": {}, "gemm_log": [], "classes": {}, "scales": {}, "engaged": {}}
+        self.pol, self.out = pol, {"sha256": {}, "gemm_log": [], "classes": {}, "scales": {}, "values": {}, "refusals": [], "engaged": {}}
         pol.prof_enable(True)
 
     def tensor(self, name, t):
@@ -211,6 +212,11 @@ for _kind in ("gato", "gpt", "flamingo"):
         CASES["baseline %s %s" % (_kind, _prec)] = (180, lambda k=_kind, p=_prec: baseline_case(k, p))
 
 
+# the `episodes` group: the episode entry points of the C ABI and their refusals (scripts/episode_entry_cases.py)
+from scripts.episode_entry_cases import episode_cases  # noqa: E402
+CASES.update(episode_cases(Rec, DEV))
+
+
 def child(name):
     import torch
     with torch.no_grad():
@@ -250,7 +256,7 @@ def main():
         for k, v in b["engaged"].items():
             print("   engaged  %s: %s" % (k, v))
         same = True
-        for part in ("sha256", "gemm_log", "classes", "scales"):
+        for part in ("sha256", "gemm_log", "classes", "scales", "values", "refusals"):
             eq = a[part] == b[part]
             same = same and eq
             print("   %-8s %s" % (part, "EQUAL" if eq else "DIFFERENT"))
@@ -259,6 +265,10 @@ def main():
                     print("      %s: parent %s | new %s" % (k, a[part][k] if not isinstance(a[part], dict) or k in a[part] else None, b[part][k]))
         for call, cls in b["classes"].items():
             print("   launches %s: %s; GEMM log of %d launches" % (call, {k: v[0] for k, v in cls.items()}, sum(len(l) for nm, l in b["gemm_log"] if nm == call)))
+        for k, v in b["values"].items():
+            print("   value    %s: %s" % (k, v))
+        for r in b["refusals"]:
+            print("   refused  %s" % r)
         for call, sc in b["scales"].items():
             print("   scales   %s: %s" % (call, {g: (None if v is None else "%d values, sha256 %s" % (len(v), hashlib.sha256(json.dumps(v).encode()).hexdigest()[:16])) for g, v in sc.items()}))
         sys.stdout.flush()
@@ -266,7 +276,7 @@ def main():
             print("STOPPED: the libraries differ in this case")
             return 1
         n += 1
-    print("\nALL %d CASES EQUAL (output hashes, GEMM launch logs, per-class launch counts / FLOPs / bytes, fp8 scale vectors)" % n)
+    print("\nALL %d CASES EQUAL (output hashes, GEMM launch logs, per-class launch counts / FLOPs / bytes, fp8 scale vectors, host values, refusals)" % n)
     return 0
 
 

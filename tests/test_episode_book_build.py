@@ -1,5 +1,5 @@
 """The host bookkeeping of the episode caches itself (vima_amd/csrc/episode_book.h, the one EpisodeBook behind vima_decode_* and vima_seq_*) on the
-CPU: tests/episode_book_driver.cpp is compiled as a stand-alone host program under AddressSanitizer and UndefinedBehaviorSanitizer, run in a child
+CPU: tests/episode_book_driver.cpp is compiled (tests/episode_driver.py) as a stand-alone host program under AddressSanitizer and UndefinedBehaviorSanitizer, run in a child
 process, and compared line for line with the three Python restatements (tests/episode_prefill_reference.EpisodeBook for the prefix P0 = 0,
 tests/seq_prefill_reference.SeqBook on top of tests/seq_ring_reference.Ring for P0 = Lp + 1), which stay independent of it.
 
@@ -7,48 +7,14 @@ What the C++ adds to the restatements and the test derives by the stated rule: h
 win_end = 0, Lk = row + Lq; a refusal carries the steps that still fit for the offending sample (= its steps_left). The restatements name a unit
 longer than the whole ring by its first victim ("sample 0"; EpisodeBook at batch step 0: "longer than n_positions"); the C++ has a kind of its own
 for it ("long", sample 0), so that pair is the one place where the two are matched by rule and not by text."""
-import os
 import random
 import re
-import shutil
-import subprocess
 
 import pytest
 
 from tests import episode_prefill_reference as eref
 from tests import seq_prefill_reference as sref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FLAGS = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-# the sanitizer runtimes linked statically where the compiler has the choice: the program runs whatever else the process environment loads
-COMPILERS = (["g++", "-static-libasan", "-static-libubsan"], [os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++")], ["g++"])
-
-
-@pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("episode_book") / "episode_book_driver")
-    errors = []
-    for cc in COMPILERS:
-        if not shutil.which(cc[0]):
-            continue
-        r = subprocess.run(cc + FLAGS + ["-I", os.path.join(ROOT, "vima_amd", "csrc"), os.path.join(ROOT, "tests", "episode_book_driver.cpp"), "-o", exe],
-                           capture_output=True, text=True)
-        if r.returncode == 0:
-            return exe
-        errors.append(" ".join(cc) + ":\n" + r.stderr[-2000:])
-    raise AssertionError("no host compiler built the driver with -fsanitize=address,undefined:\n" + "\n".join(errors))
-
-
-def _run(exe, ops):
-    r = subprocess.run([exe], input="".join(o + "\n" for o in ops), capture_output=True, text=True)
-    assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr[-3000:])      # a sanitizer report ends the program with a non-zero status
-    lines = r.stdout.splitlines()
-    assert len(lines) == len(ops)
-    return lines
-
-
-def _flags(flags):
-    return " ".join("1" if f else "0" for f in flags)
+from tests.episode_driver import _flags, _run, driver  # noqa: F401
 
 
 class _Twin:
@@ -129,6 +95,13 @@ class _Twin:
             return f"rows {T}", f"refused room {self.room_now()}"
         return f"rows {T}", " ".join(map(str, ["rows", self._age(T)] + self.book.history_rows(T)))
 
+    def hist(self, T):
+        """EpisodeBook::history as the library's entries call it: the identity over the prefix, then the rows. Any other line is its range check
+        ([P0, written_end()) for every history row) failing; a history beyond the room is refused with the room"""
+        if T > self.room_now():
+            return f"hist {T}", f"refused room {self.room_now()}"
+        return f"hist {T}", " ".join(map(str, ["hist", self._age(T), "|"] + list(range(self.P0)) + self.book.history_rows(T)))
+
     def install(self, T, flags):
         op = f"install {T} " + _flags(flags)
         try:
@@ -176,7 +149,7 @@ class _Script:
 
 def _schedules(seq, seed=0, schedules=300):
     """The generator of the two selfcheck functions (restarts with probability 1 / 4 and of every sample out of steps, units of 1, 1, 2 or 3 steps,
-    every third schedule single steps only, every fourth linear), with real installs of 1, the room and a random T after every unit."""
+    every third schedule single steps only, every fourth linear), with real installs of 1, the room and a random T after every unit, each behind the table the library builds for it."""
     rng = random.Random(seed)
     sc = _Script()
     seen = dict(wrap_skips=0, chunk_refused_step_passes=0, installs=0, refused_installs=0, ring=0, linear=0)
@@ -219,9 +192,11 @@ def _schedules(seq, seed=0, schedules=300):
                 if Th < 1 or Th > room:
                     continue
                 sc.add(*twin.rows(Th))
+                sc.add(*twin.hist(Th))
                 sc.add(*twin.install(Th, [rng.random() < 0.5 for _ in range(B)]))
                 sc.after(twin)
                 seen["installs"] += 1
+            sc.add(*twin.hist(room + 1))                            # one step more than the room: refused with the room, whatever the record holds
             if room < min(len(twin.book.slots), Lmax):
                 sc.add(*twin.rows(room + 1))
                 sc.add(*twin.install(room + 1, [True] * B))

@@ -1,9 +1,10 @@
 """Branch rollouts (vima_decode_fork / vima_seq_decode_fork / vima_op_episode_fork, episode_fork_kernel) without a GPU: the fork bookkeeping of
 vima_amd/csrc/episode_book.h (fork_ok, fork, live_ranges) in a stand-alone host program under AddressSanitizer and UndefinedBehaviorSanitizer
-(tests/episode_fork_driver.cpp, built and run exactly like tests/episode_book_driver.cpp) against the brute-force restatement of
+(tests/episode_book_driver.cpp, built by tests/episode_driver.py) against the brute-force restatement of
 tests/episode_fork_reference.py over 300 random schedules; the C ABI declares, exports and binds the three functions; the Python surface; the
 kernel cross-compiles for gfx950 without scratch; and the scenario of tests/test_episode_fork_gpu.py contains the forks it is about."""
 import ctypes
+import functools
 import inspect
 import os
 import random
@@ -14,42 +15,14 @@ import subprocess
 import pytest
 
 from vima_amd import _lib
+from tests import episode_driver
 from tests import episode_fork_reference as fref
+from tests.episode_driver import ROOT, _ints, driver  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 needs_hipcc = pytest.mark.skipif(not shutil.which(HIPCC) and not os.path.exists(HIPCC), reason="hipcc not available")
 NEW = ("vima_decode_fork", "vima_seq_decode_fork", "vima_op_episode_fork")
-FLAGS = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-# the sanitizer runtimes linked statically where the compiler has the choice: the program runs whatever else the process environment loads
-COMPILERS = (["g++", "-static-libasan", "-static-libubsan"], [os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++")], ["g++"])
-
-
-@pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("episode_fork") / "episode_fork_driver")
-    errors = []
-    for cc in COMPILERS:
-        if not shutil.which(cc[0]):
-            continue
-        r = subprocess.run(cc + FLAGS + ["-I", os.path.join(ROOT, "vima_amd", "csrc"), os.path.join(ROOT, "tests", "episode_fork_driver.cpp"), "-o", exe],
-                           capture_output=True, text=True)
-        if r.returncode == 0:
-            return exe
-        errors.append(" ".join(cc) + ":\n" + r.stderr[-2000:])
-    raise AssertionError("no host compiler built the driver with -fsanitize=address,undefined:\n" + "\n".join(errors))
-
-
-def _run(exe, ops):
-    r = subprocess.run([exe], input="".join(o + "\n" for o in ops), capture_output=True, text=True)
-    assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr[-3000:])      # a sanitizer report ends the program with a non-zero status
-    lines = r.stdout.splitlines()
-    assert len(lines) == len(ops)
-    return lines
-
-
-def _ints(xs):
-    return " ".join(str(int(x)) for x in xs)
+_run = functools.partial(episode_driver._run, brief=True)
 
 
 class _Script:

@@ -1,6 +1,6 @@
 """Episode snapshots (vima_decode_snapshot / vima_decode_restore, the vima_seq_* pair, vima_op_episode_pack / _unpack) without a GPU: the
 bookkeeping of vima_amd/csrc/episode_book.h (steps_of, history_rows, install) in a stand-alone host program under AddressSanitizer and
-UndefinedBehaviorSanitizer (tests/episode_snapshot_driver.cpp, built and run exactly like tests/episode_fork_driver.cpp) against the brute-force
+UndefinedBehaviorSanitizer (tests/episode_book_driver.cpp, built by tests/episode_driver.py) against the brute-force
 restatement of tests/episode_snapshot_reference.py over 300 random schedules per cache family; the C ABI declares, exports and binds the new
 functions; the Python surface; the kernels cross-compile for gfx950 without scratch and LDS; and the scenario of
 tests/test_episode_snapshot_gpu.py contains the snapshots and restores it is about."""
@@ -9,40 +9,17 @@ import inspect
 import os
 import random
 import re
-import shutil
 import subprocess
 
 import pytest
 
 from vima_amd import _lib
 from tests import episode_snapshot_reference as sref
-from tests.test_episode_fork_build import COMPILERS, FLAGS, HIPCC, ROOT, _ints, _random_source, needs_hipcc
+from tests.episode_driver import ROOT, _ints, driver  # noqa: F401
+from tests.test_episode_fork_build import HIPCC, _random_source, _run, needs_hipcc
 
 NEW = ("vima_decode_snapshot_size", "vima_decode_snapshot", "vima_decode_restore", "vima_seq_decode_snapshot_size", "vima_seq_decode_snapshot",
        "vima_seq_decode_restore", "vima_op_episode_pack", "vima_op_episode_unpack")
-
-
-@pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("episode_snapshot") / "episode_snapshot_driver")
-    errors = []
-    for cc in COMPILERS:
-        if not shutil.which(cc[0]):
-            continue
-        r = subprocess.run(cc + FLAGS + ["-I", os.path.join(ROOT, "vima_amd", "csrc"), os.path.join(ROOT, "tests", "episode_snapshot_driver.cpp"), "-o", exe],
-                           capture_output=True, text=True)
-        if r.returncode == 0:
-            return exe
-        errors.append(" ".join(cc) + ":\n" + r.stderr[-2000:])
-    raise AssertionError("no host compiler built the driver with -fsanitize=address,undefined:\n" + "\n".join(errors))
-
-
-def _run(exe, ops):
-    r = subprocess.run([exe], input="".join(o + "\n" for o in ops), capture_output=True, text=True)
-    assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr[-3000:])      # a sanitizer report ends the program with a non-zero status
-    lines = r.stdout.splitlines()
-    assert len(lines) == len(ops)
-    return lines
 
 
 class _Script:
@@ -142,6 +119,11 @@ def _schedules(seq, seed=0, schedules=300):
             p = bk.step(T)
             sc.add(f"step {T}", "refused" if p is None else f"plan {p[0]} {p[1]} {p[2]}")
             sc.after(bk)
+            # EpisodeBook::history as the entries call it, for the longest history that fits (the identity over the prefix, then the rows; any other
+            # line is its range check failing) and for one step more (refused with the room)
+            room = bk.room()
+            sc.add(f"hist {room}", f"hist {sum(bk.adv[len(bk.adv) - room:]) if room else 0}" + _rows(list(range(P0)) + bk.rows_of_last(room)))
+            sc.add(f"hist {room + 1}", f"refused room {room}")
             if p is None:
                 if T == 1:
                     assert not ring, "ring: every sample out of steps was restarted, a single step must pass"

@@ -13,30 +13,17 @@ Both are data recorded from the parent, none of it is what the code under test g
 vima_op_gemm and so have no route rows: they are held by the gemm_a8_ok / gemm_headmajor_ok(a8 = 1) columns here, by tests/test_fp8_gpu.py and
 by whole-model launch logs (profiles/gemm_route_launch_logs.txt)."""
 import os
-import shutil
 import subprocess
 
 import pytest
 
 from tests import gemm_route_cases as C
-from tests.test_episode_book_build import COMPILERS, FLAGS
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.episode_driver import ROOT, build_driver
 
 
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("gemm_route") / "gemm_route_driver")
-    errors = []
-    for cc in COMPILERS:
-        if not shutil.which(cc[0]):
-            continue
-        r = subprocess.run(cc + FLAGS + ["-I", os.path.join(ROOT, "vima_amd", "csrc"), os.path.join(ROOT, "tests", "gemm_route_driver.cpp"), "-o", exe],
-                           capture_output=True, text=True)
-        if r.returncode == 0:
-            return exe
-        errors.append(" ".join(cc) + ":\n" + r.stderr[-2000:])
-    raise AssertionError("no host compiler built the driver with -fsanitize=address,undefined:\n" + "\n".join(errors))
+    return build_driver(tmp_path_factory, "gemm_route_driver")
 
 
 @pytest.fixture(scope="module")

@@ -12,7 +12,7 @@ import subprocess
 import pytest
 
 from tests import gemm_route_cases as C
-from tests.test_episode_book_build import COMPILERS, FLAGS
+from tests.episode_driver import COMPILERS, FLAGS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NCU = 256

@@ -176,7 +176,7 @@ int hfgpt_stack(Run& R, float* x32, void* xT, const uint8_t* mask, int B, int L,
     R.linear(xT, E, D.c_attn, rq, ACT_NONE, nullptr, 0, nullptr, 0, nullptr, 0, qkv, 3 * E);
     if (kv_store) {
       KvRowsArgs c;
-      c.in = R.offT(qkv, E); c.ld = 3 * E; c.out = ep_layer(h, i); c.list = kv_list; c.rowmap = kv_rowmap; c.n = B; c.L = L; c.N = 2 * E; c.Lc = h->ep_Lmax;
+      c.in = R.offT(qkv, E); c.ld = 3 * E; c.out = ep_layer(h, i); c.list = kv_list; c.rowmap = kv_rowmap; c.n = B; c.L = L; c.N = 2 * E; c.Lc = h->ep.Lmax;
       OTHER(R, launch_kv_rows(c, (int)h->esz(), R.st), kv_rowmap ? "kv_scatter_rows" : "seq_kv_store");
     }
     AttnArgs s;   // Attention._attn (gpt/gpt.py:268-301): /sqrt(d), w*b + -1e4*(1-b), + (1-mask)*finfo.min

@@ -1,5 +1,5 @@
 // Host bookkeeping of an episode cache: which cache rows the next env steps of a batch write, and which may be overwritten. Plain C++17, no HIP:
-// tests/episode_book_driver.cpp and tests/episode_fork_driver.cpp (forks), tests/episode_snapshot_driver.cpp (snapshots) hold it on the CPU against the Python restatements.
+// tests/episode_book_driver.cpp holds it on the CPU against the Python restatements (units, forks, snapshots).
 //
 // Rows [0, P0) of every sample's cache block are a fixed prefix (P0 = 0 for the XAttnGPT policies, prompt + separator for GPT / Gato); the rows
 // [P0, Lmax) behind it are ONE row index space for the whole batch, linear or a ring (options decode_ring / seq_ring). A call of T env steps is one
@@ -79,6 +79,23 @@ struct EpisodeBook {
   }
 
   void install(const std::vector<int>& list, int a) { for (int b : list) age[(size_t)b] = a; }
+
+  // A history of the last T batch steps as every entry installs it (restart with a history, snapshot, restore). fits: the room rule, 0 <= T <=
+  // room -- nothing else is filled when it fails. rows: [the identity over the prefix [0, P0), when asked | history_rows(T)]; age: what
+  // history_rows returns (T = 0: 0). in_range: every history row lies in [P0, written_end()) -- a batch step wrote each of them, so a row outside
+  // is an error of this book
+  struct History { bool fits, in_range; int room, age; std::vector<int> rows; };
+  History history(int T, bool with_prefix) const {
+    History H{false, true, room(), 0, {}};
+    H.fits = T >= 0 && T <= H.room;
+    if (!H.fits) return H;
+    const int P = with_prefix ? P0 : 0, R = std::max(T * (Q + 1) - 1, 0);
+    H.rows.resize((size_t)P + R);
+    for (int l = 0; l < P; ++l) H.rows[(size_t)l] = l;
+    if (T > 0) H.age = history_rows(T, H.rows.data() + P);
+    for (int l = P; l < P + R; ++l) H.in_range = H.in_range && H.rows[(size_t)l] >= P0 && H.rows[(size_t)l] < written_end();
+    return H;
+  }
 
   // Episode snapshots: the number n of env steps sample b's episode has taken -- the trailing slots whose advances sum to age[b] exactly (0 right
   // after a restart); history_rows(n, .) then lists the episode's rows in compact time order. -1 when no suffix of the slot record sums to the age

@@ -223,25 +223,25 @@ struct VimaHandle {
   hipStream_t aux = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   std::vector<hipEvent_t> ev_layer;   // per decoder layer: "prompt K/V of layer i projected" (aux -> main)
-  // cross-step prompt K/V cache: per-layer key_value(prompt + pos-emb) (components.py:175) is
-  // loop-invariant across the env steps of an episode
-  void* kv_cache = nullptr;
-  size_t kv_cache_bytes = 0;
-  int kv_B = 0, kv_Lp = 0;
-  bool kv_valid = false;
-  // incremental decoding (vima_decode_step): per-layer self-attention K/V of the history [NL][B][ep_Lmax][2E] (operand
-  // type), its key mask [B][ep_Lmax] and the per-sample count of valid tokens (next position id)
-  void* ep_kv = nullptr; size_t ep_kv_bytes = 0;
-  uint8_t* ep_mask = nullptr; int* ep_poscnt = nullptr; size_t ep_aux_cap = 0;
-  uint8_t* ep_fresh = nullptr;   // [B] 1 = the sample was restarted (vima_decode_restart): its next step has no previous action
-  int ep_B = 0, ep_Q = 0, ep_Lmax = 0, ep_Lp = 0, ep_step = -1;
-  // decoder-only episode (vima_seq_prefill / vima_seq_decode_step; GPT / GATO handles, which never run vima_decode_step: ep_kv / ep_mask / ep_poscnt /
-  // ep_fresh, ep_B / ep_Q / ep_Lp / ep_Lmax and the book are theirs)
-  bool seq_live = false;
-  // The ONE row index space of the episode caches behind the fixed prefix (XAttnGPT: none; GPT / GATO: prompt + separator), linear or a ring (options
-  // "decode_ring" / "seq_ring"): write pointer, high-water mark, next batch step, per-sample ages and the slot record (episode_book.h). Valid while
-  // ep_step >= 0 / seq_live; decode_prepare / seq_prepare plan, decode_commit / the seq entries commit
-  EpisodeBook book;
+  // cross-step prompt K/V cache: per-layer key_value(prompt + pos-emb) (components.py:175) is loop-invariant across the env
+  // steps of an episode. Built by kv_cache_mode 1 (full-history vima_decode, step 0 of an episode) for B samples of Lp rows; hm: its layout as
+  // built, [B][2 Hx][Lp][D] instead of [B * Lp][2E]
+  struct PromptKV { void* ptr = nullptr; size_t bytes = 0; int B = 0, Lp = 0; bool valid = false, hm = false; } pkv;
+  // The episode batch of incremental decoding (vima_decode_step on VIMA / Flamingo handles, vima_seq_prefill / vima_seq_decode_step on GPT / GATO
+  // handles; a handle runs one family only): per-layer self-attention K | V of the history [NL][B][Lmax][2E] (operand type), its key mask
+  // [B][Lmax], the per-sample count of valid tokens (next position id) and fresh [B], 1 = the sample was restarted: its next step has no previous
+  // action. book: the ONE row index space of the caches behind the fixed prefix (XAttnGPT: none; GPT / GATO: prompt + separator), linear or a
+  // ring (options "decode_ring" / "seq_ring"): write pointer, high-water mark, next batch step, per-sample ages and the slot record
+  // (episode_book.h). live: a batch is running and the book is valid -- false from a step-0 decode_prepare until decode_commit, and from the
+  // start of vima_seq_prefill until its end; ep_running() is the one check of it
+  struct Episode {
+    void* kv = nullptr; size_t kv_bytes = 0;
+    uint8_t* mask = nullptr; int* poscnt = nullptr; size_t aux_cap = 0;
+    uint8_t* fresh = nullptr;
+    int B = 0, Q = 0, Lp = 0, Lmax = 0;
+    bool live = false;
+    EpisodeBook book;
+  } ep;
   int seq_ring = 0, decode_ring = 0;
   int restart_batched = 1;                       // option "restart_batched": vima_decode_restart rebuilds the flagged samples' prompt K / V together (0: one sample at a time)
   std::vector<int> restart_list;                 // host copy of the flagged sample indices (source of the upload)
@@ -285,7 +285,6 @@ struct VimaHandle {
                                                  // XAttention's feed-forward folded into the GEMMs either side of it (GemmArgs::sum_out / rs_sum) where the GEGLU pair forms exist
   int geglu_pair = 1;                            // option "geglu_pair": GEGLU layers whose two products read the same input run as ONE launch over block-interleaved weights where gemm_pair_ok()
   int kv_headmajor = 1;                          // option "kv_headmajor": write the decoder's prompt K / V head-major where the projection GEMM allows it
-  bool kv_hm = false;                            // layout of the prompt K / V CACHE as built (kv_cache_mode 1): [B][2 Hx][Lp][D] instead of [B * Lp][2E]
   Lin t5_post; bool has_t5_post = false;
   float *pos_emb = nullptr, *xpos_emb = nullptr;
   struct DecLayer {
@@ -811,6 +810,14 @@ struct Run {
     if (!p && !err) err = fail("workspace allocation failed");
     return p;
   }
+  // A handle-owned host vector -> the workspace carved for it, on the stream (the vector is the source of an asynchronous copy: it must outlive the
+  // call). Issued where the open-coded copies were: behind the call's workspace carving and its R.err check
+  template <typename P> int upload(P* dst, const std::vector<P>& v) {
+    if (err) return err;
+    const hipError_t e = hipMemcpyAsync(dst, v.data(), v.size() * sizeof(P), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) err = fail(std::string("hipMemcpyAsync (upload): ") + hipGetErrorString(e), (int)e);
+    return err;
+  }
   void* offT(void* p, long long elems) const { return reinterpret_cast<char*>(p) + elems * (long long)h->esz(); }
   const void* offT(const void* p, long long elems) const { return reinterpret_cast<const char*>(p) + elems * (long long)h->esz(); }
 
@@ -947,13 +954,16 @@ struct Run {
   } while (0)
 
 // ------------------------------------------------------------------------------------------------ episode cache (decode_launch, hfgpt_step_stack)
-// Layer i of the episode batch's caches (ep_B samples): the self-attention K | V cache [NL][ep_B][ep_Lmax][2E] and the prompt K / V cache
-// [NL][ep_B][Lp][2E] (either layout)
+// the episode family of the handle: vima_seq_* (GPT / GATO, decoder-only) or vima_decode_* (VIMA / Flamingo, XAttnGPT)
+bool ep_seq(const VimaHandle* h) { return h->cfg.policy_kind == VIMA_POLICY_GPT || h->cfg.policy_kind == VIMA_POLICY_GATO; }
+
+// Layer i of the episode batch's caches (ep.B samples): the self-attention K | V cache [NL][ep.B][ep.Lmax][2E] and the prompt K / V cache
+// [NL][ep.B][Lp][2E] (either layout)
 void* ep_layer(const VimaHandle* h, int i) {
-  return reinterpret_cast<char*>(h->ep_kv) + (size_t)i * h->ep_B * h->ep_Lmax * 2 * h->cfg.embed_dim * h->esz();
+  return reinterpret_cast<char*>(h->ep.kv) + (size_t)i * h->ep.B * h->ep.Lmax * 2 * h->cfg.embed_dim * h->esz();
 }
 void* kv_layer(const VimaHandle* h, int i, int Lp) {
-  return reinterpret_cast<char*>(h->kv_cache) + (size_t)i * h->ep_B * Lp * 2 * h->cfg.embed_dim * h->esz();
+  return reinterpret_cast<char*>(h->pkv.ptr) + (size_t)i * h->ep.B * Lp * 2 * h->cfg.embed_dim * h->esz();
 }
 
 // c_attn of the new rows xT [rq = B Lq, E]: q dense [rq, E], k | v APPENDED to the layer's episode cache [B][Lmax][2E] by the GEMM's row-remap
@@ -985,7 +995,7 @@ int c_attn_append(Run& R, const Lin& c_attn, const void* xT, int rq, int Lq, int
 void attn_from_cache(Run& R, AttnArgs& s, const void* q, void* cache, int row, int Lmax, int Lk, int win_end) {
   const int E = R.h->cfg.embed_dim;
   s.q = q; s.ldq = E; s.k = cache; s.ldk = 2 * E; s.v = R.offT(cache, E); s.ldv = 2 * E;
-  s.kmask = R.h->ep_mask; s.Lk = Lk; s.Lk_rows = Lmax; s.q_off = row; s.win_end = win_end;
+  s.kmask = R.h->ep.mask; s.Lk = Lk; s.Lk_rows = Lmax; s.q_off = row; s.win_end = win_end;
 }
 
 // ------------------------------------------------------------------------------------------------ stages
@@ -1581,6 +1591,22 @@ void set_bounds(ActSelectArgs& s, const float* bounds) {
 
 #include "baselines.inc"
 
+// One unit of the running episode batch -- T env steps as ONE pass (decode_launch's incremental branch, seq_step_launch) of Lq = T (Q + 1) rows per
+// sample (one fewer at batch step 0) at one row offset, one unit of the ring, instead of T passes of Q + 1 rows; 1 / T of the launches -- and its
+// commit on success. A step (T = 1) is the only form that is graphed, under the caller's key. A longer chunk runs eager also with option "graphs":
+// it is a rare call (prefill, resume), and every distinct (T, row, keys read) would be a graph of its own; the step graphs captured before stay
+// valid (they read the episode state from the device and the plan from their key) and are replayed again from the next step on.
+// Ring mode: the launch sequence of a step depends on (write pointer, keys read, action slot), not on the step number -- from the second lap on
+// the write pointers repeat, so the set of captured graphs stays bounded however long the rollout runs -- and one eager step with an action slot
+// warms all of them (`warm`: same shapes, same workspace, same kernels: the attention launcher picks by Lk < 64 / >= 64): each (write pointer,
+// keys read) is captured when first seen.
+template <class Launch, class Commit>
+int episode_unit(VimaHandle* h, int T, hipStream_t stream, const std::string& key, const std::string& warm, Launch launch, Commit commit) {
+  const int rc = T > 1 ? launch(stream) : run_graphed(h, key, stream, launch, warm);
+  if (!rc) commit();
+  return rc;
+}
+
 }  // namespace
 
 // =================================================================================================== C ABI
@@ -1644,11 +1670,11 @@ void vima_destroy(VimaHandle* h) {
   h->arena.release();
   for (auto e : h->ev_pool) (void)hipEventDestroy(e);
   for (auto e : h->ev_layer) (void)hipEventDestroy(e);
-  if (h->kv_cache) (void)hipFree(h->kv_cache);
-  if (h->ep_kv) (void)hipFree(h->ep_kv);
-  if (h->ep_mask) (void)hipFree(h->ep_mask);
-  if (h->ep_poscnt) (void)hipFree(h->ep_poscnt);
-  if (h->ep_fresh) (void)hipFree(h->ep_fresh);
+  if (h->pkv.ptr) (void)hipFree(h->pkv.ptr);
+  if (h->ep.kv) (void)hipFree(h->ep.kv);
+  if (h->ep.mask) (void)hipFree(h->ep.mask);
+  if (h->ep.poscnt) (void)hipFree(h->ep.poscnt);
+  if (h->ep.fresh) (void)hipFree(h->ep.fresh);
   drop_graphs(h);
   if (h->ev_gin) (void)hipEventDestroy(h->ev_gin);
   if (h->ev_gout) (void)hipEventDestroy(h->ev_gout);
@@ -1756,9 +1782,11 @@ int vima_set_option(VimaHandle* h, const char* key, int64_t value) {
   else if (k == "op_bias_far") h->op_bias_far = (int)value;
   else if (k == "geglu_pair") h->geglu_pair = (int)value;
   else if (k == "ln_fuse") h->ln_fuse = (int)value;
-  else if (k == "kv_headmajor") { h->kv_headmajor = (int)value; h->kv_valid = false; h->ep_step = -1; }   // the next decode rebuilds the cache in the chosen layout; a running episode (vima_decode_step) ends: start a new one with step 0
-  else if (k == "decode_ring") { h->decode_ring = value != 0; h->ep_step = -1; h->seq_live = false; }   // a running episode (vima_decode_step) ends: start a new one with step 0
-  else if (k == "seq_ring") { h->seq_ring = value != 0; h->seq_live = false; }   // a running episode (vima_seq_decode_step) ends: start a new one with vima_seq_prefill
+  // The episode has ONE live flag for both families (ep_seq): decode_ring ends the running episode of every handle kind, kv_headmajor that of an
+  // XAttnGPT handle, seq_ring that of a decoder-only handle -- start a new one with vima_decode_step(step = 0) / vima_seq_prefill
+  else if (k == "kv_headmajor") { h->kv_headmajor = (int)value; h->pkv.valid = false; if (!ep_seq(h)) h->ep.live = false; }   // the next decode rebuilds the cache in the chosen layout
+  else if (k == "decode_ring") { h->decode_ring = value != 0; h->ep.live = false; }
+  else if (k == "seq_ring") { h->seq_ring = value != 0; if (ep_seq(h)) h->ep.live = false; }
   else if (k == "restart_batched") h->restart_batched = (int)value;
   else if (k == "t5_fuse_rms") h->t5_fuse_rms = (int)value;
   else if (k == "stream_T") h->stream_T = (int)value;
@@ -1981,22 +2009,42 @@ static int plan_refused(const char* fn, const char* restart_fn, const EpisodeBoo
               ", or take fewer steps at once (a chunk skips the ring's tail as ONE unit)", 34);
 }
 
+// THE check that an episode batch of the entry's family is running (seq: the vima_seq_* entries, else vima_decode_*). B / Lp: what the entry
+// compares (kAny: not that one); prompt_kv: the batch's prompt K / V cache must stand too (the XAttnGPT entries that read or rebuild it; valid
+// beside a live episode it has the batch's B and Lp: only decode_commit writes the three). which: how the entry words the batch it asks for;
+// family: its own refusal of a handle of the other family (nullptr: it has none, such a handle simply has no running batch)
+constexpr int kAny = -1;
+static int ep_running(const VimaHandle* h, const char* fn, bool seq, int B, int Lp, bool prompt_kv, const char* which, const char* family = nullptr) {
+  const bool mine = ep_seq(h) == seq;
+  if (!mine && family) return fail(std::string(fn) + ": " + family);
+  const VimaHandle::Episode& e = h->ep;
+  if (mine && e.live && (B == kAny || e.B == B) && (Lp == kAny || e.Lp == Lp) && (!prompt_kv || (h->pkv.valid && h->pkv.B == e.B && h->pkv.Lp == e.Lp)))
+    return 0;
+  return fail(std::string(fn) + ": no running episode batch" + which + " (start one with " + (seq ? "vima_seq_prefill)" : "vima_decode_step(step = 0))"));
+}
+
+// A history longer than the room (EpisodeBook::history): code 34, nothing has changed. lead: "<entry>: a history of T steps" / "<entry>: snapshot i
+// holds n steps and"
+static int room_refused(const std::string& lead, int room) {
+  return fail(lead + " does not fit: room for " + std::to_string(room) + " (the batch steps whose cache rows are all still there)", 34);
+}
+
 // The episode caches for B samples of Lmax rows: per-layer self-attention K | V [layer][B][Lmax][2E], key mask [B][Lmax], position counter and
 // restart flag [B]. Grown (never shrunk) on demand; a reallocation invalidates the captured graphs.
 static int ep_reserve(VimaHandle* h, int B, int Lmax) {
   const size_t need = (size_t)h->cfg.xf_n_layers * B * Lmax * 2 * h->cfg.embed_dim * h->esz();
-  if (h->ep_kv_bytes >= need && h->ep_aux_cap >= (size_t)B * Lmax) return 0;
+  if (h->ep.kv_bytes >= need && h->ep.aux_cap >= (size_t)B * Lmax) return 0;
   HIPCK(hipDeviceSynchronize());
-  if (h->ep_kv) (void)hipFree(h->ep_kv);
-  if (h->ep_mask) (void)hipFree(h->ep_mask);
-  if (h->ep_poscnt) (void)hipFree(h->ep_poscnt);
-  if (h->ep_fresh) (void)hipFree(h->ep_fresh);
-  h->ep_kv = nullptr; h->ep_mask = nullptr; h->ep_poscnt = nullptr; h->ep_fresh = nullptr; h->ep_kv_bytes = 0; h->ep_aux_cap = 0;
-  HIPCK(hipMalloc(&h->ep_kv, need));
-  HIPCK(hipMalloc((void**)&h->ep_mask, (size_t)B * Lmax));
-  HIPCK(hipMalloc((void**)&h->ep_poscnt, (size_t)B * sizeof(int)));
-  HIPCK(hipMalloc((void**)&h->ep_fresh, (size_t)B));
-  h->ep_kv_bytes = need; h->ep_aux_cap = (size_t)B * Lmax;
+  if (h->ep.kv) (void)hipFree(h->ep.kv);
+  if (h->ep.mask) (void)hipFree(h->ep.mask);
+  if (h->ep.poscnt) (void)hipFree(h->ep.poscnt);
+  if (h->ep.fresh) (void)hipFree(h->ep.fresh);
+  h->ep.kv = nullptr; h->ep.mask = nullptr; h->ep.poscnt = nullptr; h->ep.fresh = nullptr; h->ep.kv_bytes = 0; h->ep.aux_cap = 0;
+  HIPCK(hipMalloc(&h->ep.kv, need));
+  HIPCK(hipMalloc((void**)&h->ep.mask, (size_t)B * Lmax));
+  HIPCK(hipMalloc((void**)&h->ep.poscnt, (size_t)B * sizeof(int)));
+  HIPCK(hipMalloc((void**)&h->ep.fresh, (size_t)B));
+  h->ep.kv_bytes = need; h->ep.aux_cap = (size_t)B * Lmax;
   ++h->state_gen;
   return 0;
 }
@@ -2037,44 +2085,44 @@ static int decode_prepare(VimaHandle* h, const float* act_tok, int T, int B, int
   if (inc) {
     if (has_act && !act_tok) return fail("vima_decode_step: the previous action token is required for step > 0");
     if (chunk && !act_tok) return fail("vima_decode_chunk: the action tokens between the chunk's steps are required");
-    if (step > 0 && !(h->ep_step == step - 1 && h->ep_B == B && h->ep_Q == Q && h->ep_Lp == Lp && h->kv_valid))
+    if (step > 0 && !(h->ep.live && h->ep.book.next == step && h->ep.B == B && h->ep.Q == Q && h->ep.Lp == Lp && h->pkv.valid))
       return fail(std::string(fn) + ": step " + std::to_string(step) + " does not continue the episode state (last step " +
-                  std::to_string(h->ep_step) + "); start an episode with step 0");
+                  std::to_string(h->ep.live ? h->ep.book.next - 1 : -1) + "); start an episode with step 0");
     kv_cache_mode = step == 0 ? 1 : 2;
     if (step == 0) {   // a new episode batch: the one that ran ends here
       if (int e = ep_reserve(h, B, Lmax)) return e;
-      h->ep_step = -1; h->ep_B = B; h->ep_Lmax = Lmax;   // the caches' shape (ep_layer); the episode itself is valid from decode_commit on
-      h->book.begin(B, Q, 0, Lmax, ring);
+      h->ep.live = false; h->ep.B = B; h->ep.Lmax = Lmax;   // the caches' shape (ep_layer); the episode itself is live from decode_commit on
+      h->ep.book.begin(B, Q, 0, Lmax, ring);
     }
-    u = h->book.plan(T);   // the book is at `step` (the continuity check above): a chunk is ONE unit of Lq rows
-    if (u.refused) return plan_refused(fn, "vima_decode_restart", h->book, u, T);
+    u = h->ep.book.plan(T);   // the book is at `step` (the continuity check above): a chunk is ONE unit of Lq rows
+    if (u.refused) return plan_refused(fn, "vima_decode_restart", h->ep.book, u, T);
   }
   if (kv_cache_mode < 0 || kv_cache_mode > 2) return fail("vima_decode: kv_cache_mode must be 0, 1 or 2");
-  if (kv_cache_mode == 2 && !(h->kv_valid && h->kv_B == B && h->kv_Lp == Lp))
+  if (kv_cache_mode == 2 && !(h->pkv.valid && h->pkv.B == B && h->pkv.Lp == Lp))
     return fail("vima_decode: kv_cache_mode 2 without a matching cache (build it with mode 1 for the same B, Lp)");
   if (kv_cache_mode == 1) {
     const size_t need = (size_t)B * Lp * 2 * E * h->esz() * h->cfg.xf_n_layers;
-    h->kv_valid = false;
-    if (h->kv_cache_bytes < need) {
+    h->pkv.valid = false;
+    if (h->pkv.bytes < need) {
       HIPCK(hipDeviceSynchronize());
-      if (h->kv_cache) (void)hipFree(h->kv_cache);
-      h->kv_cache = nullptr; h->kv_cache_bytes = 0;
-      HIPCK(hipMalloc(&h->kv_cache, need));
-      h->kv_cache_bytes = need;
+      if (h->pkv.ptr) (void)hipFree(h->pkv.ptr);
+      h->pkv.ptr = nullptr; h->pkv.bytes = 0;
+      HIPCK(hipMalloc(&h->pkv.ptr, need));
+      h->pkv.bytes = need;
       ++h->state_gen;
     }
   }
-  if (!inc) h->ep_step = -1;   // a full-history call may rebuild the prompt cache: the episode state no longer matches
+  if (!inc) h->ep.live = false;   // a full-history call may rebuild the prompt cache: the episode state no longer matches
   P = DecodePlan{inc, has_act, kv_cache_mode, u};
   return 0;
 }
 
 // T: how many env steps the call took (vima_decode_chunk)
 static void decode_commit(VimaHandle* h, const DecodePlan& P, int B, int Q, int Lp, int T = 1) {
-  if (P.kv_mode == 1) { h->kv_valid = true; h->kv_B = B; h->kv_Lp = Lp; }
+  if (P.kv_mode == 1) { h->pkv.valid = true; h->pkv.B = B; h->pkv.Lp = Lp; }
   if (P.inc) {
-    h->book.commit(P.u, T);
-    h->ep_step = h->book.next - 1; h->ep_B = B; h->ep_Q = Q; h->ep_Lp = Lp; h->ep_Lmax = h->book.Lmax;
+    h->ep.book.commit(P.u, T);
+    h->ep.live = true; h->ep.B = B; h->ep.Q = Q; h->ep.Lp = Lp; h->ep.Lmax = h->ep.book.Lmax;
   }
 }
 
@@ -2089,8 +2137,8 @@ static int decode_launch(VimaHandle* h, const float* obs_tok, const uint8_t* obs
   const bool inc = P.inc;
   const int has_act = P.has_act, L_hist = P.u.row, Lq = P.u.Lq, Lmax = h->cfg.n_positions, kv_cache_mode = P.kv_mode;
   if (inc && !has_act) {   // step 0
-    HIPCK(hipMemsetAsync(h->ep_poscnt, 0, (size_t)B * sizeof(int), stream));
-    HIPCK(hipMemsetAsync(h->ep_fresh, 0, (size_t)B, stream));
+    HIPCK(hipMemsetAsync(h->ep.poscnt, 0, (size_t)B * sizeof(int), stream));
+    HIPCK(hipMemsetAsync(h->ep.fresh, 0, (size_t)B, stream));
   }
   Run R{h, (hipStream_t)stream};
   const int rq = B * Lq, rp = B * Lp;
@@ -2111,7 +2159,7 @@ static int decode_launch(VimaHandle* h, const float* obs_tok, const uint8_t* obs
   const bool dual = h->dual_stream != 0 && build_kv;
   std::vector<void*> KVs(NL);
   if (use_cache) {
-    for (int i = 0; i < NL; ++i) KVs[i] = reinterpret_cast<char*>(h->kv_cache) + kv_layer_bytes * i;
+    for (int i = 0; i < NL; ++i) KVs[i] = reinterpret_cast<char*>(h->pkv.ptr) + kv_layer_bytes * i;
   } else {
     for (int i = 0; i < (dual ? NL : 1); ++i) KVs[i] = R.wsT((size_t)rp * 2 * E);
     if (!dual) for (int i = 1; i < NL; ++i) KVs[i] = KVs[0];
@@ -2140,14 +2188,13 @@ static int decode_launch(VimaHandle* h, const float* obs_tok, const uint8_t* obs
   if (R.err) return R.err;
   if (hist) {
     if ((int)h->restart_list.size() != B || (int)h->hist_rowmap.size() != Lq) return fail("vima_decode_restart_history: internal row map mismatch");
-    HIPCK(hipMemcpyAsync(hlist, h->restart_list.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, R.st));
-    HIPCK(hipMemcpyAsync(hmap, h->hist_rowmap.data(), (size_t)Lq * sizeof(int), hipMemcpyHostToDevice, R.st));
+    if (R.upload(hlist, h->restart_list) || R.upload(hmap, h->hist_rowmap)) return R.err;
     OTHER(R, launch_mask_rows_gather(prompt_mask, hpmask, hlist, B, Lp, R.st), "mask_rows_gather");
     prompt_mask = hpmask;
   }
   if (inc)   // T env steps (a step is a chunk of one): Lq = T (Q + 1) [- 1 at step 0] rows per sample at row L_hist
-    OTHER(R, launch_dec_embed_chunk(obs_tok, obs_mask, act_tok, h->pos_emb, h->cfg.n_positions, x32, xT, h->ep_mask, h->ep_poscnt,
-                                    L_hist, Lmax, T, B, Q, has_act, E, h->bf16, R.st, h->ep_fresh), "dec_embed_chunk");
+    OTHER(R, launch_dec_embed_chunk(obs_tok, obs_mask, act_tok, h->pos_emb, h->cfg.n_positions, x32, xT, h->ep.mask, h->ep.poscnt,
+                                    L_hist, Lmax, T, B, Q, has_act, E, h->bf16, R.st, h->ep.fresh), "dec_embed_chunk");
   else
     OTHER(R, launch_dec_embed(obs_tok, obs_mask, act_tok, h->pos_emb, h->cfg.n_positions, x32, xT, dmask, T, B, Q, L_act, E,
                               h->bf16, R.st), "dec_embed");
@@ -2175,14 +2222,14 @@ static int decode_launch(VimaHandle* h, const float* obs_tok, const uint8_t* obs
   // Layout of the per-layer prompt K / V: head-major [B][2 Hx][Lp][Dx] when the projection runs on the persistent 256x256 kernels (whose epilogue
   // can write it: GemmArgs::hm_D) -- the split-key cross attention then streams Lp x Dx contiguous elements per (batch, head) instead of 2 Dx-byte
   // slices of 4 E-byte rows (round 3 measured 86 against 104 us per layer at the benchmark shape); row-major [B * Lp][2E] otherwise. A cache keeps
-  // the layout it was built with (h->kv_hm); the values are the same, so is every result.
+  // the layout it was built with (h->pkv.hm); the values are the same, so is every result.
   const int Dx = E / Hx;
   bool hm = false;
   if (build_kv)
     hm = h->kv_headmajor && h->bf16 && gemm_headmajor_ok(&h->tune, rp, 2 * E, E, E, E, Dx, Lp, p8 != nullptr ? 1 : 0) != 0;
   else
-    hm = hist ? false : h->kv_hm;   // hist: gathered below, row-major
-  if (use_cache && build_kv) h->kv_hm = hm;
+    hm = hist ? false : h->pkv.hm;   // hist: gathered below, row-major
+  if (use_cache && build_kv) h->pkv.hm = hm;
   auto kv_proj = [&](Run& Rr, int i, void* KV) {
     GemmArgs g = Rr.linear_args(Opnd{pT, E, p8, p8 ? kv_scale : 0.f}, h->dec[i].kv, 0, 2 * E, rp, ACT_NONE, nullptr, Opnd{KV, 2 * E});
     if (hm) { g.hm_D = Dx; g.hm_L = Lp; }
@@ -2213,7 +2260,7 @@ static int decode_launch(VimaHandle* h, const float* obs_tok, const uint8_t* obs
       kv_proj(R, i, KV);
     else if (hist) {     // the flagged samples' blocks of the prompt K / V cache (either layout), which the restart in front of this pass has rebuilt
       KvRowsArgs c;
-      c.in = kv_layer(h, i, Lp); c.out = KV; c.list = hlist; c.n = B; c.L = c.Lc = Lp; c.N = c.ld = 2 * E; c.D = h->kv_hm ? Dx : 0; c.to_cache = false;
+      c.in = kv_layer(h, i, Lp); c.out = KV; c.list = hlist; c.n = B; c.L = c.Lc = Lp; c.N = c.ld = 2 * E; c.D = h->pkv.hm ? Dx : 0; c.to_cache = false;
       OTHER(R, launch_kv_rows(c, (int)h->esz(), R.st), "kv_gather");
     }
     AttnArgs a;
@@ -2278,7 +2325,7 @@ static int decode_launch(VimaHandle* h, const float* obs_tok, const uint8_t* obs
   if (inc) OTHER(R, launch_gather_pred(x32, out, T, B, Q, Lq, E, R.st, has_act), "gather_pred");   // the last obs row of every slot (T = 1: row Lq - 1)
   else if (out) OTHER(R, launch_gather_pred(x32, out, T, B, Q, Lq, E, R.st), "gather_pred");
   if (hist)   // lo = hi = 0: the restart in front of this pass has cleared the samples' mask rows
-    OTHER(R, launch_history_install(dmask, hlist, hmap, B, Lq, 0, 0, Lmax, h->ep_mask, h->ep_poscnt, h->ep_fresh, R.st), "history_install");
+    OTHER(R, launch_history_install(dmask, hlist, hmap, B, Lq, 0, 0, Lmax, h->ep.mask, h->ep.poscnt, h->ep.fresh, R.st), "history_install");
   if (dual && join_aux(R)) return 1;
   return R.err;
 }
@@ -2290,7 +2337,7 @@ int vima_decode(VimaHandle* h, const float* obs_tok, const uint8_t* obs_mask, co
   if (int e = decode_prepare(h, act_tok, T, B, Q, L_act, Lp, kv_cache_mode, -1, P)) return e;
   const std::string key = gkey("decode", {(long long)(uintptr_t)obs_tok, (long long)(uintptr_t)obs_mask, (long long)(uintptr_t)act_tok, T, B, Q,
                                           L_act, (long long)(uintptr_t)prompt, stride_b, stride_l, (long long)(uintptr_t)prompt_mask, Lp,
-                                          P.kv_mode, (long long)(uintptr_t)out, (long long)(uintptr_t)h->kv_cache});
+                                          P.kv_mode, (long long)(uintptr_t)out, (long long)(uintptr_t)h->pkv.ptr});
   const int rc = run_graphed(h, key, (hipStream_t)stream, [&](hipStream_t st) {
     return decode_launch(h, obs_tok, obs_mask, act_tok, T, B, Q, L_act, prompt, stride_b, stride_l, prompt_mask, Lp, P, out, st);
   });
@@ -2298,35 +2345,23 @@ int vima_decode(VimaHandle* h, const float* obs_tok, const uint8_t* obs_mask, co
   return rc;
 }
 
-// T env steps of the running episode batch as ONE pass of the incremental branch: Lq = T (Q + 1) rows per sample (one fewer at batch step 0) at
-// one row offset -- one unit of the ring -- instead of T passes of Q + 1 rows; 1 / T of the launches. vima_decode_step is T = 1, the only form
-// that is graphed. A longer chunk runs eager also with option "graphs": it is a rare call (prefill, resume), and every distinct (T, row, keys
-// read) would be a graph of its own; the step graphs captured before stay valid (they read the episode state from the device and the plan from
-// their key) and are replayed again from the next step on.
+// vima_decode_step (T = 1) and vima_decode_chunk
 static int decode_unit(VimaHandle* h, const float* obs_tok, const uint8_t* obs_mask, const float* act_tok, int step, int T, int B, int Q,
                        const float* prompt, int64_t stride_b, int64_t stride_l, const uint8_t* prompt_mask, int Lp, float* out, hipStream_t stream) {
   DecodePlan P;
   if (int e = decode_prepare(h, act_tok, T, B, Q, 0, Lp, 0, step, P)) return e;
-  auto launch = [&](hipStream_t st) {
-    return decode_launch(h, obs_tok, obs_mask, act_tok, T, B, Q, 0, prompt, stride_b, stride_l, prompt_mask, Lp, P, out, st);
-  };
-  int rc;
-  if (T > 1) {
-    rc = launch(stream);
-  } else {
-    // ring mode: the launch sequence depends on (write pointer, keys read, action slot), not on the step number -- from the second lap on the write
-    // pointers repeat, so the set of captured graphs stays bounded however long the rollout runs
-    const long long kstep = h->book.ring ? -1 - (((long long)P.u.row * (h->book.Lmax + 1) + P.u.Lk) * 2 + P.has_act) : step;
-    const std::string key = gkey("decode_step", {(long long)(uintptr_t)obs_tok, (long long)(uintptr_t)obs_mask, (long long)(uintptr_t)act_tok, kstep,
-                                                 B, Q, (long long)(uintptr_t)prompt, stride_b, stride_l, (long long)(uintptr_t)prompt_mask,
-                                                 Lp, (long long)(uintptr_t)out, (long long)(uintptr_t)h->kv_cache, (long long)(uintptr_t)h->ep_kv});
-    // ... and one eager step with an action slot warms all of them (same shapes, same workspace, same kernels: the attention launcher picks by Lk < 64 / >= 64):
-    // each (write pointer, keys read) is captured when first seen
-    const std::string warm = h->book.ring && P.has_act ? gkey("decode_step_ring", {B, Q, Lp, P.u.Lk >= 64 ? 1 : 0}) : std::string();
-    rc = run_graphed(h, key, stream, launch, warm);
+  const EpisodeBook& bk = h->ep.book;
+  std::string key, warm;
+  if (T == 1) {
+    const long long kstep = bk.ring ? -1 - (((long long)P.u.row * (bk.Lmax + 1) + P.u.Lk) * 2 + P.has_act) : step;
+    key = gkey("decode_step", {(long long)(uintptr_t)obs_tok, (long long)(uintptr_t)obs_mask, (long long)(uintptr_t)act_tok, kstep, B, Q,
+                               (long long)(uintptr_t)prompt, stride_b, stride_l, (long long)(uintptr_t)prompt_mask, Lp, (long long)(uintptr_t)out,
+                               (long long)(uintptr_t)h->pkv.ptr, (long long)(uintptr_t)h->ep.kv});
+    if (bk.ring && P.has_act) warm = gkey("decode_step_ring", {B, Q, Lp, P.u.Lk >= 64 ? 1 : 0});
   }
-  if (!rc) decode_commit(h, P, B, Q, Lp, T);
-  return rc;
+  return episode_unit(h, T, stream, key, warm, [&](hipStream_t st) {
+    return decode_launch(h, obs_tok, obs_mask, act_tok, T, B, Q, 0, prompt, stride_b, stride_l, prompt_mask, Lp, P, out, st);
+  }, [&] { decode_commit(h, P, B, Q, Lp, T); });
 }
 
 int vima_decode_step(VimaHandle* h, const float* obs_tok, const uint8_t* obs_mask, const float* act_tok, int step, int B, int Q,
@@ -2341,6 +2376,27 @@ int vima_decode_chunk(VimaHandle* h, const float* obs_tok, const uint8_t* obs_ma
                       vima_stream_t stream) {
   if (step < 0 || T < 1) return fail("vima_decode_chunk: step must be >= 0 and T >= 1");
   return decode_unit(h, obs_tok, obs_mask, act_tok, step, T, B, Q, prompt, stride_b, stride_l, prompt_mask, Lp, out, (hipStream_t)stream);
+}
+
+// What vima_seq_decode_restart and the two *_restart_history entries share in front of their launches (vima_decode_restart keeps its own
+// prologue, the one text the clock was held against; profiles/episode_entry_time.txt): the null-argument refusal, the running-batch check (family: ep_running) and
+// the flagged samples (restart: HOST array [B]). None flagged: the entry returns 0 with nothing launched and nothing uploaded; an entry that goes
+// on to launch moves the list into h->restart_list, the source of its R.upload and of its closing book.restart / install -- a refused call
+// leaves the handle as it was
+static int restart_begin(const VimaHandle* h, const char* fn, bool seq, bool null_arg, const uint8_t* restart, int B, int Lp, const char* family,
+                         std::vector<int>& flagged) {
+  if (null_arg) return fail(std::string(fn) + ": null argument");
+  if (int e = ep_running(h, fn, seq, B, Lp, !seq, " with this B / Lp", family)) return e;
+  flagged = flagged_list(restart, B);
+  return 0;
+}
+
+// vima_decode_history_room / vima_seq_history_room behind their preambles
+static int history_room(VimaHandle* h, const char* fn, bool seq, int32_t* steps_host, const char* family) {
+  if (!steps_host) return fail(std::string(fn) + ": null argument");
+  if (int e = ep_running(h, fn, seq, kAny, kAny, false, "", family)) return e;
+  *steps_host = h->ep.book.room();
+  return 0;
 }
 
 // Per-sample episode restart inside a running batch of incremental decoding (batched environments whose episodes end at different
@@ -2359,7 +2415,7 @@ int vima_decode_restart(VimaHandle* h, const uint8_t* restart, int B, const floa
                         const uint8_t* prompt_mask, int Lp, vima_stream_t stream) {
   if (int e = check_ready(h)) return e;
   if (!restart || !prompt || !prompt_mask) return fail("vima_decode_restart: null argument");
-  if (!(h->ep_step >= 0 && h->ep_B == B && h->ep_Lp == Lp && h->kv_valid && h->kv_B == B && h->kv_Lp == Lp))
+  if (!(h->ep.live && !ep_seq(h) && h->ep.B == B && h->ep.Lp == Lp && h->pkv.valid && h->pkv.B == B && h->pkv.Lp == Lp))
     return fail("vima_decode_restart: no running episode batch with this B / Lp (start one with vima_decode_step(step = 0))");
   const int E = h->cfg.embed_dim, NL = h->cfg.xf_n_layers;
   Run R{h, (hipStream_t)stream};
@@ -2370,12 +2426,11 @@ int vima_decode_restart(VimaHandle* h, const uint8_t* restart, int B, const floa
   const int n_ws = batched ? n_r : 1;
   int* list = R.ws<int>((size_t)n_r);
   void* pT = R.wsT((size_t)n_ws * Lp * E);
-  void* kvrow = (h->kv_hm || batched) ? R.wsT((size_t)n_ws * Lp * 2 * E) : nullptr;   // row-major K | V before the scatter / the head-major transposition
-  if (R.err) return R.err;
-  HIPCK(hipMemcpyAsync(list, h->restart_list.data(), (size_t)n_r * sizeof(int), hipMemcpyHostToDevice, R.st));
-  OTHER(R, launch_episode_restart(list, n_r, h->ep_mask, h->ep_poscnt, h->ep_fresh, 0, h->ep_Lmax, h->ep_Lmax, R.st), "restart_samples");
+  void* kvrow = (h->pkv.hm || batched) ? R.wsT((size_t)n_ws * Lp * 2 * E) : nullptr;   // row-major K | V before the scatter / the head-major transposition
+  if (R.upload(list, h->restart_list)) return R.err;
+  OTHER(R, launch_episode_restart(list, n_r, h->ep.mask, h->ep.poscnt, h->ep.fresh, 0, h->ep.Lmax, h->ep.Lmax, R.st), "restart_samples");
   KvRowsArgs c;   // row-major K | V rows of kvrow -> the samples' blocks of a layer of the prompt K / V cache, in the cache's layout
-  c.in = kvrow; c.L = c.Lc = Lp; c.N = c.ld = 2 * E; c.D = h->kv_hm ? E / h->cfg.xattn_n_heads : 0;
+  c.in = kvrow; c.L = c.Lc = Lp; c.N = c.ld = 2 * E; c.D = h->pkv.hm ? E / h->cfg.xattn_n_heads : 0;
   if (batched) {
     OTHER(R, launch_prompt_pos(prompt, stride_b, stride_l, prompt_mask, h->xpos_emb, h->cfg.xattn_n_positions, pT, n_r, Lp, E, h->bf16, R.st, list),
           "prompt_pos");
@@ -2391,7 +2446,7 @@ int vima_decode_restart(VimaHandle* h, const uint8_t* restart, int B, const floa
                                h->cfg.xattn_n_positions, pT, 1, Lp, E, h->bf16, R.st), "prompt_pos");
     for (int i = 0; i < NL; ++i) {
       void* KV = R.offT(kv_layer(h, i, Lp), (long long)b * Lp * 2 * E);
-      if (!h->kv_hm) {
+      if (!h->pkv.hm) {
         R.linear(pT, E, h->dec[i].kv, Lp, ACT_NONE, nullptr, 0, nullptr, 0, nullptr, 0, KV, 2 * E);
       } else {   // head-major cache: the sample's block is [2 Hx][Lp][Dx]; Lp rows are too few for the kernel that writes it directly
         R.linear(pT, E, h->dec[i].kv, Lp, ACT_NONE, nullptr, 0, nullptr, 0, nullptr, 0, kvrow, 2 * E);
@@ -2400,17 +2455,13 @@ int vima_decode_restart(VimaHandle* h, const uint8_t* restart, int B, const floa
       }
     }
   }
-  if (!R.err) h->book.restart(h->restart_list);
+  if (!R.err) h->ep.book.restart(h->restart_list);
   return R.err;
 }
 
-int vima_decode_history_room(VimaHandle* h, int32_t* steps_host) {
-  if (!h || !steps_host) return fail("vima_decode_history_room: null argument");
-  if (h->cfg.policy_kind != VIMA_POLICY_VIMA && h->cfg.policy_kind != VIMA_POLICY_FLAMINGO)
-    return fail("vima_decode_history_room: the handle's policy has no XAttnGPT episode caches");
-  if (h->ep_step < 0) return fail("vima_decode_history_room: no running episode batch (start one with vima_decode_step(step = 0))");
-  *steps_host = h->book.room();
-  return 0;
+int vima_decode_history_room(VimaHandle* h, int32_t* steps_host) {   // host only: the device is not touched
+  if (!h) return fail("vima_decode_history_room: null argument");
+  return history_room(h, "vima_decode_history_room", false, steps_host, "the handle's policy has no XAttnGPT episode caches");
 }
 
 // vima_decode_restart with a history: the restart itself (same code, same bits), then the T env steps of history of the n_r flagged samples as ONE
@@ -2422,45 +2473,38 @@ int vima_decode_restart_history(VimaHandle* h, const uint8_t* restart, int B, co
                                 const uint8_t* prompt_mask, int Lp, const float* hist_obs, const uint8_t* hist_mask, const float* hist_act, int T,
                                 float* out, vima_stream_t stream) {
   if (T == 0) return vima_decode_restart(h, restart, B, prompt, stride_b, stride_l, prompt_mask, Lp, stream);
+  const char* fn = "vima_decode_restart_history";
+  std::vector<int> flagged;
   if (!h) return fail("null handle");
   if (T < 0) return fail("vima_decode_restart_history: T must be >= 0");
-  if (!restart || !prompt || !prompt_mask || !hist_obs || !hist_mask || (T > 1 && !hist_act)) return fail("vima_decode_restart_history: null argument");
-  if (h->cfg.policy_kind != VIMA_POLICY_VIMA && h->cfg.policy_kind != VIMA_POLICY_FLAMINGO)
-    return fail("vima_decode_restart_history: the handle's policy has no XAttnGPT episode caches");
-  if (!(h->ep_step >= 0 && h->ep_B == B && h->ep_Lp == Lp && h->kv_valid && h->kv_B == B && h->kv_Lp == Lp))
-    return fail("vima_decode_restart_history: no running episode batch with this B / Lp (start one with vima_decode_step(step = 0))");
-  const int Q = h->ep_Q, Lmax = h->ep_Lmax;
-  const int room = h->book.room();
-  if (T > room)
-    return fail("vima_decode_restart_history: a history of " + std::to_string(T) + " steps does not fit: room for " + std::to_string(room) +
-                " (the batch steps whose cache rows are all still there)", 34);
-  const long long Lh = (long long)T * (Q + 1) - 1;
-  if (Lh > 512 || Lh > Lmax) return fail("vima_decode_restart_history: a history holds at most min(512, n_positions) rows");
-  if (int e = vima_decode_restart(h, restart, B, prompt, stride_b, stride_l, prompt_mask, Lp, stream)) return e;
-  const int n_r = (int)h->restart_list.size();
-  if (n_r == 0) return 0;
+  if (int e = restart_begin(h, fn, false, !restart || !prompt || !prompt_mask || !hist_obs || !hist_mask || (T > 1 && !hist_act), restart, B, Lp,
+                            "the handle's policy has no XAttnGPT episode caches", flagged))
+    return e;
   // history step s sits in the slot of batch step t - T + s: its Q obs rows in the slot's obs rows, a_{s-1} in its action row (s > 0; the first
   // slot's action row stays masked). Compact rows (dec_embed_kernel): [o_0 (Q), a_0, o_1 (Q), a_1, ...]
-  h->hist_rowmap.resize((size_t)Lh);
-  const int age = h->book.history_rows(T, h->hist_rowmap.data());
-  for (int r : h->hist_rowmap)
-    if (r < 0 || r >= Lmax) return fail("vima_decode_restart_history: internal error: history row outside the cache");
+  EpisodeBook::History H = h->ep.book.history(T, false);
+  if (!H.fits) return room_refused(std::string(fn) + ": a history of " + std::to_string(T) + " steps", H.room);
+  const int Q = h->ep.Q, Lmax = h->ep.Lmax;
+  const long long Lh = (long long)T * (Q + 1) - 1;
+  if (Lh > 512 || Lh > Lmax) return fail("vima_decode_restart_history: a history holds at most min(512, n_positions) rows");
+  if (!H.in_range) return fail("vima_decode_restart_history: internal error: history row outside the written cache");
+  if (int e = vima_decode_restart(h, restart, B, prompt, stride_b, stride_l, prompt_mask, Lp, stream)) return e;
+  if (flagged.empty()) return 0;
+  const int n_r = (int)flagged.size();   // (the restart has put the list into h->restart_list)
+  h->hist_rowmap = std::move(H.rows);
   DecodePlan P{false, 0, 0, {}};
   P.u.Lq = (int)Lh;
   const int rc = decode_launch(h, hist_obs, hist_mask, hist_act, T, n_r, Q, T - 1, prompt, stride_b, stride_l, prompt_mask, Lp, P, out,
                                (hipStream_t)stream, true);
-  if (!rc) h->book.install(h->restart_list, age);
+  if (!rc) h->ep.book.install(h->restart_list, H.age);
   return rc;
 }
 
 // Host-only: how many further vima_decode_step / vima_seq_decode_step calls would succeed if sample b alone were never restarted (EpisodeBook::steps_left).
 int vima_decode_steps_left(VimaHandle* h, int B, int32_t* out_host) {
   if (!h || !out_host) return fail("vima_decode_steps_left: null argument");
-  const bool seq = h->cfg.policy_kind == VIMA_POLICY_GPT || h->cfg.policy_kind == VIMA_POLICY_GATO;   // the episode of vima_seq_prefill / vima_seq_decode_step
-  if (!((seq ? h->seq_live : h->ep_step >= 0) && h->ep_B == B))
-    return fail(std::string("vima_decode_steps_left: no running episode batch of this size (start one with ") +
-                (seq ? "vima_seq_prefill)" : "vima_decode_step(step = 0))"));
-  for (int b = 0; b < B; ++b) out_host[b] = h->book.steps_left(b);
+  if (int e = ep_running(h, "vima_decode_steps_left", ep_seq(h), B, kAny, false, " of this size")) return e;   // either family's episode
+  for (int b = 0; b < B; ++b) out_host[b] = h->ep.book.steps_left(b);
   return 0;
 }
 
@@ -2580,20 +2624,20 @@ int vima_seq_prefill(VimaHandle* h, const float* prompt, int64_t stride_b, int64
   const int E = h->cfg.embed_dim, Lmax = h->cfg.n_positions, L = Lp + 1;
   if (L > Lmax)
     return fail("vima_seq_prefill: prompt of " + std::to_string(Lp) + " tokens + separator exceeds n_positions " + std::to_string(Lmax), 34);
-  h->seq_live = false;   // from here on the caches belong to the new episode
+  h->ep.live = false;   // from here on the caches belong to the new episode
   if (int e = ep_reserve(h, B, Lmax)) return e;
   Run R{h, (hipStream_t)stream};
   float* x32 = R.ws<float>((size_t)B * L * E);
   void* xT = R.wsT((size_t)B * L * E);
   uint8_t* mask = R.ws<uint8_t>((size_t)B * L);
   if (R.err) return R.err;
-  HIPCK(hipMemsetAsync(h->ep_fresh, 0, (size_t)B, R.st));
-  h->ep_B = B; h->ep_Q = rgb_tokens_per_image(h->cfg.policy_kind); h->ep_Lp = Lp; h->ep_Lmax = Lmax;   // (ep_layer reads the caches' shape)
-  OTHER(R, launch_seq_embed(prompt, stride_b, stride_l, prompt_mask, h->sep_token, nullptr, nullptr, h->pos_emb, Lmax, x32, xT, mask, B, L, Lp, h->ep_Q,
-                            E, h->bf16, R.st, nullptr, h->ep_mask, h->ep_poscnt, Lmax), "seq_embed_prefill");
+  HIPCK(hipMemsetAsync(h->ep.fresh, 0, (size_t)B, R.st));
+  h->ep.B = B; h->ep.Q = rgb_tokens_per_image(h->cfg.policy_kind); h->ep.Lp = Lp; h->ep.Lmax = Lmax;   // (ep_layer reads the caches' shape)
+  OTHER(R, launch_seq_embed(prompt, stride_b, stride_l, prompt_mask, h->sep_token, nullptr, nullptr, h->pos_emb, Lmax, x32, xT, mask, B, L, Lp, h->ep.Q,
+                            E, h->bf16, R.st, nullptr, h->ep.mask, h->ep.poscnt, Lmax), "seq_embed_prefill");
   if (hfgpt_stack(R, x32, xT, mask, B, L, true)) return R.err;
-  h->seq_live = true;
-  h->book.begin(B, h->ep_Q, L, Lmax, h->seq_ring != 0);   // the fixed prefix: prompt + separator
+  h->ep.live = true;
+  h->ep.book.begin(B, h->ep.Q, L, Lmax, h->seq_ring != 0);   // the fixed prefix: prompt + separator
   return 0;
 }
 
@@ -2601,12 +2645,12 @@ int vima_seq_prefill(VimaHandle* h, const float* prompt, int64_t stride_b, int64
 static int seq_step_launch(VimaHandle* h, const float* obs_tok, const float* act_tok, int T, int B, int Q, int has_act, const EpisodeBook::Plan& P,
                            float* out, hipStream_t stream) {
   if (int e = check_ready(h)) return e;
-  const int E = h->cfg.embed_dim, Lmax = h->ep_Lmax, Lq = P.Lq;
+  const int E = h->cfg.embed_dim, Lmax = h->ep.Lmax, Lq = P.Lq;
   Run R{h, stream};
   float* x32 = R.ws<float>((size_t)B * Lq * E);
   void* xT = R.wsT((size_t)B * Lq * E);
   if (R.err) return R.err;
-  OTHER(R, launch_seq_embed_chunk(obs_tok, act_tok, h->pos_emb, Lmax, x32, xT, h->ep_mask, h->ep_poscnt, h->ep_fresh, P.row, T, B, Q, has_act, E, h->bf16,
+  OTHER(R, launch_seq_embed_chunk(obs_tok, act_tok, h->pos_emb, Lmax, x32, xT, h->ep.mask, h->ep.poscnt, h->ep.fresh, P.row, T, B, Q, has_act, E, h->bf16,
                                   R.st), "seq_embed_chunk");
   if (hfgpt_step_stack(R, x32, xT, B, Lq, P.row, Lmax, P.Lk, P.win_end)) return R.err;
   OTHER(R, launch_gather_pred(x32, out, T, B, Q, Lq, E, R.st, has_act), "gather_pred");
@@ -2619,40 +2663,30 @@ static int seq_prepare(VimaHandle* h, const char* fn, const float* obs_tok, cons
   if (int e = seq_ready(h, fn)) return e;
   if (!obs_tok || !out) return fail(std::string(fn) + ": null argument");
   if (step < 0 || T < 1 || B <= 0) return fail(std::string(fn) + ": step must be >= 0, T >= 1 and B > 0");
-  if (!(h->seq_live && h->book.next == step && h->ep_B == B))
+  if (!(h->ep.live && h->ep.book.next == step && h->ep.B == B))
     return fail(std::string(fn) + ": step " + std::to_string(step) + " of " + std::to_string(B) + " samples does not continue the episode state (" +
-                (h->seq_live ? "next step " + std::to_string(h->book.next) + " of " + std::to_string(h->ep_B) + " samples" : std::string("no episode")) +
+                (h->ep.live ? "next step " + std::to_string(h->ep.book.next) + " of " + std::to_string(h->ep.B) + " samples" : std::string("no episode")) +
                 "); start an episode with vima_seq_prefill");
   if ((step > 0 || T > 1) && !act_tok)
     return fail(std::string(fn) + ": the action tokens are required (the previous action for step > 0, those between a chunk's steps)");
-  P = h->book.plan(T);
-  return P.refused ? plan_refused(fn, "vima_seq_decode_restart", h->book, P, T) : 0;
+  P = h->ep.book.plan(T);
+  return P.refused ? plan_refused(fn, "vima_seq_decode_restart", h->ep.book, P, T) : 0;
 }
 
-// T env steps of the running episode batch as ONE pass of hfgpt_step_stack: Lq = T (Q + 1) rows per sample (one fewer at batch step 0) at one row
-// offset -- one unit of the ring -- instead of T passes of Q + 1 rows; 1 / T of the launches. vima_seq_decode_step is T = 1, the only form that is
-// graphed. A longer chunk runs eager also with option "graphs" (a rare call: prefill, resume; every (T, row, keys read) would be a graph of its
-// own); the step graphs captured before stay valid -- they read the episode state from the device and their plan from the key.
+// vima_seq_decode_step (T = 1) and vima_seq_decode_chunk
 static int seq_unit(VimaHandle* h, const char* fn, const float* obs_tok, const float* act_tok, int step, int T, int B, float* out, hipStream_t stream) {
   EpisodeBook::Plan P;
   if (int e = seq_prepare(h, fn, obs_tok, act_tok, step, T, B, out, P)) return e;
-  const int has_act = step > 0 ? 1 : 0, Q = h->ep_Q;
-  auto launch = [&](hipStream_t st) { return seq_step_launch(h, obs_tok, has_act || T > 1 ? act_tok : nullptr, T, B, Q, has_act, P, out, st); };
-  int rc;
-  if (T > 1) {
-    rc = launch(stream);
-  } else {
-    // ring mode: the launch sequence depends on (write pointer, keys read, action slot), not on the step number -- from the second lap on every step
-    // has Q + 1 rows and the write pointers repeat, so the set of captured graphs stays bounded however long the rollout runs ...
-    const std::string key = gkey("seq_step", {(long long)(uintptr_t)obs_tok, (long long)(uintptr_t)act_tok, (long long)(uintptr_t)out, B, P.row, has_act,
-                                              (long long)(uintptr_t)h->ep_kv, P.Lk, P.win_end});
-    // ... and one eager step with an action slot warms all of them (same shapes, same workspace, same kernels: the attention launcher picks by Lk < 64 / >= 64):
-    // each (write pointer, keys read) is captured when first seen
-    const std::string warm = h->book.ring && has_act ? gkey("seq_step_ring", {B, P.Lk >= 64 ? 1 : 0}) : std::string();
-    rc = run_graphed(h, key, stream, launch, warm);
+  const int has_act = step > 0 ? 1 : 0, Q = h->ep.Q;
+  std::string key, warm;
+  if (T == 1) {
+    key = gkey("seq_step", {(long long)(uintptr_t)obs_tok, (long long)(uintptr_t)act_tok, (long long)(uintptr_t)out, B, P.row, has_act,
+                            (long long)(uintptr_t)h->ep.kv, P.Lk, P.win_end});
+    if (h->ep.book.ring && has_act) warm = gkey("seq_step_ring", {B, P.Lk >= 64 ? 1 : 0});
   }
-  if (!rc) h->book.commit(P, T);
-  return rc;
+  return episode_unit(h, T, stream, key, warm, [&](hipStream_t st) {
+    return seq_step_launch(h, obs_tok, has_act || T > 1 ? act_tok : nullptr, T, B, Q, has_act, P, out, st);
+  }, [&] { h->ep.book.commit(P, T); });
 }
 
 int vima_seq_decode_step(VimaHandle* h, const float* obs_tok, const float* act_tok, int step, int B, float* out, vima_stream_t stream) {
@@ -2667,36 +2701,30 @@ int vima_seq_decode_chunk(VimaHandle* h, const float* obs_tok, const float* act_
 // scatters by the sample list -- 2 + launches of one stack pass, whatever the number of flagged samples.
 int vima_seq_decode_restart(VimaHandle* h, const uint8_t* restart, int B, const float* prompt, int64_t stride_b, int64_t stride_l,
                             const uint8_t* prompt_mask, int Lp, vima_stream_t stream) {
+  std::vector<int> flagged;
   if (int e = seq_ready(h, "vima_seq_decode_restart")) return e;
-  if (!restart || !prompt || !prompt_mask) return fail("vima_seq_decode_restart: null argument");
-  if (!(h->seq_live && h->ep_B == B && h->ep_Lp == Lp))
-    return fail("vima_seq_decode_restart: no running episode batch with this B / Lp (start one with vima_seq_prefill)");
-  const int E = h->cfg.embed_dim, Lmax = h->ep_Lmax, L = Lp + 1;
-  h->restart_list = flagged_list(restart, B);
-  const int n_r = (int)h->restart_list.size();
-  if (n_r == 0) return 0;
+  if (int e = restart_begin(h, "vima_seq_decode_restart", true, !restart || !prompt || !prompt_mask, restart, B, Lp, nullptr, flagged)) return e;
+  if (flagged.empty()) return 0;
+  h->restart_list = std::move(flagged);
+  const int E = h->cfg.embed_dim, Lmax = h->ep.Lmax, L = Lp + 1, n_r = (int)h->restart_list.size();
   Run R{h, (hipStream_t)stream};
   int* list = R.ws<int>((size_t)n_r);
   float* x32 = R.ws<float>((size_t)n_r * L * E);
   void* xT = R.wsT((size_t)n_r * L * E);
   uint8_t* mask = R.ws<uint8_t>((size_t)n_r * L);
-  if (R.err) return R.err;
-  HIPCK(hipMemcpyAsync(list, h->restart_list.data(), (size_t)n_r * sizeof(int), hipMemcpyHostToDevice, R.st));
+  if (R.upload(list, h->restart_list)) return R.err;
   // ring mode: the sample's history may lie anywhere in the written part [P0, hw) of the ring
-  OTHER(R, launch_episode_restart(list, n_r, h->ep_mask, nullptr, h->ep_fresh, L, h->book.written_end(), Lmax, R.st), "seq_restart");
-  OTHER(R, launch_seq_embed(prompt, stride_b, stride_l, prompt_mask, h->sep_token, nullptr, nullptr, h->pos_emb, Lmax, x32, xT, mask, n_r, L, Lp, h->ep_Q,
-                            E, h->bf16, R.st, list, h->ep_mask, h->ep_poscnt, Lmax), "seq_embed_prefill");
+  OTHER(R, launch_episode_restart(list, n_r, h->ep.mask, nullptr, h->ep.fresh, L, h->ep.book.written_end(), Lmax, R.st), "seq_restart");
+  OTHER(R, launch_seq_embed(prompt, stride_b, stride_l, prompt_mask, h->sep_token, nullptr, nullptr, h->pos_emb, Lmax, x32, xT, mask, n_r, L, Lp, h->ep.Q,
+                            E, h->bf16, R.st, list, h->ep.mask, h->ep.poscnt, Lmax), "seq_embed_prefill");
   hfgpt_stack(R, x32, xT, mask, n_r, L, true, list);
-  if (!R.err) h->book.restart(h->restart_list);
+  if (!R.err) h->ep.book.restart(h->restart_list);
   return R.err;
 }
 
 int vima_seq_history_room(VimaHandle* h, int32_t* steps_host) {
   if (int e = seq_ready(h, "vima_seq_history_room")) return e;
-  if (!steps_host) return fail("vima_seq_history_room: null argument");
-  if (!h->seq_live) return fail("vima_seq_history_room: no running episode batch (start one with vima_seq_prefill)");
-  *steps_host = h->book.room();
-  return 0;
+  return history_room(h, "vima_seq_history_room", true, steps_host, nullptr);
 }
 
 // vima_seq_decode_restart with a history: ONE full pass of the vima_seq_decode form over the n_r flagged samples, [prompt | sep | o_0, a_0, .., o_{T-1}],
@@ -2711,46 +2739,35 @@ int vima_seq_decode_restart_history(VimaHandle* h, const uint8_t* restart, int B
   const char* fn = "vima_seq_decode_restart_history";
   if (int e = seq_ready(h, fn)) return e;
   if (T < 0) return fail("vima_seq_decode_restart_history: T must be >= 0");
-  if (!restart || !prompt || !prompt_mask || !hist_obs || (T > 1 && !hist_act)) return fail("vima_seq_decode_restart_history: null argument");
-  if (!(h->seq_live && h->ep_B == B && h->ep_Lp == Lp))
-    return fail("vima_seq_decode_restart_history: no running episode batch with this B / Lp (start one with vima_seq_prefill)");
-  const int E = h->cfg.embed_dim, Q = h->ep_Q, Lmax = h->ep_Lmax, P0 = Lp + 1;
-  const int room = h->book.room();
-  if (T > room)
-    return fail("vima_seq_decode_restart_history: a history of " + std::to_string(T) + " steps does not fit: room for " + std::to_string(room) +
-                " (the batch steps whose cache rows are all still there)", 34);
+  std::vector<int> flagged;
+  if (int e = restart_begin(h, fn, true, !restart || !prompt || !prompt_mask || !hist_obs || (T > 1 && !hist_act), restart, B, Lp, nullptr, flagged)) return e;
+  const int E = h->cfg.embed_dim, Q = h->ep.Q, Lmax = h->ep.Lmax, P0 = Lp + 1;
+  // compact row l of the sequence -> cache row: the identity over the prefix; history step s sits in the slot of batch step t - T + s, its Q obs rows
+  // in the slot's obs rows and a_s in the action row of the NEXT slot (the first slot's own action row, if it has one, stays masked)
+  EpisodeBook::History H = h->ep.book.history(T, true);
+  if (!H.fits) return room_refused(std::string(fn) + ": a history of " + std::to_string(T) + " steps", H.room);
   const long long L64 = (long long)Lp + (long long)T * (Q + 1);
   if (L64 > h->cfg.n_positions)
     return fail("vima_seq_decode_restart_history: sequence of " + std::to_string(L64) + " tokens (prompt, separator and " + std::to_string(T) +
                 " steps) exceeds n_positions " + std::to_string(h->cfg.n_positions), 34);
-  const int L = (int)L64;
-  const std::vector<int> flagged = flagged_list(restart, B);
-  const int n_r = (int)flagged.size();
+  const int L = (int)L64, hi = h->ep.book.written_end(), n_r = (int)flagged.size();
   if (n_r == 0) return 0;
-  // compact row l of the sequence -> cache row: the identity over the prefix; history step s sits in the slot of batch step t - T + s, its Q obs rows
-  // in the slot's obs rows and a_s in the action row of the NEXT slot (the first slot's own action row, if it has one, stays masked)
-  std::vector<int> rowmap((size_t)L);
-  for (int l = 0; l <= Lp; ++l) rowmap[(size_t)l] = l;
-  const int age = h->book.history_rows(T, rowmap.data() + P0), hi = h->book.written_end();
-  for (int l = P0; l < L; ++l)
-    if (rowmap[(size_t)l] < P0 || rowmap[(size_t)l] >= hi) return fail("vima_seq_decode_restart_history: internal error: history row outside the written cache");
-  h->restart_list = flagged;
-  h->hist_rowmap = rowmap;
+  if (!H.in_range || (int)H.rows.size() != L) return fail("vima_seq_decode_restart_history: internal error: history row outside the written cache");
+  h->restart_list = std::move(flagged);
+  h->hist_rowmap = std::move(H.rows);
   Run R{h, (hipStream_t)stream};
   int* list = R.ws<int>((size_t)n_r);
   int* hmap = R.ws<int>((size_t)L);
   float* x32 = R.ws<float>((size_t)n_r * L * E);
   void* xT = R.wsT((size_t)n_r * L * E);
   uint8_t* mask = R.ws<uint8_t>((size_t)n_r * L);
-  if (R.err) return R.err;
-  HIPCK(hipMemcpyAsync(list, h->restart_list.data(), (size_t)n_r * sizeof(int), hipMemcpyHostToDevice, R.st));
-  HIPCK(hipMemcpyAsync(hmap, h->hist_rowmap.data(), (size_t)L * sizeof(int), hipMemcpyHostToDevice, R.st));
+  if (R.upload(list, h->restart_list) || R.upload(hmap, h->hist_rowmap)) return R.err;
   OTHER(R, launch_seq_embed(prompt, stride_b, stride_l, prompt_mask, h->sep_token, hist_obs, hist_act, h->pos_emb, h->cfg.n_positions, x32, xT, mask,
                             n_r, L, Lp, Q, E, h->bf16, R.st, list), "seq_embed");
   if (hfgpt_stack(R, x32, xT, mask, n_r, L, true, list, hmap)) return R.err;
   if (out) OTHER(R, launch_gather_pred(x32 + (size_t)P0 * E, out, T, n_r, Q, L, E, R.st), "gather_pred");   // teacher-forced: the last obs row of every history step
-  OTHER(R, launch_history_install(mask, list, hmap, n_r, L, P0, hi, Lmax, h->ep_mask, h->ep_poscnt, h->ep_fresh, R.st), "seq_history_install");
-  if (!R.err) h->book.install(h->restart_list, age);
+  OTHER(R, launch_history_install(mask, list, hmap, n_r, L, P0, hi, Lmax, h->ep.mask, h->ep.poscnt, h->ep.fresh, R.st), "seq_history_install");
+  if (!R.err) h->ep.book.install(h->restart_list, H.age);
   return R.err;
 }
 
@@ -3501,8 +3518,7 @@ static int fork_launch(Run& R, const ForkTable& T, const std::vector<int>& dsts,
   std::copy(dsts.begin(), dsts.end(), tab.begin() + (nj0 + nj1) * ji);
   std::copy(srcs.begin(), srcs.end(), tab.begin() + (nj0 + nj1) * ji + np);
   int* dev = R.ws<int>(tab.size());
-  if (R.err) return R.err;
-  HIPCK(hipMemcpyAsync(dev, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, R.st));
+  if (R.upload(dev, tab)) return R.err;
   const int* ddst = dev + (nj0 + nj1) * ji;
   for (int c = 0; c < 2; ++c) {
     if (T.jobs[c].empty()) continue;
@@ -3515,13 +3531,12 @@ static int fork_launch(Run& R, const ForkTable& T, const std::vector<int>& dsts,
   return R.err;
 }
 
-// vima_decode_fork / vima_seq_decode_fork behind their policy checks
-static int fork_episode(VimaHandle* h, const char* fn, bool seq, const int32_t* source, int B, hipStream_t st) {
-  if (!source) return fail(std::string(fn) + ": null argument");
-  if (seq ? !(h->seq_live && h->ep_B == B) : !(h->ep_step >= 0 && h->ep_B == B && h->kv_valid && h->kv_B == B))
-    return fail(std::string(fn) + ": no running episode batch with this B (start one with " + (seq ? "vima_seq_prefill)" : "vima_decode_step(step = 0))"));
+// vima_decode_fork / vima_seq_decode_fork behind check_ready; family: the entry's refusal of a handle of the other family, which comes first
+static int fork_episode(VimaHandle* h, const char* fn, bool seq, const int32_t* source, int B, hipStream_t st, const char* family) {
+  if (!source && ep_seq(h) == seq) return fail(std::string(fn) + ": null argument");
+  if (int e = ep_running(h, fn, seq, B, kAny, !seq, " with this B", family)) return e;
   const std::vector<int> src(source, source + B);
-  if (!h->book.fork_ok(src)) {
+  if (!h->ep.book.fork_ok(src)) {
     for (int b = 0; b < B; ++b) {
       const int s = src[(size_t)b];
       if (s < 0 || s >= B) return fail(std::string(fn) + ": source[" + std::to_string(b) + "] = " + std::to_string(s) + " is not a sample of the batch [0, " + std::to_string(B) + ")", 22);
@@ -3530,7 +3545,7 @@ static int fork_episode(VimaHandle* h, const char* fn, bool seq, const int32_t* 
                     std::to_string(src[(size_t)s]) + "): a source must be its own source, no chains and no swaps", 22);
     }
   }
-  const int E = h->cfg.embed_dim, NL = h->cfg.xf_n_layers, Lmax = h->ep_Lmax, Lp = h->ep_Lp;
+  const int E = h->cfg.embed_dim, NL = h->cfg.xf_n_layers, Lmax = h->ep.Lmax, Lp = h->ep.Lp;
   if (((size_t)2 * E * h->esz()) % 16) return fail(std::string(fn) + ": rows of 2 x embed_dim elements must be a multiple of 16 bytes", 22);
   const long long rv = (long long)2 * E * (long long)h->esz() / 16;
   std::vector<int> dsts, srcs;
@@ -3541,32 +3556,30 @@ static int fork_episode(VimaHandle* h, const char* fn, bool seq, const int32_t* 
       if (src[(size_t)b] == s && b != s) { dsts.push_back(b); srcs.push_back(s); ++g.ndst; }
     if (!g.ndst) continue;
     int rg[2][2];
-    const int nr = h->book.live_ranges(s, rg);
-    if (seq) T.add(0, g, 0, h->book.P0, rv);          // the fixed prefix [prompt | sep]
+    const int nr = h->ep.book.live_ranges(s, rg);
+    if (seq) T.add(0, g, 0, h->ep.book.P0, rv);          // the fixed prefix [prompt | sep]
     for (int i = 0; i < nr; ++i) T.add(0, g, rg[i][0], rg[i][1], rv);
     if (!seq) T.add(1, g, 0, Lp, rv);                 // the sample's block of the prompt K / V cache, either layout
   }
   if (dsts.empty()) return 0;
   Run R{h, st};
-  void* const cache[2] = {h->ep_kv, h->kv_cache};
+  void* const cache[2] = {h->ep.kv, h->pkv.ptr};
   const int L[2] = {Lmax, Lp};
-  if (fork_launch(R, T, dsts, srcs, cache, L, NL, B, 2 * E, h->bf16, h->ep_mask, h->ep_poscnt, h->ep_fresh, Lmax)) return R.err;
-  h->book.fork(src);
+  if (fork_launch(R, T, dsts, srcs, cache, L, NL, B, 2 * E, h->bf16, h->ep.mask, h->ep.poscnt, h->ep.fresh, Lmax)) return R.err;
+  h->ep.book.fork(src);
   return 0;
 }
 
 int vima_decode_fork(VimaHandle* h, const int32_t* source, int B, vima_stream_t stream) {
   if (int e = check_ready(h)) return e;
-  if (h->cfg.policy_kind != VIMA_POLICY_VIMA && h->cfg.policy_kind != VIMA_POLICY_FLAMINGO)
-    return fail("vima_decode_fork: the handle's policy has no XAttnGPT episode caches (GPT / GATO handles fork with vima_seq_decode_fork)");
-  return fork_episode(h, "vima_decode_fork", false, source, B, (hipStream_t)stream);
+  return fork_episode(h, "vima_decode_fork", false, source, B, (hipStream_t)stream,
+                      "the handle's policy has no XAttnGPT episode caches (GPT / GATO handles fork with vima_seq_decode_fork)");
 }
 
 int vima_seq_decode_fork(VimaHandle* h, const int32_t* source, int B, vima_stream_t stream) {
   if (int e = check_ready(h)) return e;
-  if (h->cfg.policy_kind != VIMA_POLICY_GPT && h->cfg.policy_kind != VIMA_POLICY_GATO)
-    return fail("vima_seq_decode_fork: decoder-only policies (GPT / GATO) only; VIMAPolicy / VIMAFlamingoPolicy handles fork with vima_decode_fork");
-  return fork_episode(h, "vima_seq_decode_fork", true, source, B, (hipStream_t)stream);
+  return fork_episode(h, "vima_seq_decode_fork", true, source, B, (hipStream_t)stream,
+                      "decoder-only policies (GPT / GATO) only; VIMAPolicy / VIMAFlamingoPolicy handles fork with vima_decode_fork");
 }
 
 int vima_op_episode_fork(VimaHandle* h, void* cache, int elem_bytes, int NL, int B, int L, int N, const int32_t* group_src, const int32_t* group_ptr,
@@ -3675,8 +3688,7 @@ static int snap_launch(Run& R, const SnapTable& T, bool pack, const SnapCache c[
   if (ns) memcpy(tab.data() + os, T.state.data(), ns * sizeof(SnapStateJob));
   if (nm) memcpy(tab.data() + om, T.map.data(), nm * sizeof(int));
   long long* dev = R.ws<long long>(words);
-  if (R.err) return R.err;
-  HIPCK(hipMemcpyAsync(dev, tab.data(), words * sizeof(long long), hipMemcpyHostToDevice, R.st));
+  if (R.upload(dev, tab)) return R.err;
   const int* dmap = reinterpret_cast<const int*>(dev + om);
   const int rpc = snap_rows_per_unit((long long)N * (is_bf16 ? 2 : 4) / 16);
   for (int i = 0; i < 2; ++i) {
@@ -3697,26 +3709,19 @@ static int snap_launch(Run& R, const SnapTable& T, bool pack, const SnapCache c[
 
 // the policy and running-batch checks of the six entry points
 static int snap_ready(VimaHandle* h, const std::string& fn, bool seq) {
-  if (seq) {
-    if (int e = seq_ready(h, fn.c_str())) return e;
-    if (!h->seq_live) return fail(fn + ": no running episode batch (start one with vima_seq_prefill)");
-  } else {
-    if (int e = check_ready(h)) return e;
-    if (h->cfg.policy_kind != VIMA_POLICY_VIMA && h->cfg.policy_kind != VIMA_POLICY_FLAMINGO)
-      return fail(fn + ": the handle's policy has no XAttnGPT episode caches (GPT / GATO handles use the vima_seq_decode_* form)");
-    if (!(h->ep_step >= 0 && h->kv_valid && h->kv_B == h->ep_B && h->kv_Lp == h->ep_Lp))
-      return fail(fn + ": no running episode batch (start one with vima_decode_step(step = 0))");
-  }
+  if (int e = seq ? seq_ready(h, fn.c_str()) : check_ready(h)) return e;
+  if (int e = ep_running(h, fn.c_str(), seq, kAny, kAny, !seq, "", "the handle's policy has no XAttnGPT episode caches (GPT / GATO handles use the vima_seq_decode_* form)"))
+    return e;
   if (((size_t)2 * h->cfg.embed_dim * h->esz()) % 16) return fail(fn + ": rows of 2 x embed_dim elements must be a multiple of 16 bytes", 22);
-  if (!seq && h->kv_hm && ((size_t)(h->cfg.embed_dim / h->cfg.xattn_n_heads) * h->esz()) % 16)
+  if (!seq && h->pkv.hm && ((size_t)(h->cfg.embed_dim / h->cfg.xattn_n_heads) * h->esz()) % 16)
     return fail(fn + ": head-major prompt K / V pieces must be a multiple of 16 bytes", 22);
   return 0;
 }
 
 static VimaEpisodeSnapshotInfo snap_info(const VimaHandle* h, bool seq, int steps, bool with_prompt) {
   VimaEpisodeSnapshotInfo I{};
-  I.steps = steps; I.Q = h->ep_Q; I.embed_dim = h->cfg.embed_dim; I.layers = h->cfg.xf_n_layers;
-  I.prompt_len = seq ? h->book.P0 : h->ep_Lp; I.elem_bytes = (int)h->esz();
+  I.steps = steps; I.Q = h->ep.Q; I.embed_dim = h->cfg.embed_dim; I.layers = h->cfg.xf_n_layers;
+  I.prompt_len = seq ? h->ep.book.P0 : h->ep.Lp; I.elem_bytes = (int)h->esz();
   I.flags = with_prompt ? VIMA_SNAPSHOT_PROMPT : 0; I.policy_kind = h->cfg.policy_kind;
   I.bytes = snap_layout(I, seq).bytes;
   return I;
@@ -3727,23 +3732,21 @@ static int snap_infos(VimaHandle* h, const std::string& fn, bool seq, const int3
   if (!samples || !infos || n < 0) return fail(fn + ": null argument");
   for (int i = 0; i < n; ++i) {
     const int b = samples[i];
-    if (b < 0 || b >= h->ep_B) return fail(fn + ": sample " + std::to_string(b) + " is not a sample of the batch [0, " + std::to_string(h->ep_B) + ")", 22);
-    const int steps = h->book.steps_of(b);
-    if (steps < 0 || steps > h->book.room())
+    if (b < 0 || b >= h->ep.B) return fail(fn + ": sample " + std::to_string(b) + " is not a sample of the batch [0, " + std::to_string(h->ep.B) + ")", 22);
+    const int steps = h->ep.book.steps_of(b);
+    if (steps < 0 || steps > h->ep.book.room())
       return fail(fn + ": internal error: no run of the last batch steps adds up to the age of sample " + std::to_string(b));
     infos[i] = snap_info(h, seq, steps, with_prompt != 0);
   }
   return 0;
 }
 
-// row table of a call whose longest episode has nmax steps: [identity over the prefix (seq) | history_rows(nmax)]; -> the age history_rows returns
-static int snap_rowmap(VimaHandle* h, const std::string& fn, bool seq, int nmax, std::vector<int>& map) {
-  const int P0 = seq ? h->book.P0 : 0, Rmax = std::max(nmax * (h->ep_Q + 1) - 1, 0);
-  map.resize((size_t)P0 + Rmax);
-  for (int l = 0; l < P0; ++l) map[(size_t)l] = l;
-  if (nmax > 0) h->book.history_rows(nmax, map.data() + P0);
-  for (int l = P0; l < P0 + Rmax; ++l)
-    if (map[(size_t)l] < P0 || map[(size_t)l] >= h->ep_Lmax) return fail(fn + ": internal error: episode row outside the cache");
+// row table of a call whose longest episode has nmax steps (at most the room: snap_infos, snap_restore): [identity over the prefix (seq) |
+// history_rows(nmax)]
+static int snap_rowmap(VimaHandle* h, const std::string& fn, int nmax, std::vector<int>& map) {
+  EpisodeBook::History H = h->ep.book.history(nmax, true);
+  if (!H.fits || !H.in_range) return fail(fn + ": internal error: episode row outside the cache");
+  map = std::move(H.rows);
   return 0;
 }
 
@@ -3765,8 +3768,8 @@ static int snap_take(VimaHandle* h, const std::string& fn, bool seq, const int32
       if (payloads[j] == payloads[i]) return fail(fn + ": payloads " + std::to_string(j) + " and " + std::to_string(i) + " are the same buffer", 22);
   }
   SnapTable T;
-  if (int e = snap_rowmap(h, fn, seq, nmax, T.map)) return e;
-  const int E = h->cfg.embed_dim, NL = h->cfg.xf_n_layers, Lmax = h->ep_Lmax, B = h->ep_B;
+  if (int e = snap_rowmap(h, fn, nmax, T.map)) return e;
+  const int E = h->cfg.embed_dim, NL = h->cfg.xf_n_layers, Lmax = h->ep.Lmax, B = h->ep.B;
   const int rpc = snap_rows_per_unit((long long)2 * E * (long long)h->esz() / 16), total = (int)T.map.size();
   for (int i = 0; i < n; ++i) {
     const SnapLayout s = snap_layout(I[(size_t)i], seq);
@@ -3776,8 +3779,8 @@ static int snap_take(VimaHandle* h, const std::string& fn, bool seq, const int32
     T.state.push_back(SnapStateJob{(long long)(uintptr_t)p, samples[i], total - s.R, s.R, s.npre});
   }
   Run R{h, st};
-  const SnapCache c[2] = {{h->ep_kv, Lmax, 0, true}, {h->kv_cache, h->ep_Lp, h->kv_hm ? E / h->cfg.xattn_n_heads : 0, false}};
-  if (snap_launch(R, T, true, c, NL, B, 2 * E, h->bf16, h->ep_mask, h->ep_poscnt, h->ep_fresh, Lmax, 0, 0)) return R.err;
+  const SnapCache c[2] = {{h->ep.kv, Lmax, 0, true}, {h->pkv.ptr, h->ep.Lp, h->pkv.hm ? E / h->cfg.xattn_n_heads : 0, false}};
+  if (snap_launch(R, T, true, c, NL, B, 2 * E, h->bf16, h->ep.mask, h->ep.poscnt, h->ep.fresh, Lmax, 0, 0)) return R.err;
   for (int i = 0; i < n; ++i) infos[i] = I[(size_t)i];
   return 0;
 }
@@ -3787,7 +3790,8 @@ static int snap_restore(VimaHandle* h, const std::string& fn, bool seq, const in
   if (int e = snap_ready(h, fn, seq)) return e;
   if (!slots || !payloads || !infos || n < 0) return fail(fn + ": null argument");
   if (n == 0) return 0;
-  const int B = h->ep_B, room = h->book.room();
+  const int B = h->ep.B;
+  std::vector<int> ages((size_t)n);
   int nmax = 0;
   for (int i = 0; i < n; ++i) {
     const VimaEpisodeSnapshotInfo& I = infos[i];
@@ -3806,30 +3810,28 @@ static int snap_restore(VimaHandle* h, const std::string& fn, bool seq, const in
     if (I.prompt_len != want.prompt_len)
       return fail(who + " has a prompt of " + std::to_string(I.prompt_len) + " rows, the running batch " + std::to_string(want.prompt_len) + " (Lp)", 22);
     if (I.steps < 0 || (I.flags & ~VIMA_SNAPSHOT_PROMPT) || I.bytes != want.bytes) return fail(who + ": the info is not one this library wrote", 22);
-    if (I.steps > room)
-      return fail(who + " holds " + std::to_string(I.steps) + " steps and does not fit: room for " + std::to_string(room) +
-                  " (the batch steps whose cache rows are all still there)", 34);
+    const EpisodeBook::History H = h->ep.book.history(I.steps, false);
+    if (!H.fits) return room_refused(who + " holds " + std::to_string(I.steps) + " steps and", H.room);
+    ages[(size_t)i] = H.age;
     if (int e = snap_device_ptr(fn, payloads[i], I.bytes, i)) return e;
     nmax = std::max(nmax, I.steps);
   }
   SnapTable T;
-  if (int e = snap_rowmap(h, fn, seq, nmax, T.map)) return e;
-  const int E = h->cfg.embed_dim, NL = h->cfg.xf_n_layers, Lmax = h->ep_Lmax, P0 = seq ? h->book.P0 : 0;
+  if (int e = snap_rowmap(h, fn, nmax, T.map)) return e;
+  const int E = h->cfg.embed_dim, NL = h->cfg.xf_n_layers, Lmax = h->ep.Lmax, P0 = seq ? h->ep.book.P0 : 0;
   const int rpc = snap_rows_per_unit((long long)2 * E * (long long)h->esz() / 16), total = (int)T.map.size();
-  std::vector<int> ages((size_t)n), tmp(T.map.size() + 1);
   for (int i = 0; i < n; ++i) {
     const SnapLayout s = snap_layout(infos[i], seq);
     const char* p = static_cast<const char*>(payloads[i]);
-    ages[(size_t)i] = infos[i].steps > 0 ? h->book.history_rows(infos[i].steps, tmp.data()) : 0;
     T.add(0, p + s.rows, (long long)s.R * s.row_bytes, slots[i], total - s.R, s.R, rpc);
     if (s.has_prompt) T.add(seq ? 0 : 1, p + s.prompt, (long long)infos[i].prompt_len * s.row_bytes, slots[i], 0, infos[i].prompt_len, rpc);
     T.state.push_back(SnapStateJob{(long long)(uintptr_t)p, slots[i], total - s.R, s.R, s.npre});
   }
   Run R{h, st};
-  const SnapCache c[2] = {{h->ep_kv, Lmax, 0, true}, {h->kv_cache, h->ep_Lp, h->kv_hm ? E / h->cfg.xattn_n_heads : 0, false}};
+  const SnapCache c[2] = {{h->ep.kv, Lmax, 0, true}, {h->pkv.ptr, h->ep.Lp, h->pkv.hm ? E / h->cfg.xattn_n_heads : 0, false}};
   // the restart of the slot: its old episode's keys are masked -- everywhere behind the prefix (the ring's written part; rows beyond it are never read)
-  if (snap_launch(R, T, false, c, NL, B, 2 * E, h->bf16, h->ep_mask, h->ep_poscnt, h->ep_fresh, Lmax, P0, seq ? h->book.written_end() : Lmax)) return R.err;
-  for (int i = 0; i < n; ++i) h->book.install(std::vector<int>{slots[i]}, ages[(size_t)i]);
+  if (snap_launch(R, T, false, c, NL, B, 2 * E, h->bf16, h->ep.mask, h->ep.poscnt, h->ep.fresh, Lmax, P0, seq ? h->ep.book.written_end() : Lmax)) return R.err;
+  for (int i = 0; i < n; ++i) h->ep.book.install(std::vector<int>{slots[i]}, ages[(size_t)i]);
   return 0;
 }
 
