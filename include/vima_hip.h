@@ -46,7 +46,9 @@ enum { VIMA_PRECISION_FP32 = 0, VIMA_PRECISION_BF16 = 1, VIMA_PRECISION_FP8W = 2
  *       representative data before comparing or serving; (ii) scale = headroom x max |x| / 448 with option "fp8_headroom_pct" (default 125):
  *       later activations up to 1.25x the calibrating maximum stay representable, larger ones SATURATE at +-448 x scale silently (call
  *       "fp8_recalibrate" when the input distribution changes); (iii) a calibrating batch that holds an inf / NaN activation is refused
- *       (the call fails, nothing is frozen); (iv) vima_decode_restart rebuilds the restarted samples' prompt K/V rows with bf16
+ *       (the call fails, nothing is frozen: max |x| is taken over the magnitude bit patterns, where every NaN orders above inf). A NaN
+ *       AFTER calibration is NOT detected: fmed3(NaN, -448, 448) is -448, so every e4m3 producer turns a NaN activation into the byte
+ *       0xFE (-448) silently (vima_op_fp8_quant; tests/test_fp8_producers_gpu.py pins the byte); (iv) vima_decode_restart rebuilds the restarted samples' prompt K/V rows with bf16
  *       activations (M = Lp rows is below the fp8 kernel's size), i.e. a restarted sample matches a fresh episode to the fp8 tolerance, not
  *       bit for bit. */
 
@@ -545,7 +547,9 @@ int vima_op_linear(VimaHandle* h, const float* A, const float* W, const float* b
  * device buffers; nothing is cast, widened or staged, and the launcher's own validation is the only one: a form or geometry it
  * refuses is returned as an error with no output written. x3 = 1 asks for the split-bf16 products of a BF16X3 handle. The handle's
  * GEMM options apply; *kernel_id (optional) receives the kernel the launcher chose (the ids of vima_prof_read_gemm_kernels).
- * fp8 operands / outputs are not reachable through this entry. */
+ * The GEMM's fp8 operands (GemmArgs::a8 / w8) and its e4m3 output (out8) are not reachable through this entry or any other operator entry:
+ * they are held at model level only (tests/test_fp8_gpu.py). The e4m3 producers OUTSIDE the GEMM epilogue have entries of their own
+ * (vima_op_fp8_quant ... vima_op_vit_attention_cls_fp8 below). */
 typedef struct VimaGemmDesc {
   const void* A; const void* W; const void* A2; const void* W2; const void* mul; const void* resT;
   void* outT; void* outT_lo;
@@ -604,7 +608,8 @@ int vima_op_bbox_l1(VimaHandle* h, const int64_t* bbox, const float* W, const fl
  * vima_op_norm: kind VIMA_NORM_LN launch_layernorm (fp32 rows), VIMA_NORM_LN_T launch_layernorm_T (x cast to the operand type first: x holds
  * rows * ldin elements), VIMA_NORM_LN2 launch_layernorm2 (y = LN(x; gamma, beta, eps) -> out32 / outT, LN(y; gamma2, beta2, eps2) -> out2T),
  * VIMA_NORM_RMS_STATS launch_rms_stats (outT = x, ssq[r] = sum x[r][:]^2; ldin == E). rms = 1: T5 RMSNorm (beta NULL). out32 / outT optional
- * where the launcher makes them so; the fp8 output of the launchers is not reachable here. */
+ * where the launcher makes them so. The e4m3 output of launch_layernorm_T is reached through vima_op_norm_fp8 (below), not through this entry;
+ * no other norm launcher has one. */
 enum { VIMA_NORM_LN = 0, VIMA_NORM_LN_T = 1, VIMA_NORM_LN2 = 2, VIMA_NORM_RMS_STATS = 3 };
 typedef struct VimaNormDesc {
   const float* x; const float* gamma; const float* beta; const float* gamma2; const float* beta2;
@@ -614,6 +619,28 @@ typedef struct VimaNormDesc {
   float eps, eps2;
 } VimaNormDesc;
 int vima_op_norm(VimaHandle* h, const VimaNormDesc* desc, vima_stream_t stream);
+/* The e4m3 producers of precision "fp8" outside the GEMM epilogue and the calibration's max |x|, ONE launcher call each (additive, ABI version
+ * unchanged; tests/test_fp8_producers_gpu.py holds them bit for bit). Every one of them ends in fmed3(v * inv, -448, 448) and cvt_pk_fp8_f32
+ * (round to nearest even) on an fp32 value v: out8 byte = OCP e4m3 code of clamp(v * inv), 0x7E / 0xFE at saturation, +-inf -> +-448, a NaN
+ * -> 0xFE (-448). Conventions of the blocks above: fp32 device buffers in, cast to bf16 internally (exact for bf16-exact values); out8 is the
+ * caller's DEVICE byte buffer and is written by the launcher directly. The launchers emit e4m3 from bf16 operands only: on an FP32 / BF16X3
+ * handle every entry fails with nothing written, as does a NULL required argument, a non-positive size or anything the launcher refuses.
+ * vima_op_fp8_quant: launch_quant_fp8, out8[r, c] = e4m3(x[r, c] * inv) for c < cols; x [rows, ldin], out8 [rows, ldo]; cols, ldin and ldo
+ *   multiples of 8 (else refused); columns >= cols are neither read into the result nor written; rows = 0 succeeds and writes nothing.
+ * vima_op_fp8_amax: launch_amax, *slot = max(*slot, max |x[:, :cols]|) on a DEVICE float that is NOT zeroed here (a non-negative value is the
+ *   caller's to provide); all-zero data leaves it as it was, an inf in the data makes it inf and a NaN makes it a NaN. cols, ldin multiples of 8.
+ * vima_op_norm_fp8: launch_layernorm_T (kind VIMA_NORM_LN_T only) with its e4m3 output: out8 [rows, E] = e4m3(y * inv8) of the fp32 y the
+ *   kernel also stores to desc->out32 (NOT of its bf16 rounding); out32 and outT are optional, out8 alone works.
+ * vima_op_vit_attention_fp8 / _cls_fp8: vima_op_vit_attention / _cls with out8 [M*S, W] / [M, W] = e4m3(out * inv8) of the fp32 head outputs
+ *   written INSTEAD of the operand-type output; impl as there, the kernels bit-identical where more than one applies. */
+int vima_op_fp8_quant(VimaHandle* h, const float* x, int64_t ldin, int64_t rows, int cols, float inv, uint8_t* out8, int64_t ldo,
+                      vima_stream_t stream);
+int vima_op_fp8_amax(VimaHandle* h, const float* x, int64_t ldin, int64_t rows, int cols, float* slot, vima_stream_t stream);
+int vima_op_norm_fp8(VimaHandle* h, const VimaNormDesc* desc, uint8_t* out8, float inv8, vima_stream_t stream);
+int vima_op_vit_attention_fp8(VimaHandle* h, const float* qkv, int M, int S, int W, int heads, int impl, float inv8, uint8_t* out8,
+                              vima_stream_t stream);
+int vima_op_vit_attention_cls_fp8(VimaHandle* h, const float* q, const float* kv, int M, int S, int W, int heads, float inv8, uint8_t* out8,
+                                  vima_stream_t stream);
 /* row r: tok_src[r] >= 0 word_table[word_ids[tok_src[r]]], -1 zeros (mask 0), <= -2 object row -(v + 2) of obj_tokens / obj_mask -> x [rows, E],
  * mask [rows]. stats = 0 launch_prompt_assemble (x fp32); stats = 1 launch_prompt_assemble_stats (x = the operand-type rows widened, ssq [rows]). */
 int vima_op_prompt_assemble(VimaHandle* h, const int32_t* tok_src, const int64_t* word_ids, const float* word_table, const float* obj_tokens,

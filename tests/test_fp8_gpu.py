@@ -181,6 +181,15 @@ def test_fp8_calibration_has_headroom_and_refuses_non_finite_maxima():
     with pytest.raises(Exception, match="non-finite"):
         bad.forward_prompt_assembly(p)
     assert bad.fp8_act_scales() is None
+    # poison with a NaN and NO inf: one NaN per row of the word-embedding table, in column 0. fmaxf would drop it and the scales would be frozen
+    # from the finite elements; amax_kernel takes the maximum over the magnitude bit patterns, so the NaN reaches the slot and the freeze refuses it
+    sd_nan = {k: v.clone() for k, v in sd.items()}
+    sd_nan[key][:, 0] = float("nan")
+    assert not torch.isinf(sd_nan[key]).any()
+    bad = loaded_policy(cfg, sd_nan, "fp8", dual_stream=0)
+    with pytest.raises(Exception, match="non-finite"):
+        bad.forward_prompt_assembly(p)
+    assert bad.fp8_act_scales() is None
 
 
 def test_fp8_benchmarked_shape_200m_lp1024_against_reference_golden(golden_dir):

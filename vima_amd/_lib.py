@@ -151,6 +151,11 @@ PROTOTYPES = {
     "vima_op_vit_embed": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),
     "vima_op_bbox_l1": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]),
     "vima_op_norm": (ctypes.c_int, [vp, ctypes.POINTER(VimaNormDesc), vp]),
+    "vima_op_fp8_quant": (ctypes.c_int, [vp, vp, c_i64, c_i64, ctypes.c_int, c_f32, vp, c_i64, vp]),
+    "vima_op_fp8_amax": (ctypes.c_int, [vp, vp, c_i64, c_i64, ctypes.c_int, vp, vp]),
+    "vima_op_norm_fp8": (ctypes.c_int, [vp, ctypes.POINTER(VimaNormDesc), vp, c_f32, vp]),
+    "vima_op_vit_attention_fp8": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32, vp, vp]),
+    "vima_op_vit_attention_cls_fp8": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32, vp, vp]),
     "vima_op_prompt_assemble": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]),
     "vima_op_dec_embed": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]),
     "vima_op_dec_embed_step": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp]),

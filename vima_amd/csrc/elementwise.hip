@@ -672,7 +672,9 @@ __global__ __launch_bounds__(256) void quant_fp8_kernel(const bf16_t* __restrict
 __global__ __launch_bounds__(256) void amax_kernel(const bf16_t* __restrict__ in, long long ldin, long long rows, int cols, unsigned* slot) {
   const int cpr = cols >> 3;
   const long long total = rows * cpr;
-  float m = 0.f;
+  // the maximum is taken over the MAGNITUDE BIT PATTERNS as unsigned integers: finite magnitudes order like their values, inf above them and
+  // every NaN pattern above inf, so a NaN activation reaches the slot (fmaxf would drop it) and the freeze refuses it like an inf
+  unsigned m = 0;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const long long r = i / cpr;
     const int c = (int)(i - r * cpr) * 8;
@@ -680,12 +682,13 @@ __global__ __launch_bounds__(256) void amax_kernel(const bf16_t* __restrict__ in
     const uint32_t w[4] = {u.x, u.y, u.z, u.w};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      m = fmaxf(m, fabsf(__uint_as_float(w[j] << 16)));
-      m = fmaxf(m, fabsf(__uint_as_float(w[j] & 0xffff0000u)));
+      m = max(m, (w[j] << 16) & 0x7fffffffu);
+      m = max(m, w[j] & 0x7fff0000u);
     }
   }
-  m = wave_max(m);
-  if ((threadIdx.x & 63) == 0 && m > 0.f && m == m) atomicMax(slot, __float_as_uint(m));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
+  if ((threadIdx.x & 63) == 0 && m > 0) atomicMax(slot, m);
 }
 
 inline unsigned nblk(long long n, int per) { return (unsigned)((n + per - 1) / per); }

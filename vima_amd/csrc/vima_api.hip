@@ -3214,6 +3214,103 @@ int vima_op_norm(VimaHandle* h, const VimaNormDesc* d, vima_stream_t stream) {
   return two ? op_widen(R, o2T, d->out2T, n) : 0;
 }
 
+// ---- the e4m3 producers outside the GEMM epilogue and the calibration's max |x| (tests/test_fp8_producers_gpu.py), one launcher call each.
+// Same conventions; the caller's out8 receives the launcher's bytes directly (nothing to widen). The launchers only emit e4m3 from bf16 operands, so
+// every entry refuses a handle whose operand type is fp32 before anything is written.
+static int op_fp8_begin(VimaHandle* h, const char* fn) {
+  if (int e = op_begin(h, fn)) return e;
+  OP_REQ(h->bf16, "the e4m3 producers read bf16 operands: needs a BF16 / FP8W / FP8 handle");
+  return 0;
+}
+
+// the fp32 rows [rows, ldin] of a caller as the bf16 operand the launcher reads
+static void* op_stage_rows(Run& R, const float* x, long long rows, long long ldin) {
+  void* xT = R.wsT((size_t)(rows * ldin));
+  if (R.err) return nullptr;
+  OTHER(R, launch_cast(x, xT, rows * ldin, true, R.st), "cast");
+  return R.err ? nullptr : xT;
+}
+
+int vima_op_fp8_quant(VimaHandle* h, const float* x, int64_t ldin, int64_t rows, int cols, float inv, uint8_t* out8, int64_t ldo, vima_stream_t stream) {
+  const char* fn = "vima_op_fp8_quant";
+  if (int e = op_fp8_begin(h, fn)) return e;
+  OP_REQ(x && out8, "null argument");
+  OP_REQ(rows >= 0 && cols > 0, "rows must not be negative and cols must be positive");
+  OP_REQ(ldin >= cols && ldo >= cols, "ldin and ldo must be at least cols");
+  if (rows == 0) return 0;
+  Run R{h, (hipStream_t)stream};
+  void* xT = op_stage_rows(R, x, rows, ldin);
+  if (!xT) return R.err;
+  OTHER(R, launch_quant_fp8(xT, ldin, rows, cols, inv, out8, ldo, R.st), "vima_op_fp8_quant: quant_fp8");
+  return R.err;
+}
+
+int vima_op_fp8_amax(VimaHandle* h, const float* x, int64_t ldin, int64_t rows, int cols, float* slot, vima_stream_t stream) {
+  const char* fn = "vima_op_fp8_amax";
+  if (int e = op_fp8_begin(h, fn)) return e;
+  OP_REQ(x && slot, "null argument");
+  OP_REQ(rows >= 0 && cols > 0, "rows must not be negative and cols must be positive");
+  OP_REQ(ldin >= cols, "ldin must be at least cols");
+  if (rows == 0) return 0;
+  Run R{h, (hipStream_t)stream};
+  void* xT = op_stage_rows(R, x, rows, ldin);
+  if (!xT) return R.err;
+  OTHER(R, launch_amax(xT, ldin, rows, cols, slot, R.st), "vima_op_fp8_amax: amax");
+  return R.err;
+}
+
+int vima_op_norm_fp8(VimaHandle* h, const VimaNormDesc* d, uint8_t* out8, float inv8, vima_stream_t stream) {
+  const char* fn = "vima_op_norm_fp8";
+  if (int e = op_fp8_begin(h, fn)) return e;
+  OP_REQ(d && out8, "null argument");
+  OP_REQ(d->kind == VIMA_NORM_LN_T, "kind must be 1 (launch_layernorm_T), the only norm launcher with an e4m3 output");
+  OP_REQ(d->x && d->gamma && d->rows > 0 && d->E > 0, "x, gamma, rows and E are required");
+  OP_REQ(d->ldin >= d->E, "ldin must be at least E");
+  Run R{h, (hipStream_t)stream};
+  const long long n = (long long)d->rows * d->E;
+  void* oT = d->outT ? R.wsT((size_t)n) : nullptr;
+  if (R.err) return R.err;
+  void* xT = op_stage_rows(R, d->x, d->rows, d->ldin);
+  if (!xT) return R.err;
+  OTHER(R, launch_layernorm_T(xT, d->ldin, d->gamma, d->beta, d->eps, d->rms, d->rows, d->E, d->out32, oT, true, R.st, out8, inv8), "vima_op_norm_fp8: layernorm_T");
+  if (R.err) return R.err;
+  return oT ? op_widen(R, oT, d->outT, n) : 0;
+}
+
+int vima_op_vit_attention_fp8(VimaHandle* h, const float* qkv, int M, int S, int W, int heads, int impl, float inv8, uint8_t* out8, vima_stream_t stream) {
+  const char* fn = "vima_op_vit_attention_fp8";
+  if (int e = op_fp8_begin(h, fn)) return e;
+  OP_REQ(qkv && out8, "null argument");
+  OP_REQ(M > 0 && S > 0 && W > 0 && heads > 0, "M, S, W and heads must be positive");
+  OP_REQ(impl >= 0 && impl <= 2, "impl must be 0 (the launcher's choice), 1 (register kernel) or 2 (its 16-score instantiation)");
+  OP_REQ(W % heads == 0 && W / heads == 32, "the head dim W / heads must be 32");
+  Run R{h, (hipStream_t)stream};
+  const long long rows = (long long)M * S;
+  void* oT = R.wsT((size_t)rows * W);   // the operand-type output of the launcher: not written on this path
+  if (R.err) return R.err;
+  void* qT = op_stage_rows(R, qkv, rows, 3LL * W);
+  if (!qT) return R.err;
+  OTHER(R, launch_vit_attn(qT, oT, M, S, W, heads, true, R.st, out8, inv8, impl), "vima_op_vit_attention_fp8: vit_attn");
+  return R.err;
+}
+
+int vima_op_vit_attention_cls_fp8(VimaHandle* h, const float* q, const float* kv, int M, int S, int W, int heads, float inv8, uint8_t* out8, vima_stream_t stream) {
+  const char* fn = "vima_op_vit_attention_cls_fp8";
+  if (int e = op_fp8_begin(h, fn)) return e;
+  OP_REQ(q && kv && out8, "null argument");
+  OP_REQ(M > 0 && S > 0 && W > 0 && heads > 0, "M, S, W and heads must be positive");
+  OP_REQ(W % heads == 0 && W / heads == 32, "the head dim W / heads must be 32");
+  Run R{h, (hipStream_t)stream};
+  void* oT = R.wsT((size_t)M * W);
+  if (R.err) return R.err;
+  void* qT = op_stage_rows(R, q, M, W);
+  if (!qT) return R.err;
+  void* kvT = op_stage_rows(R, kv, (long long)M * S, 2LL * W);
+  if (!kvT) return R.err;
+  OTHER(R, launch_vit_attn_cls(qT, kvT, oT, M, S, W, heads, true, R.st, out8, inv8), "vima_op_vit_attention_cls_fp8: vit_attn_cls");
+  return R.err;
+}
+
 int vima_op_prompt_assemble(VimaHandle* h, const int32_t* tok_src, const int64_t* word_ids, const float* word_table, const float* obj_tokens,
                             const uint8_t* obj_mask, int rows, int E, int stats, float* x, float* ssq, uint8_t* mask, vima_stream_t stream) {
   const char* fn = "vima_op_prompt_assemble";
